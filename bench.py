@@ -12,12 +12,17 @@ weights (default init, noise weights ~N(0, 0.1^2) so the noise path is live), in
 A "step" is one such forward.  Synthesis shards by image with no collective, so N GPUs
 = N independent batches per step: weak scaling; value = N * 32 * K / time.
 
-With the default ``--workload all`` (what the driver runs) the same process then times the two segmentation training
+A plain run (``--gpus N --steps K --warmup W``) builds the generator, warms up, times the K steps and prints the line: the
+headline ``value`` / ``ms_per_step`` and nothing else measured.  ``--dump-outputs DIR`` then writes the last timed step's
+image and activations (seeded inputs: the same in every run) as .npy files, so that two builds can be compared output for
+output.  Everything below -- the image-only rate, the roofline, the CPU baseline, the training legs -- needs ``--full``.
+
+With ``--full`` and the default ``--workload all`` the same process then times the two segmentation training
 steps the metric also names -- BASELINE.json configs[3] EMANet-50 256^2 B=16 fp32 and configs[4] TransUNet R50-ViT-B/16
 512^2 B=8 bf16 -- with the same K, and nests them as ``seg_train: {emanet: {...}, transunet_bf16: {...}}`` (images/s,
 ms/step, roofline with executed vs nominal FLOPs, cpu_baseline); ``value`` stays the synthesis rate.
 
-Two extra objects on the JSON line:
+Two extra objects on the JSON line of a ``--full`` run:
   roofline      dominant kernel (by summed device time) measured live with HIP events on the launch
                 stream: EXECUTED FLOPs per launch / average launch duration vs the fp32 MFMA peak (frac <= 1); the
                 direct-form (algorithmic) count of SURVEY.md 8(d) rides along as algorithmic_tflops / algorithmic_frac.
@@ -69,6 +74,25 @@ def synth_inputs(g, batch, device, seed):
 def step(g, z, noise):
     with torch.no_grad():
         return g([z], noise=noise, return_intermediate_activations=True)
+
+
+DUMP_CAP = {"image": 1 << 22}   # elements written per array (float32); every other array: DUMP_CAP_DEFAULT
+DUMP_CAP_DEFAULT = 1 << 19        # synthesis: 4 Mi + 14 x 512 Ki elements = 44 MiB at most
+
+
+def dump_outputs(path, arrays):
+    """``--dump-outputs DIR``: each array the timed path returned from its last step as ``DIR/<name>.npy``, float32.  One
+    larger than its cap is written as a fixed sample, 1-D: its flat elements at the sorted indices that
+    ``numpy.random.RandomState(crc32(name)).randint(0, numel, cap)`` draws -- the same in every run and every build."""
+    import zlib
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        cap = DUMP_CAP.get(name, DUMP_CAP_DEFAULT)
+        if t.numel() > cap:
+            idx = np.sort(np.random.RandomState(zlib.crc32(name.encode())).randint(0, t.numel(), size=cap))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, f"{name}.npy"), t.float().cpu().numpy())
 
 
 def exec_ratio(kernel_name):
@@ -628,6 +652,22 @@ def bench_synthesis(args, world, rank, device, distributed):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     assert torch.isfinite(out[0]).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"image": out[0], **{f"activation_{k:02d}": v for k, v in sorted(out[1].items())}})
+    n_gpus = world
+    total_images = batch * args.steps * n_gpus
+    result = {
+        "metric": METRIC, "value": round(total_images / elapsed, 2), "unit": "images/s", "n_gpus": n_gpus,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"StyleGAN2 Generator(256,512,8,cm=2).forward, batch {batch} per GPU, explicit noise, "
+                               "return_intermediate_activations=True (BASELINE.json configs[1])",
+                   "batch_per_gpu": batch, "image_size": SIZE, "parallelism": f"replicated x{n_gpus}, "
+                   "images sharded, no collective"},
+        "roofline": None,
+    }
+    if not args.full:   # a plain run: the headline rate, nothing measured besides it
+        return result if rank == 0 else None
     # SURVEY.md §8(d) config 2 asks for both modes: (ii) with the 14 activations returned is `value` above (what
     # dataset creation calls); (i) image only is timed here the same way (same kernels, nothing retained).
     fence()
@@ -645,8 +685,6 @@ def bench_synthesis(args, world, rank, device, distributed):
     if rank != 0:
         return None
 
-    n_gpus = world
-    total_images = batch * args.steps * n_gpus
     prof_steps = min(args.steps, 5)
     agg = kernel_profile(g, z, noise, prof_steps)
     dom_name = max(agg, key=lambda k: agg[k]["ms"])
@@ -676,17 +714,8 @@ def bench_synthesis(args, world, rank, device, distributed):
                                 "executed_tflops": round(v["flops"] * exec_ratio(k) / (v["ms"] * 1e-3) / 1e12, 2) if v["flops"] else None,
                                 "gbs": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["bytes"] else None}
                             for k, v in sorted(agg.items(), key=lambda kv: -kv[1]["ms"])}}
-    result = {
-        "metric": METRIC, "value": round(total_images / elapsed, 2), "unit": "images/s", "n_gpus": n_gpus,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"StyleGAN2 Generator(256,512,8,cm=2).forward, batch {batch} per GPU, explicit noise, "
-                               "return_intermediate_activations=True (BASELINE.json configs[1])",
-                   "batch_per_gpu": batch, "image_size": SIZE, "parallelism": f"replicated x{n_gpus}, "
-                   "images sharded, no collective",
-                   "images_per_s_image_only": round(total_images / elapsed_image_only, 2)},
-        "roofline": roofline,
-    }
+    result["config"]["images_per_s_image_only"] = round(total_images / elapsed_image_only, 2)
+    result["roofline"] = roofline
     if n_gpus == 1 and not args.no_cpu_baseline:
         cb, img_cpu, (z4, noise4) = cpu_baseline(g, seed=1234)
         with torch.no_grad():
@@ -782,8 +811,8 @@ def launch_ranks(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="all", choices=["all", "synthesis", "emanet", "transunet", "dataset", "gan"],
-                    help="all (default, what the driver runs): the synthesis headline + both segmentation training steps on "
-                         "one JSON line")
+                    help="all (default, what the driver runs): the synthesis headline, with --full + both segmentation "
+                         "training steps on one JSON line")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
@@ -794,7 +823,15 @@ def main():
                     help="training workloads at N = 1: skip the data-parallel rehearsal over a world-size-1 RCCL communicator")
     ap.add_argument("--miopen-search", action="store_true",
                     help="training workloads: MIOpen solver search for the library convolutions (minutes at start-up)")
+    ap.add_argument("--full", action="store_true",
+                    help="synthesis / all: besides the headline rate, the image-only rate, the per-kernel roofline, the CPU "
+                         "baseline and (all) the segmentation-training legs; without it a run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="synthesis / all: write the image and activations of the last timed step to DIR/<name>.npy "
+                         "(float32; arrays above a size cap as a fixed seeded sample, see dump_outputs)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload not in ("all", "synthesis"):
+        raise SystemExit("bench.py: --dump-outputs writes the synthesis step's outputs (--workload all or synthesis)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` with no launcher: start the N ranks ourselves (the reference spawns its own workers too,
@@ -836,7 +873,7 @@ def main():
         result = bench_training(args, args.workload, world, rank, device, distributed)
     else:
         result = bench_synthesis(args, world, rank, device, distributed)
-        if args.workload == "all":
+        if args.workload == "all" and args.full:
             # The metric names two numbers: `value` stays the configs[1] synthesis rate; the segmentation training steps of
             # configs[3] (EMANet-50, 256^2, B=16, fp32) and configs[4] (TransUNet R50-ViT-B/16, 512^2, B=8, bf16) are timed
             # next in the same process with the same K, each with its own roofline and CPU baseline.

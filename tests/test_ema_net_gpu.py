@@ -105,10 +105,12 @@ def test_ema_net_label_maps_bit_exact(device, golden_dir):
 
 
 def test_ema_net_step_vs_oracle_fresh_seed(device):
-    """Same step on a seed the golden file has never seen, against the oracle run live on the host."""
+    """Same step on a seed the golden file has never seen, against the oracle run live on the host -- in float64: in fp32
+    the oracle's own loss moves by up to 7e-5 with the host's instruction set and thread count, most of this bound."""
     sd = E.seeded_state_dict(50, 3, seed=31)
     batch = E.seeded_batch(2, 128, 3, seed=32)
-    total, loss_o, mu_o, grads_o = E.train_step(dict(sd), {}, batch)
+    sd64 = {k: v.double() if v.is_floating_point() else v for k, v in sd.items()}
+    total, loss_o, mu_o, grads_o = E.train_step(sd64, {}, {"images": batch["images"].double(), "segmented": batch["segmented"]})
     net = _net(device, 31)
     loss, mu = net(batch["images"].to(device), batch["segmented"].squeeze(1).to(device))
     np.testing.assert_allclose(loss.detach().cpu().numpy(), loss_o.numpy(), rtol=1e-4)

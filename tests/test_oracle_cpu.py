@@ -5,8 +5,8 @@
 (2) both agree with the committed known-answer vectors;
 (3) the functional generator oracle reproduces the golden outputs that tests/golden/make_golden.py
     captured from the UNMODIFIED reference model.py;
-(4) where /root/reference exists (this container) the oracle is bit-identical to the imported
-    reference on a fresh seed -- skipped on the GPU box, where the reference never travels.
+(4) the oracle is bit-identical to what the imported reference computed on a fresh seed
+    (tests/golden/reference_checks.npz, tests/golden/make_golden_reference_checks.py).
 """
 import os
 
@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import c_ops, load_reference, ops_ref
+from oracle import c_ops, ops_ref
 from oracle import stylegan2_ref as R
 
 
@@ -122,32 +122,38 @@ def test_generator_oracle_vs_golden_256(golden_dir):
         np.testing.assert_allclose(sums[:, 1:], g[f"act{k}_sums"][:, 1:], rtol=1e-5)
 
 
-@pytest.mark.skipif(not load_reference.reference_available(), reason="reference tree only exists in the build container")
-def test_oracle_bit_identical_to_imported_reference():
-    ref = load_reference.load_reference_stylegan2()
-    g = ref.Generator(16, 64, 3, channel_multiplier=1).eval()
-    assert [k for k, _ in R.state_dict_schema(16, 64, 3, 1)] == list(g.state_dict().keys())
-    sd = R.seeded_state_dict(16, 64, 3, 1, seed=99)
-    g.load_state_dict(sd, strict=True)
-    z, noise = R.seeded_inputs(16, 3, 64, seed=98)
-    with torch.no_grad():
-        a, acts_a = g([z], noise=noise, return_intermediate_activations=True)
-        b, acts_b = R.generator_forward(sd, [z], noise=noise, return_intermediate_activations=True)
-    assert torch.equal(a, b)
-    for k in acts_a:
-        assert torch.equal(acts_a[k], acts_b[k])
+def _reference_checks():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_golden_reference_checks", os.path.join(
+        os.path.dirname(__file__), "golden", "make_golden_reference_checks.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
 
 
-@pytest.mark.skipif(not load_reference.reference_available(), reason="reference tree only exists in the build container")
-def test_k2_restatements_equal_the_references_own_native_statement():
-    """``upfirdn2d_native`` (op/upfirdn2d.py:152-186), lifted from the reference file with ``ast``, on fresh inputs."""
-    native = load_reference.load_reference_upfirdn2d_native()
-    rng = np.random.RandomState(77)
-    for major, ih, iw, minor, kh, kw, up, down, p0, p1 in [(3, 9, 7, 1, 4, 4, 1, 1, 1, 1), (2, 5, 6, 2, 4, 4, 2, 1, 2, 1),
-                                                           (2, 8, 9, 1, 4, 4, 1, 2, 1, 1), (1, 6, 5, 3, 3, 2, 2, 2, 1, -1),
-                                                           (2, 4, 4, 1, 2, 2, 2, 1, 1, 0)]:
-        x, k = rng.standard_normal((major, ih, iw, minor)), rng.standard_normal((kh, kw))
-        want = native(torch.from_numpy(x), torch.from_numpy(k), up, up, down, down, p0, p1, p0, p1).numpy()
+def test_oracle_bit_identical_to_imported_reference(golden_dir):
+    """The reference Generator(16, 64, 3, cm=1) on seeds 99 / 98 (tests/golden/reference_checks.npz): the oracle's schema is
+    its state_dict, and the oracle reproduces its image and every activation bit for bit -- both computed under the
+    make_golden_reference_checks.PINNED_ENV float kernels, which round alike on every x86-64 host."""
+    mk = _reference_checks()
+    g = _load(golden_dir, "reference_checks.npz")
+    schema = R.state_dict_schema(*mk.GEN16)
+    assert [k for k, _ in schema] == [str(k) for k in g["gen16_names"]]
+    assert [list(s) for _, s in schema] == [[d for d in row if d >= 0] for row in g["gen16_shapes"].tolist()]
+    mine = mk.pinned_gen16(use_reference=False)
+    assert sorted(f"gen16_{k}_sha256" for k in mine) == sorted(k for k in g.files if k.startswith("gen16_") and k.endswith("_sha256"))
+    for k, v in mine.items():
+        np.testing.assert_allclose(mk.strided_slice(v), g[f"gen16_{k}_slice"], rtol=1e-5, atol=1e-6, err_msg=k)
+        assert mk.digest(v) == str(g[f"gen16_{k}_sha256"]), f"{k}: not bit-identical to the reference"
+
+
+def test_k2_restatements_equal_the_references_own_native_statement(golden_dir):
+    """``upfirdn2d_native`` (op/upfirdn2d.py:152-186), lifted from the reference file with ``ast``, on fresh inputs: its
+    outputs are tests/golden/reference_checks.npz ``k2_want<i>``."""
+    mk = _reference_checks()
+    g = _load(golden_dir, "reference_checks.npz")
+    for i, ((x, k), (major, ih, iw, minor, kh, kw, up, down, p0, p1)) in enumerate(zip(mk.k2_inputs(), mk.K2_CASES)):
+        want = g[f"k2_want{i}"]
         got_c = c_ops.upfirdn2d_nhwc(x, k, up, up, down, down, p0, p1, p0, p1)
         got_t = ops_ref.upfirdn2d_nhwc(torch.from_numpy(x), torch.from_numpy(k), up, up, down, down, p0, p1, p0, p1).numpy()
         np.testing.assert_allclose(got_c, want, rtol=0, atol=1e-12)

@@ -5,7 +5,6 @@ Nothing here launches a kernel: schedules, config -> builder -> optimizer wiring
 fixture produced by the reference's own ``load_from``, the epoch-boundary restart of a finite loader, and the
 generator factories under their reference names."""
 import argparse
-import ast
 import importlib.util
 import math
 import os
@@ -19,7 +18,6 @@ from torch import nn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "synthesis-in-style_amd")
-REF = "/root/reference/stylegan_code_finder"
 
 
 def _sgd(lrs):
@@ -39,28 +37,19 @@ def test_clamped_cosine_closed_form():
     assert opt.param_groups[0]["lr"] == 1e-8
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree only exists in the build container")
 def test_clamped_cosine_equals_the_reference_class():
     """The reference class (utils/clamped_cosine.py:8-19) lifted with ``ast`` (its module imports the absent
-    ``pytorch_training``) on top of torch's own CosineAnnealingLR (recursive form) vs the closed form used here."""
-    from torch.optim.lr_scheduler import CosineAnnealingLR
+    ``pytorch_training``) on top of torch's own CosineAnnealingLR (recursive form) vs the closed form used here: the
+    reference's learning rates are tests/golden/reference_checks.npz ``cosine_lrs`` (tests/golden/make_golden_reference_checks.py)."""
     from utils.clamped_cosine import ClampedCosineAnnealingLR
-    path = os.path.join(REF, "utils", "clamped_cosine.py")
-    node = next(n for n in ast.parse(open(path).read()).body if isinstance(n, ast.ClassDef) and n.name == "ClampedCosineAnnealingLR")
-
-    class Base(CosineAnnealingLR):  # the reference forwards ``verbose`` (torch 1.9); torch >= 2.7 dropped the argument
-        def __init__(self, optimizer, T_max, eta_min=0, last_epoch=-1, verbose=False):
-            super().__init__(optimizer, T_max, eta_min, last_epoch)
-
-    scope = {"CosineAnnealingLR": Base}
-    exec(compile(ast.Module(body=[node], type_ignores=[]), path, "exec"), scope)
-    a, b = _sgd([0.009, 0.018]), _sgd([0.009, 0.018])
-    ref = scope["ClampedCosineAnnealingLR"](a, 15, eta_min=1e-8)
+    want = np.load(os.path.join(ROOT, "tests", "golden", "reference_checks.npz"))["cosine_lrs"]
+    assert want.shape == (25, 2)
+    b = _sgd([0.009, 0.018])
     mine = ClampedCosineAnnealingLR(b, 15, eta_min=1e-8)
-    for _ in range(25):
-        a.step(), ref.step(), mine.step()
-        for ga, gb in zip(a.param_groups, b.param_groups):
-            assert gb["lr"] == pytest.approx(ga["lr"], rel=1e-9, abs=1e-15)
+    for step in range(25):
+        b.step(), mine.step()
+        for ga, gb in zip(want[step], b.param_groups):
+            assert gb["lr"] == pytest.approx(float(ga), rel=1e-9, abs=1e-15)
 
 
 def test_get_scheduler_end_iteration_and_warm_restarts():
@@ -261,3 +250,29 @@ def test_bench_line_stays_compact_and_carries_the_training_legs(tmp_path, capsys
     detail = json.load(open(tmp_path / "gpurun_out" / "bench_detail_all.json"))
     assert len(detail["seg_train"]["emanet"]["roofline"]["own_kernels_eager_iteration"]) == 120
     assert len(detail["roofline_tables"]["kernels"]) == 120
+
+
+def test_bench_dump_outputs_writes_float32_and_samples_large_arrays_the_same_way(tmp_path):
+    """bench.py ``--dump-outputs`` (host logic only): arrays under their cap are written whole with their shape, larger ones as
+    the same seeded 1-D sample in every call, everything float32 and within 64 MB for the synthesis step's 15 outputs."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    gen = torch.Generator().manual_seed(3)
+    arrays = {"image": torch.randn(32, 3, 256, 256, generator=gen), "activation_00": torch.randn(32, 512, 4, 4, generator=gen),
+              "activation_13": torch.randn(4, 128, 256, 256, generator=gen).double()}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    for name, t in arrays.items():
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b), name
+        cap = bench.DUMP_CAP.get(name, bench.DUMP_CAP_DEFAULT)
+        if t.numel() <= cap:
+            assert a.shape == tuple(t.shape) and np.array_equal(a, t.float().numpy()), name
+        else:
+            assert a.shape == (cap,), name
+            assert np.isin(a, t.float().numpy().reshape(-1)).all(), name   # elements of the array, not something derived
+    worst = bench.DUMP_CAP["image"] + 14 * bench.DUMP_CAP_DEFAULT
+    assert worst * 4 <= 64e6

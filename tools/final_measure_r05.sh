@@ -3,10 +3,10 @@
 set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/final_r05; mkdir -p $O
-python bench.py --gpus 1 --steps 20 --warmup 5 2> $O/bench.err | grep "^{" > $O/bench.json
+python bench.py --gpus 1 --steps 20 --warmup 5 --full 2> $O/bench.err | grep "^{" > $O/bench.json
 python -c "import json; s=open('$O/bench.json').read(); d=json.loads(s); print(len(s), 'bytes; synth', d['value'], d['roofline']['frac'], {k: (v['images_per_s'], v['roofline']['frac'], v['dp_rehearsal_graph_ms_per_step']) for k, v in d['seg_train'].items()})"
 cp gpurun_out/bench_detail_all.json $O/bench_detail_all.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_syn -- python3 bench.py --workload synthesis --steps 20 --warmup 5 > $O/bench_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_syn -- python3 bench.py --workload synthesis --steps 20 --warmup 5 --full > $O/bench_rocprof.log 2>&1
 grep "^{" $O/bench_rocprof.log > $O/bench_under_rocprof.json
 cp $(find $O/prof_syn -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv
 python tools/step_timeline.py $(find $O/prof_syn -name "*kernel_trace.csv" | head -1) > $O/step_timeline.txt

@@ -12,8 +12,8 @@ OUT=gpurun_out/pmc_traffic_$TAG
 mkdir -p $OUT
 export SIS_STEP_GRAPH=0
 for W in $WORKLOADS; do
-  rocprofv3 --kernel-trace --output-format csv -d $OUT/$W/fetch --pmc FETCH_SIZE -- python3 bench.py --workload $W --steps 2 --warmup 1 --no-cpu-baseline --no-dp-rehearsal > $OUT/$W.fetch.log 2>&1
-  rocprofv3 --kernel-trace --output-format csv -d $OUT/$W/write --pmc WRITE_SIZE -- python3 bench.py --workload $W --steps 2 --warmup 1 --no-cpu-baseline --no-dp-rehearsal > $OUT/$W.write.log 2>&1
+  rocprofv3 --kernel-trace --output-format csv -d $OUT/$W/fetch --pmc FETCH_SIZE -- python3 bench.py --workload $W --steps 2 --warmup 1 --no-cpu-baseline --no-dp-rehearsal --full > $OUT/$W.fetch.log 2>&1
+  rocprofv3 --kernel-trace --output-format csv -d $OUT/$W/write --pmc WRITE_SIZE -- python3 bench.py --workload $W --steps 2 --warmup 1 --no-cpu-baseline --no-dp-rehearsal --full > $OUT/$W.write.log 2>&1
   echo "pmc passes of $W done"
 done
 python3 tools/pmc_traffic.py $OUT gpurun_out/traffic_$TAG.json $WORKLOADS

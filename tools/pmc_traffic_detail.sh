@@ -6,7 +6,7 @@ TAG=${1:-r03}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/pmc_traffic_detail_$TAG
 mkdir -p $OUT
-CMD="python3 bench.py --workload synthesis --steps 2 --warmup 1 --no-cpu-baseline"
+CMD="python3 bench.py --workload synthesis --steps 2 --warmup 1 --no-cpu-baseline --full"
 rocprofv3 --kernel-trace --output-format csv -d $OUT/p1 --pmc FETCH_SIZE -- $CMD > $OUT/p1.log 2>&1
 rocprofv3 --kernel-trace --output-format csv -d $OUT/p2 --pmc WRITE_SIZE -- $CMD > $OUT/p2.log 2>&1
 rocprofv3 --kernel-trace --output-format csv -d $OUT/p3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum -- $CMD > $OUT/p3.log 2>&1

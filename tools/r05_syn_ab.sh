@@ -6,7 +6,7 @@ python -m pytest tests/test_generator_gpu.py -x -q -m gpu -k "tail_split or batc
 tail -2 $O/tests.log
 for round in 1 2; do
  for parts in 1 2 4; do
-  SIS_RGB_TAIL_SPLIT=$parts python bench.py --workload synthesis --steps 40 --warmup 5 --no-cpu-baseline 2> $O/err.txt | grep "^{" > $O/out.json
+  SIS_RGB_TAIL_SPLIT=$parts python bench.py --workload synthesis --steps 40 --warmup 5 --no-cpu-baseline --full 2> $O/err.txt | grep "^{" > $O/out.json
   python -c "import json; d=json.load(open('$O/out.json')); print('parts $parts round $round', d['value'], d['ms_per_step'])" | tee -a $O/ab.txt
  done
 done
