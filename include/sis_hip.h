@@ -668,6 +668,55 @@ int sis_ce_dice_fwd(float* out3, float* stats, float* workspace, const void* log
 int sis_ce_dice_bwd(void* grad_logits, const void* logits, int dtype, const int64_t* labels, const float* stats,
                     const float* grad_loss, int batch, int classes, int hw, void* stream);
 
+/* ---- DocUFCN segmenter (networks/doc_ufcn/doc_ufcn.py:11-101, training_builder/doc_ufcn_train_builder.py:18-33), fp32 NCHW
+ * (csrc/doc_ufcn.hip).
+ *   sis_dconv3x3           out [B][Cout][H][W] = conv2d(x, weight [Cout][Cin][3][3], bias or NULL, stride 1, padding = dilation,
+ *                          dilation); any Cin, Cout >= 1.  Data gradient: the same call on sis_dconv3x3_adjoint's weights
+ *                          (wa [Cin][Cout][3][3] = weight with the channel axes swapped and the taps rotated by 180 degrees).
+ *   sis_dconv3x3_wgrad     dw [Cout][Cin][taps] from grad_output [B][Cout][H][W] and x [B][Cin][H][W]: taps 9 = the dilated 3x3
+ *                          convolution above, taps 1 = a 1x1 product.  Fixed pixel slices summed in order.
+ *   sis_channel_sum        out [C] = sum over batch and pixels of x [B][C][HW] (bias gradients), fixed order.
+ *   sis_pixel_shuffle2     out [B][C][2H][2W] from in [B][4C][H][W] (nn.PixelShuffle(2) order) + bias [C] or NULL; inverse = 1:
+ *                          out [B][4C][H][W] from in [B][C][2H][2W] (its gradient).  The wide map's samples are
+ *                          wide_batch_stride floats apart (a channel slice of a wider buffer).
+ *   sis_transpose2d        out [cols][rows] = in [rows][cols]^T.
+ *   sis_bn_drop_fwd        y = dropout(relu(gamma * (x - mean) * invstd + beta)), y written with a batch stride (a channel slice of
+ *                          a wider buffer); train mode: mean / invstd from sis_bn_stats, dropout of element e drawn from the
+ *                          counter stream (seed word, site, quad e / 4), mask (sis_bn_mask_words int64 words, or NULL) = one bit
+ *                          per element: (relu output > 0) & kept.  eval = 1: invstd_or_var is the running variance, no dropout.
+ *   sis_bn_drop_bwd        dx, dgamma, dbeta from dy (batch stride dy_batch_stride) + dy2 (contiguous, or NULL) and the mask.
+ *   sis_weighted_ce_fwd    loss[0] = sum w[y] nll / sum w[y] (nn.CrossEntropyLoss(weight=w)); stats[0] = sum w[y]; weight NULL = 1.
+ *   sis_weighted_ce_bwd    grad_logits = grad_loss[0] * d loss / d logits.
+ *   sis_adam_clip_step     clip_grad_norm_(all gradients of the table, max_norm) then torch.optim.Adam (L2 weight decay added to the
+ *                          gradient), one norm launch + one update launch.  table rows: param, grad, exp_avg, exp_avg_sq,
+ *                          count | group << 48 (chunks of sis_adam_chunk_elems); hyper float[21]: {lr, beta1, beta2, eps,
+ *                          weight_decay} per group (<= 4), max_norm; step: device int32 counter, incremented by the call;
+ *                          partial: float[n_chunks]. */
+int sis_dconv3x3(float* out, const float* x, const float* weight, const float* bias, int batch, int cin, int cout, int h, int w,
+                 int dilation, void* stream);
+int sis_dconv3x3_adjoint(float* wa, const float* weight, int cin, int cout, void* stream);
+int64_t sis_dconv3x3_wgrad_workspace_floats(int batch, int cin, int cout, int h, int w, int taps);
+int sis_dconv3x3_wgrad(float* dw, const float* grad_output, const float* x, float* workspace, int64_t workspace_floats, int batch,
+                       int cin, int cout, int h, int w, int dilation, int taps, void* stream);
+int sis_channel_sum(float* out, const float* x, int batch, int channels, int hw, void* stream);
+int sis_pixel_shuffle2(float* out, const float* in, const float* bias, int batch, int channels, int h, int w,
+                       int64_t wide_batch_stride, int inverse, void* stream);
+int sis_transpose2d(float* out, const float* in, int rows, int cols, void* stream);
+int64_t sis_bn_drop_bwd_workspace_floats(int batch, int channels, int hw);
+int sis_bn_drop_fwd(float* y, int64_t y_batch_stride, const float* x, const float* mean, const float* invstd_or_var,
+                    const float* gamma, const float* beta, int batch, int channels, int hw, int eval, float eps, const void* seed,
+                    int site, float drop_p, void* mask, void* stream);
+int sis_bn_drop_bwd(float* dx, float* dgamma, float* dbeta, const float* dy, int64_t dy_batch_stride, const float* dy2,
+                    const float* x, const float* mean, const float* invstd, const float* gamma, const void* mask, float drop_p,
+                    float* workspace, int batch, int channels, int hw, void* stream);
+int sis_weighted_ce_workspace_floats(void);
+int sis_weighted_ce_fwd(float* loss, float* stats, float* workspace, const float* logits, const int64_t* labels, const float* weight,
+                        int batch, int classes, int hw, void* stream);
+int sis_weighted_ce_bwd(float* grad_logits, const float* grad_loss, const float* logits, const int64_t* labels, const float* weight,
+                        const float* stats, int batch, int classes, int hw, void* stream);
+int sis_adam_chunk_elems(void);
+int sis_adam_clip_step(const int64_t* table, int n_chunks, float* partial, const float* hyper, int* step, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,21 @@ _SIGNATURES = {
     "sis_conv1x1_bf16_wgrad_supported": ([_i] * 4 + [_i64], _i),
     "sis_conv1x1_bf16_wgrad": ([_vp, _i, _vp, _vp] + [_i] * 4 + [_vp, _i64, _vp], _i),
     "sis_conv1x1_bf16_wgrad_multi": ([_vp, _i, _vp, _vp] + [_i] * 5 + [_vp, _i64, _vp], _i),
+    "sis_dconv3x3": ([_vp] * 4 + [_i] * 6 + [_vp], _i),
+    "sis_dconv3x3_adjoint": ([_vp, _vp, _i, _i, _vp], _i),
+    "sis_dconv3x3_wgrad_workspace_floats": ([_i] * 6, _i64),
+    "sis_dconv3x3_wgrad": ([_vp] * 4 + [_i64] + [_i] * 7 + [_vp], _i),
+    "sis_channel_sum": ([_vp, _vp, _i, _i, _i, _vp], _i),
+    "sis_pixel_shuffle2": ([_vp] * 3 + [_i] * 4 + [_i64, _i, _vp], _i),
+    "sis_transpose2d": ([_vp, _vp, _i, _i, _vp], _i),
+    "sis_bn_drop_bwd_workspace_floats": ([_i] * 3, _i64),
+    "sis_bn_drop_fwd": ([_vp, _i64] + [_vp] * 5 + [_i] * 4 + [_f, _vp, _i, _f, _vp, _vp], _i),
+    "sis_bn_drop_bwd": ([_vp] * 4 + [_i64] + [_vp] * 6 + [_f, _vp, _i, _i, _i, _vp], _i),
+    "sis_weighted_ce_workspace_floats": ([], _i),
+    "sis_weighted_ce_fwd": ([_vp] * 6 + [_i] * 3 + [_vp], _i),
+    "sis_weighted_ce_bwd": ([_vp] * 6 + [_i] * 3 + [_vp], _i),
+    "sis_adam_chunk_elems": ([], _i),
+    "sis_adam_clip_step": ([_vp, _i, _vp, _vp, _vp, _vp], _i),
 }
 
 
@@ -2202,3 +2217,209 @@ def bn_act_bwd(dy, y, x, mean, invstd, gamma, relu, want_residual_grad, mask=Non
             _ptr(invstd), _ptr(gamma), _ptr(ws), b, c, h * w, int(bool(relu)), _ptr(mask), _stream())),
                "sis_bn_act_bwd")
     return dx, dres, dgamma, dbeta
+
+
+# ------------------------------------------------------------------------------ DocUFCN (csrc/doc_ufcn.hip)
+
+
+def _dense_f32(t, name):
+    """fp32, on the device, already contiguous: the DocUFCN wrappers never copy (a hidden ``.contiguous()`` is an ATen kernel)."""
+    require_device(t, name)
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.data_ptr() % 16:
+        raise RuntimeError(f"{name}: a contiguous, 16-byte aligned float32 tensor is required ({t.dtype}, {tuple(t.stride())})")
+    return t
+
+
+def dconv3x3(x, weight, bias=None, dilation=1):
+    """conv2d(x, weight [Cout,Cin,3,3], bias, stride 1, padding = dilation, dilation) on the fp32 MFMA kernel."""
+    x, weight = _dense_f32(x, "input"), _dense_f32(weight, "weight")
+    b, cin, h, w = x.shape
+    cout = weight.shape[0]
+    if tuple(weight.shape) != (cout, cin, 3, 3):
+        raise RuntimeError(f"dconv3x3: weight {tuple(weight.shape)} does not fit {cin} input channels")
+    if bias is not None:
+        bias = _dense_f32(bias, "bias")
+    out = torch.empty((b, cout, h, w), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(_launch("dconv3x3_kernel", 2.0 * b * cout * cin * 9 * h * w, 4.0 * (x.numel() + out.numel()),
+                       lambda: lib().sis_dconv3x3(_ptr(out), _ptr(x), _ptr(weight), _ptr(bias), b, cin, cout, h, w, int(dilation),
+                                                  _stream())), "sis_dconv3x3")
+    return out
+
+
+def dconv3x3_adjoint(weight):
+    """[Cout,Cin,3,3] -> [Cin,Cout,3,3] with the taps rotated by 180 degrees: ``dconv3x3(dy, adjoint)`` is the data gradient."""
+    weight = _dense_f32(weight, "weight")
+    cout, cin = weight.shape[:2]
+    wa = torch.empty((cin, cout, 3, 3), dtype=torch.float32, device=weight.device)
+    with torch.cuda.device(weight.device):
+        _check(lib().sis_dconv3x3_adjoint(_ptr(wa), _ptr(weight), cin, cout, _stream()), "sis_dconv3x3_adjoint")
+    return wa
+
+
+def dconv3x3_wgrad(grad_output, x, dilation=1, taps=9):
+    """dW [Cout,Cin,3,3] (taps 9) or [Cout,Cin,1,1] (taps 1) from dL/dy and x; deterministic."""
+    grad_output, x = _dense_f32(grad_output, "grad_output"), _dense_f32(x, "input")
+    b, cin, h, w = x.shape
+    cout = grad_output.shape[1]
+    k = 3 if taps == 9 else 1
+    dw = torch.empty((cout, cin, k, k), dtype=torch.float32, device=x.device)
+    n_ws = int(lib().sis_dconv3x3_wgrad_workspace_floats(b, cin, cout, h, w, taps))
+    ws = torch.empty(max(n_ws, 4), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(_launch("dconv3x3_wgrad_kernel", 2.0 * b * cout * cin * taps * h * w, 4.0 * (x.numel() + grad_output.numel()),
+                       lambda: lib().sis_dconv3x3_wgrad(_ptr(dw), _ptr(grad_output), _ptr(x), _ptr(ws), n_ws, b, cin, cout, h, w,
+                                                        int(dilation), int(taps), _stream())), "sis_dconv3x3_wgrad")
+    return dw
+
+
+def channel_sum(x):
+    """[B,C,H,W] -> [C]: the bias gradient of a layer whose output gradient is x (fixed order)."""
+    x = _dense_f32(x, "input")
+    b, c = x.shape[:2]
+    out = torch.empty(c, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(lib().sis_channel_sum(_ptr(out), _ptr(x), b, c, x[0, 0].numel(), _stream()), "sis_channel_sum")
+    return out
+
+
+def pixel_shuffle2(x, bias=None, out=None, channel_offset=0):
+    """nn.PixelShuffle(2) (+ per-channel bias) of x [B,4C,H,W] -> [B,C,2H,2W].  ``out``: a contiguous [B, C', 2H, 2W] buffer whose
+    channels [channel_offset, channel_offset + C) receive the result (returned)."""
+    x = _dense_f32(x, "input")
+    b, c4, h, w = x.shape
+    c = c4 // 4
+    if bias is not None:
+        bias = _dense_f32(bias, "bias")
+    if out is None:
+        out, channel_offset = torch.empty((b, c, 2 * h, 2 * w), dtype=torch.float32, device=x.device), 0
+    out = _dense_f32(out, "out")
+    if out.shape[0] != b or tuple(out.shape[2:]) != (2 * h, 2 * w) or channel_offset + c > out.shape[1]:
+        raise RuntimeError("pixel_shuffle2: output buffer does not fit")
+    dst = ctypes.c_void_p(out.data_ptr() + 4 * channel_offset * 4 * h * w)
+    with torch.cuda.device(x.device):
+        _check(lib().sis_pixel_shuffle2(dst, _ptr(x), _ptr(bias), b, c, h, w, out.shape[1] * 4 * h * w, 0, _stream()),
+               "sis_pixel_shuffle2")
+    return out
+
+
+def pixel_shuffle2_grad(g, channels=None, channel_offset=0):
+    """Gradient of ``pixel_shuffle2``: channels [channel_offset, channel_offset + channels) of g [B, C', 2H, 2W] -> [B, 4C, H, W]."""
+    g = _dense_f32(g, "grad_output")
+    b, ctot, h2, w2 = g.shape
+    c = ctot - channel_offset if channels is None else channels
+    h, w = h2 // 2, w2 // 2
+    out = torch.empty((b, 4 * c, h, w), dtype=torch.float32, device=g.device)
+    src = ctypes.c_void_p(g.data_ptr() + 4 * channel_offset * h2 * w2)
+    with torch.cuda.device(g.device):
+        _check(lib().sis_pixel_shuffle2(_ptr(out), src, None, b, c, h, w, ctot * h2 * w2, 1, _stream()), "sis_pixel_shuffle2")
+    return out
+
+
+def max_pool2x2_slice(buf, channel_offset, channels):
+    """2x2 / stride-2 max pooling of channels [channel_offset, channel_offset + channels) of a contiguous [B, C', H, W] buffer ->
+    (out [B, channels, H/2, W/2], argmax): one ``sis_max_pool2d`` launch per sample (its planes are contiguous there)."""
+    buf = _dense_f32(buf, "input")
+    b, ctot, h, w = buf.shape
+    out = torch.empty((b, channels, h // 2, w // 2), dtype=torch.float32, device=buf.device)
+    arg = torch.empty((b, channels, h // 2, w // 2), dtype=torch.uint8, device=buf.device)
+    plane_out = channels * (h // 2) * (w // 2)
+    with torch.cuda.device(buf.device):
+        for i in range(b):
+            src = buf.data_ptr() + 4 * (i * ctot + channel_offset) * h * w
+            _check(lib().sis_max_pool2d(ctypes.c_void_p(out.data_ptr() + 4 * i * plane_out), ctypes.c_void_p(arg.data_ptr() + i * plane_out),
+                                        ctypes.c_void_p(src), F32, channels, h, w, h // 2, w // 2, 2, 2, 0, 0, _stream()),
+                   "sis_max_pool2d")
+    return out, arg
+
+
+def transpose2d(x):
+    x = _dense_f32(x, "input")
+    rows, cols = x.shape
+    out = torch.empty((cols, rows), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(lib().sis_transpose2d(_ptr(out), _ptr(x), rows, cols, _stream()), "sis_transpose2d")
+    return out
+
+
+def bn_drop_fwd(x, mean, invstd_or_var, gamma, beta, eval_mode=False, eps=1e-5, seed=None, site=0, drop_p=0.0, out=None,
+                channel_offset=0, want_mask=True):
+    """y = dropout(relu(bn(x))) -> (y, mask).  ``out``: a wider [B, C', H, W] buffer whose channels
+    [channel_offset, channel_offset + C) receive y (returned instead of a fresh tensor)."""
+    x = _dense_f32(x, "input")
+    b, c, h, w = x.shape
+    if out is None:
+        out, bstride, y = torch.empty_like(x), c * h * w, None
+    else:
+        if out.dim() != 4 or tuple(out.shape[2:]) != (h, w) or out.shape[0] != b or not out.is_contiguous() \
+                or channel_offset + c > out.shape[1]:
+            raise RuntimeError("bn_drop_fwd: out must be a contiguous [B, >= offset + C, H, W] buffer")
+        bstride, y = out.shape[1] * h * w, out
+    mask = torch.empty(lib().sis_bn_mask_words(b, c, h * w), dtype=torch.int64, device=x.device) if want_mask else None
+    dst = out.data_ptr() + 4 * channel_offset * h * w
+    with torch.cuda.device(x.device):
+        _check(lib().sis_bn_drop_fwd(ctypes.c_void_p(dst), bstride, _ptr(x), _ptr(mean), _ptr(invstd_or_var), _ptr(gamma),
+                                     _ptr(beta), b, c, h * w, int(bool(eval_mode)), float(eps), _ptr(seed), int(site),
+                                     float(drop_p), _ptr(mask), _stream()), "sis_bn_drop_fwd")
+    return (out if y is None else y), mask
+
+
+def bn_drop_bwd(dy, x, mean, invstd, gamma, mask, drop_p, channel_offset=0, dy2=None):
+    """Backward of ``bn_drop_fwd`` -> (dx, dgamma, dbeta).  dy may be a wider [B, C', H, W] buffer whose channels
+    [channel_offset, channel_offset + C) are y's gradient; ``dy2`` (contiguous, x's shape) is added to it."""
+    x = _dense_f32(x, "input")
+    b, c, h, w = x.shape
+    if dy is None:
+        dy, channel_offset = dy2, 0
+        dy2 = None
+    dy = _dense_f32(dy, "grad_output")
+    if dy.dim() != 4 or dy.shape[0] != b or tuple(dy.shape[2:]) != (h, w) or channel_offset + c > dy.shape[1]:
+        raise RuntimeError("bn_drop_bwd: grad_output must be a [B, >= offset + C, H, W] buffer")
+    if dy2 is not None:
+        dy2 = _dense_f32(dy2, "grad_output")
+    dx = torch.empty_like(x)
+    dgamma = torch.empty(c, dtype=torch.float32, device=x.device)
+    dbeta = torch.empty(c, dtype=torch.float32, device=x.device)
+    ws = torch.empty(int(lib().sis_bn_drop_bwd_workspace_floats(b, c, h * w)), dtype=torch.float32, device=x.device)
+    src = dy.data_ptr() + 4 * channel_offset * h * w
+    with torch.cuda.device(x.device):
+        _check(lib().sis_bn_drop_bwd(_ptr(dx), _ptr(dgamma), _ptr(dbeta), ctypes.c_void_p(src), dy.shape[1] * h * w, _ptr(dy2),
+                                     _ptr(x), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(mask), float(drop_p), _ptr(ws), b, c,
+                                     h * w, _stream()), "sis_bn_drop_bwd")
+    return dx, dgamma, dbeta
+
+
+def weighted_ce_fwd(logits, labels, weight=None):
+    """nn.CrossEntropyLoss(weight=weight)(logits [B,K,H,W], labels [B,H,W] int64) -> (loss [1], stats [1] = sum of weights)."""
+    logits, weight = _dense_f32(logits, "logits"), (None if weight is None else _dense_f32(weight, "weight"))
+    require_device(labels, "labels")
+    if labels.dtype != torch.int64 or not labels.is_contiguous():
+        raise RuntimeError("weighted_ce_fwd: labels must be a contiguous int64 tensor")
+    b, k, h, w = logits.shape
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    stats = torch.empty(1, dtype=torch.float32, device=logits.device)
+    ws = torch.empty(lib().sis_weighted_ce_workspace_floats(), dtype=torch.float32, device=logits.device)
+    with torch.cuda.device(logits.device):
+        _check(lib().sis_weighted_ce_fwd(_ptr(loss), _ptr(stats), _ptr(ws), _ptr(logits), _ptr(labels), _ptr(weight), b, k, h * w,
+                                         _stream()), "sis_weighted_ce_fwd")
+    return loss, stats
+
+
+def weighted_ce_bwd(grad_loss, logits, labels, weight, stats):
+    grad_loss = _dense_f32(grad_loss.reshape(1), "grad_loss")
+    b, k, h, w = logits.shape
+    grad = torch.empty_like(logits)
+    with torch.cuda.device(logits.device):
+        _check(lib().sis_weighted_ce_bwd(_ptr(grad), _ptr(grad_loss), _ptr(logits), _ptr(labels), _ptr(weight), _ptr(stats), b, k,
+                                         h * w, _stream()), "sis_weighted_ce_bwd")
+    return grad
+
+
+def adam_chunk_elems():
+    return int(lib().sis_adam_chunk_elems())
+
+
+def adam_clip_step(table, n_chunks, partial, hyper, step):
+    with torch.cuda.device(table.device):
+        _check(lib().sis_adam_clip_step(_ptr(table), int(n_chunks), _ptr(partial), _ptr(hyper), _ptr(step), _stream()),
+               "sis_adam_clip_step")

@@ -137,3 +137,52 @@ class TransUNetUpdater(_GraphedUpdater):
             loss.backward()
 
         return {'combined': loss.detach(), 'CE': loss_ce.detach(), 'Dice': loss_dice.detach()}
+
+
+class _WeightedCeFn(torch.autograd.Function):
+    """nn.CrossEntropyLoss(weight=class_weights) on full-resolution fp32 logits, one pass each way (csrc/doc_ufcn.hip)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, class_weights):
+        loss, stats = sis_hip.weighted_ce_fwd(logits, labels, class_weights)
+        ctx.save_for_backward(logits, labels, class_weights, stats)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        logits, labels, class_weights, stats = ctx.saved_tensors
+        return sis_hip.weighted_ce_bwd(grad_loss, logits, labels, class_weights, stats), None, None
+
+
+def weighted_cross_entropy(prediction, ground_truth, class_weights):
+    """``nn.CrossEntropyLoss(weight=class_weights)(prediction, ground_truth)``: the HIP kernels for fp32 logits on the device,
+    plain torch on the CPU (on a HIP device through ``sis_hip.library_call``)."""
+    if prediction.is_cuda and prediction.dtype == torch.float32 and prediction.is_contiguous():
+        labels = ground_truth if ground_truth.dtype == torch.int64 else ground_truth.long()
+        return _WeightedCeFn.apply(prediction, labels.contiguous(), class_weights)
+    if prediction.is_cuda:
+        sis_hip.library_call('weighted_cross_entropy')
+    return nn.functional.cross_entropy(prediction, ground_truth.long(), weight=class_weights)
+
+
+class StandardUpdater(_GraphedUpdater):
+    """DocUFCN's iteration (reference: updater/segmentation_updater.py:11-40): zero_grad -> forward -> class-weighted CE ->
+    backward -> step; reports ``loss/softmax``."""
+
+    def __init__(self, *args, **kwargs):
+        class_weights = kwargs.pop('class_weights')
+        super().__init__(*args, **kwargs)
+        self.class_weights = torch.as_tensor(class_weights, dtype=torch.float32).to(self.device).contiguous()
+        self._seed_grad = None   # d loss / d loss, allocated once (loss.backward() would launch a fill kernel every step)
+
+    def _iteration(self, batch):
+        network = self.networks['segmentation']
+        optimizer = self.optimizers['main']
+        optimizer.zero_grad()
+        prediction = network(batch['images'])
+        loss = weighted_cross_entropy(prediction, torch.squeeze(batch['segmented'], dim=1), self.class_weights)
+        if self._seed_grad is None or self._seed_grad.device != loss.device:
+            self._seed_grad = torch.ones((), dtype=loss.dtype, device=loss.device)
+        loss.backward(self._seed_grad)
+        optimizer.step()
+        return {'softmax': loss.detach()}
