@@ -717,6 +717,25 @@ int sis_weighted_ce_bwd(float* grad_logits, const float* grad_loss, const float*
 int sis_adam_chunk_elems(void);
 int sis_adam_clip_step(const int64_t* table, int n_chunks, float* partial, const float* hyper, int* step, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * DatasetGAN labelling (csrc/pixel_ensemble.hip): PixelEnsembleClassifier.predict_classes on the bilinearly upsampled
+ * generator activations (reference segmentation/dataset_gan_segmenter.py, data/dataset_gan_dataset.py:12-34,
+ * networks/pixel_classifier/model.py:13-121), eval mode, fp32, without the [B, S, S, F] feature tensor.
+ * _project: for each of `ngroups` activation resolutions r below the output size, out[B][r*r][m] = wt[K][m]^T . act,
+ *   where act is the K range over one or two layers [B][c][r*r]; `groups` is a HOST array of 7 int64 per group:
+ *   {r, wt, out, act0, act1, c0, c1} (c1 = 0: one layer; c0, c1 multiples of 32; m a multiple of 128).
+ * _head: labels[B][S*S] (int64) = the members' majority vote (ties: torch.mode on the device) of argmax over classes of
+ *   W3 relu(W2 relu(W1f . act_full + sum_r up(P_r) + b1) + b2) + b3, BatchNorm folded into W2 / W3 by the caller.
+ *   `full`: HOST {act0, act1, c0, c1} of the full-resolution layers (c0 = 0: none); `proj`: HOST {P_r, r} pairs.
+ *   w1f [Kf][members*hidden1], b1 [members*hidden1], w2t [members][hidden1][H2], b2 [members][H2],
+ *   w3t [members][H2][CP], b3 [members][CP] with (hidden1, H2, CP) = (128, 32, 32) for 2..31 classes, (256, 128, 64) for 32..64.
+ *   rgb (optional) [B][S*S][3] = lut[label]; logits (optional, tests) [members][B][S*S][classes]. */
+int sis_pixel_ensemble_project(const int64_t* groups, int ngroups, int batch, int m, void* stream);
+int sis_pixel_ensemble_head(const int64_t* full, const int64_t* proj, int nproj, const float* w1f, const float* b1,
+                            const float* w2t, const float* b2, const float* w3t, const float* b3, const uint8_t* lut,
+                            int64_t* labels, uint8_t* rgb, float* logits, int batch, int size, int members, int classes,
+                            int hidden1, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

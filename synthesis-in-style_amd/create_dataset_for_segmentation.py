@@ -11,6 +11,10 @@ extraction / filtering / rendering of the label image, COCO ground truth, train/
 PNG is therefore the raw cluster-id map of ``label_layer`` (id * 255 // (K-1) grey levels) instead of the rendered
 class colours.
 
+``segmenter_type: "dataset_gan"`` in the config (with ``class_to_color_map`` and ``--classifier-path``, as the
+reference's :52-81) labels every image with a trained PixelEnsembleClassifier instead
+(segmentation/dataset_gan_segmenter.py, fused on the device); the label half of the PNG is then the class-colour image.
+
 Multi-GPU (BASELINE.json configs[2]: 100k images on 8 GPUs): one process per GPU (``torch.distributed.run`` or
 manual RANK/WORLD_SIZE), rank r generates the image-id range ``shard_range(num_images, r, world)``; no collective.
 The latent stream is one global seeded stream: every rank draws the whole stream in batch order and keeps its own
@@ -53,6 +57,20 @@ def load_generator(checkpoint, size, latent_size, n_mlp, channel_multiplier, dev
     return g.to(device).eval()
 
 
+def dataset_gan_segmenter(g, classifier_path, creation_config, mean_latent, device):
+    """The reference's get_dataset_gan_params + get_dataset_segmenter (:28-81): one probe forward (B = 1, before the
+    dataset's seed is set) gives the activation layout, i.e. the feature size and one bilinear upsampler per layer."""
+    from segmentation.dataset_gan_segmenter import DatasetGANSegmenter, dataset_gan_upsamplers
+    if not classifier_path:
+        raise ValueError('segmenter_type "dataset_gan" needs --classifier-path (the trained ensemble checkpoint)')
+    with torch.no_grad():
+        _, acts = g([torch.randn(1, g.style_dim, device=device)], noise=g.make_noise(), return_intermediate_activations=True,
+                    truncation=0.7 if mean_latent is not None else 1, truncation_latent=mean_latent)
+    return DatasetGANSegmenter(base_dir=None, image_size=g.size, class_to_color_map=creation_config['class_to_color_map'],
+                               classifier_path=classifier_path, feature_size=sum(a.shape[1] for a in acts.values()),
+                               upsamplers=dataset_gan_upsamplers(acts, g.size))
+
+
 def build_dataset(args, creation_config, rank=0, world_size=1):
     device = torch.device('cuda', rank % max(torch.cuda.device_count(), 1))
     torch.cuda.set_device(device)
@@ -63,6 +81,9 @@ def build_dataset(args, creation_config, rank=0, world_size=1):
         catalogs[int(layer)] = FactorCatalog(cluster_centers=numpy.load(path))
     label_layer = int(creation_config.get('label_layer', max(catalogs) if catalogs else -1))
     mean_latent = g.mean_latent(4096) if args.truncate else None
+    dataset_gan = None
+    if creation_config.get('segmenter_type') == 'dataset_gan':
+        dataset_gan = dataset_gan_segmenter(g, getattr(args, 'classifier_path', None), creation_config, mean_latent, device)
     lo, hi = shard_range(args.num_images, rank, world_size)
     save_dir = Path(args.save_to) if args.save_to else None
     torch.random.manual_seed(creation_config.get('seed', 1))
@@ -76,7 +97,9 @@ def build_dataset(args, creation_config, rank=0, world_size=1):
         if save_dir is None:
             return
         rgb = pixels.cpu().numpy()
-        if label_layer in labels:
+        if dataset_gan is not None:
+            lab_img = labels["dataset_gan"].cpu().numpy()
+        elif label_layer in labels:
             k = catalogs[label_layer].cluster_centers.shape[0]
             lab = labels[label_layer]
             if lab.shape[-1] != rgb.shape[2]:
@@ -104,7 +127,7 @@ def build_dataset(args, creation_config, rank=0, world_size=1):
             if (a, b) != (first, first + n):
                 image = image[a - first:b - first]
                 acts = {k: v[a - first:b - first] for k, v in acts.items()}
-            job = (a,) + label_and_encode(image, acts, catalogs)  # side stream; the next batch's forward is issued first
+            job = (a,) + label_and_encode(image, acts, catalogs, dataset_gan)  # side stream; the next batch's forward is issued first
             if pending is not None:
                 flush(pending)
             pending = job
@@ -125,9 +148,11 @@ def main(args):
 if __name__ == "__main__":
     parser = argparse.ArgumentParser(description="Generate a synthetic dataset with a StyleGAN2 generator on MI355X")
     parser.add_argument("checkpoint", nargs='?', default=None, help="generator checkpoint holding 'g_ema' (omit: random weights)")
-    parser.add_argument("config", nargs='?', default=None, help="json: image_size, latent_size, seed, catalogs{layer: centres.npy}, label_layer")
+    parser.add_argument("config", nargs='?', default=None, help="json: image_size, latent_size, seed, catalogs{layer: centres.npy}, label_layer; "
+                        "or segmenter_type 'dataset_gan' with class_to_color_map")
     parser.add_argument("-n", "--num-images", type=int, default=100)
     parser.add_argument("-s", "--save-to", help="directory for the PNG pairs (omit: generate only)")
     parser.add_argument("-b", "--batch-size", default=10, type=int)
     parser.add_argument("--truncate", action='store_true', default=False, help="truncation trick (psi 0.7, mean of 4096 latents)")
+    parser.add_argument("--classifier-path", help="trained PixelEnsembleClassifier checkpoint (segmenter_type \"dataset_gan\")")
     main(parser.parse_args())

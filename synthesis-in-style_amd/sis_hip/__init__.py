@@ -160,6 +160,8 @@ _SIGNATURES = {
     "sis_weighted_ce_bwd": ([_vp] * 6 + [_i] * 3 + [_vp], _i),
     "sis_adam_chunk_elems": ([], _i),
     "sis_adam_clip_step": ([_vp, _i, _vp, _vp, _vp, _vp], _i),
+    "sis_pixel_ensemble_project": ([_vp, _i, _i, _i, _vp], _i),
+    "sis_pixel_ensemble_head": ([_vp, _vp, _i] + [_vp] * 10 + [_i] * 5 + [_vp], _i),
 }
 
 
@@ -2423,3 +2425,70 @@ def adam_clip_step(table, n_chunks, partial, hyper, step):
     with torch.cuda.device(table.device):
         _check(lib().sis_adam_clip_step(_ptr(table), int(n_chunks), _ptr(partial), _ptr(hyper), _ptr(step), _stream()),
                "sis_adam_clip_step")
+
+
+# ------------------------------------------------------------------------------ DatasetGAN pixel-ensemble labelling
+
+
+def _layer_pair(layers, name):
+    """<= 2 contiguous fp32 [B, c, r, r] tensors -> (tensors, host words {act0, act1, c0, c1})."""
+    if len(layers) > 2:
+        raise RuntimeError(f"{name}: at most two activation layers per resolution group")
+    ts = [_dense_f32(t, name) for t in layers]
+    words = [0, 0, 0, 0]
+    for i, t in enumerate(ts):
+        words[i], words[2 + i] = t.data_ptr(), t.shape[1]
+    return ts, words
+
+
+def pixel_ensemble_label(full, groups, w1f, b1, w2t, b2, w3t, b3, classes, hidden1, size, lut=None, want_logits=False):
+    """Voted DatasetGAN labels of a batch (csrc/pixel_ensemble.hip).
+
+    full: the full-resolution activation layers ([B, c, S, S], at most two; empty: none) and w1f [sum c][N * hidden1] their
+    first-layer weights (k-major); groups: [(layers at one resolution r < S (at most two), wt [sum c][N * hidden1])];
+    b1 [N * hidden1]; w2t [N][hidden1][H2], b2 [N][H2], w3t [N][H2][CP], b3 [N][CP] with BatchNorm folded in.
+    -> (labels int64 [B, S, S], colours uint8 [B, S, S, 3] when a [C, 3] uint8 lut is given, else None,
+        member logits [N, B, S, S, C] when want_logits, else None)."""
+    members, m = w2t.shape[0], b1.numel()
+    acts = list(full) + [t for layers, _ in groups for t in layers]
+    if not acts:
+        raise RuntimeError("pixel_ensemble_label: no activations")
+    dev, batch = acts[0].device, acts[0].shape[0]
+    full_ts, full_words = _layer_pair(full, "full-resolution activations")
+    keep, gwords, pwords, projs = [], [], [], []
+    for layers, wt in groups:
+        ts, words = _layer_pair(layers, "activations")
+        res = ts[0].shape[-1]
+        wt = _dense_f32(wt, "projection weights")
+        out = torch.empty((batch, res * res, m), dtype=torch.float32, device=dev)
+        keep += ts + [wt]
+        projs.append(out)
+        gwords += [res, wt.data_ptr(), out.data_ptr(), words[0], words[1], words[2], words[3]]
+        pwords += [out.data_ptr(), res]
+    weights = [_dense_f32(t, n) for t, n in ((b1, "b1"), (w2t, "w2t"), (b2, "b2"), (w3t, "w3t"), (b3, "b3"))]
+    w1f = _dense_f32(w1f, "w1f") if full_ts else None
+    labels = torch.empty((batch, size, size), dtype=torch.int64, device=dev)
+    rgb = torch.empty((batch, size, size, 3), dtype=torch.uint8, device=dev) if lut is not None else None
+    if lut is not None and (lut.dtype != torch.uint8 or not lut.is_cuda or tuple(lut.shape) != (classes, 3)):
+        raise RuntimeError("pixel_ensemble_label: the colour table must be a uint8 [C, 3] device tensor")
+    logits = torch.empty((members, batch, size, size, classes), dtype=torch.float32, device=dev) if want_logits else None
+    g_arr = (ctypes.c_int64 * max(len(gwords), 1))(*gwords)
+    p_arr = (ctypes.c_int64 * max(len(pwords), 1))(*pwords)
+    f_arr = (ctypes.c_int64 * 4)(*full_words)
+    kf = full_words[2] + full_words[3]
+    flops_proj = 2.0 * m * sum(t.shape[1] * t.shape[2] * t.shape[3] for layers, _ in groups for t in layers)
+    hidden2, cp = w2t.shape[2], w3t.shape[2]
+    flops_head = 2.0 * batch * size * size * (m * kf + members * (hidden1 * hidden2 + hidden2 * cp)) \
+        + 8.0 * batch * size * size * m * len(groups)
+    with torch.cuda.device(dev):
+        if groups:
+            _check(_launch("pe_project_kernel", flops_proj, 4.0 * (sum(t.numel() for t in keep) + sum(t.numel() for t in projs)),
+                           lambda: lib().sis_pixel_ensemble_project(g_arr, len(groups), batch, m, _stream())),
+                   "sis_pixel_ensemble_project")
+        _check(_launch(f"pe_head_kernel<{hidden1},{hidden2},{cp}>", flops_head,
+                       4.0 * (sum(t.numel() for t in full_ts) * members + sum(t.numel() for t in projs)) + 8.0 * labels.numel(),
+                       lambda: lib().sis_pixel_ensemble_head(f_arr, p_arr, len(projs), _ptr(w1f), *[_ptr(t) for t in weights],
+                                                             _ptr(lut), _ptr(labels), _ptr(rgb), _ptr(logits), batch, size,
+                                                             members, classes, hidden1, _stream())),
+               "sis_pixel_ensemble_head")
+    return labels, rgb, logits

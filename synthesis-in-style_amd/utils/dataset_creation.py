@@ -64,25 +64,34 @@ def generate_images(batch: Latents, autoencoder, device='cuda', mean_latent: Opt
 _LABEL_STREAMS = {}  # device -> side stream of the label / uint8 pass
 
 
-def label_and_encode(image: torch.Tensor, activations: Dict[int, torch.Tensor], catalogs: Dict) \
-        -> Tuple[torch.Tensor, Dict[int, torch.Tensor], Optional[torch.cuda.Event]]:
+def label_and_encode(image: torch.Tensor, activations: Dict[int, torch.Tensor], catalogs: Dict, dataset_gan=None) \
+        -> Tuple[torch.Tensor, Dict, Optional[torch.cuda.Event]]:
     """What the reference does with a batch after ``generate_images`` (create_dataset_for_segmentation.py:131-135 ->
     ``predict_clusters`` -> ``FactorCatalog.predict``; ``make_image``): nearest-centre label maps of the catalogued
     activation layers and the uint8 NHWC image, here issued on a side stream.  Both passes are HBM-bound
     readers of finished tensors, so they overlap the MFMA-bound first layers of the NEXT batch, whose small grids
     leave most compute units idle.  Returns (pixels u8 [B,H,W,3], {layer: labels}, event): wait for / synchronise on
     the event before touching the results from another stream or the host.  SIS_LABEL_STREAM=0 keeps everything on the
-    current stream (event None)."""
+    current stream (event None).  ``dataset_gan``: a DatasetGANSegmenter whose fused pass also runs there; its uint8
+    [B,H,W,3] class-colour image is returned under the key "dataset_gan"."""
     device = image.device
+
+    def labels_of():
+        labels = {k: cat.predict(activations[k]) for k, cat in catalogs.items()}
+        if dataset_gan is not None:
+            labels["dataset_gan"] = dataset_gan.label_activations(activations)[1]
+        return labels
+
     if os.environ.get("SIS_LABEL_STREAM", "1") == "0" or not image.is_cuda:
-        return sis_hip.make_image_u8(image), {k: cat.predict(activations[k]) for k, cat in catalogs.items()}, None
+        return sis_hip.make_image_u8(image), labels_of(), None
     if device not in _LABEL_STREAMS:
         _LABEL_STREAMS[device] = sis_hip.side_stream(device)
     side, main = _LABEL_STREAMS[device], torch.cuda.current_stream(device)
     side.wait_event(main.record_event())
     with torch.cuda.stream(side):
-        labels = {k: cat.predict(activations[k]) for k, cat in catalogs.items()}
+        labels = labels_of()
         pixels = sis_hip.make_image_u8(image)
-    for t in [image] + [activations[k] for k in catalogs]:
+    read = list(activations.values()) if dataset_gan is not None else [activations[k] for k in catalogs]
+    for t in [image] + read:
         t.record_stream(side)  # the caching allocator must not hand these blocks out again before the side pass has read them
     return pixels, labels, side.record_event()
