@@ -736,6 +736,33 @@ int sis_pixel_ensemble_head(const int64_t* full, const int64_t* proj, int nproj,
                             int64_t* labels, uint8_t* rgb, float* logits, int batch, int size, int members, int classes,
                             int hidden1, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Fitting spherical k-means activation catalogs (csrc/spherical_kmeans.hip): the arithmetic of
+ * MiniBatchSphericalKMeans.fit (reference segmentation/gan_local_edit/spherical_kmeans.py:161-312) as called by
+ * FactorCatalog.fit_predict (factor_catalog.py:64-67) from create_semantic_segmentation.py:114-129, on the NCHW activation
+ * x [B][C][HW] as the generator wrote it.  Row n = b*HW + p of the reference's partial_flat(x) is pixel p of sample b.
+ * Envelope: C a multiple of 8 up to 512, at most 32 centres, batch_size at most 256, B*HW below 2^31.  All fp32 data; counts,
+ * sums over members, norms and the stop rule in double; no floating-point atomics (same bytes on every run).
+ * _gather: out[i][0..C) = x_row(idx[i]) / |x_row(idx[i])| (a zero row stays zero), replacing the normalize(X) of the whole
+ *   matrix (spherical_kmeans.py:201) for the few rows a plan uses.
+ * _loop: one workgroup per fit runs up to `iters` mini-batch iterations (spherical_kmeans.py:262-296, the step :36-156) and
+ *   stops early on the no-improvement rule; fits whose state says done are skipped.  state [n_fits][sis_skm_state_doubles()]:
+ *   {ewa, ewa_min, iteration, no_improvement, done, last mini-batch inertia, k, has_ewa, counts[32]}; centres [n_fits][32][C]
+ *   (rows 0..k-1 used); last_labels [n_fits][256]: labels of the last mini-batch it ran; rows [iters][batch_size][C]: the unit
+ *   rows of this chunk's planned mini-batches (shared by all fits); picks [iters][32]: distinct mini-batch positions per
+ *   iteration for the reassignment rule.  alpha: the EWA factor min(2*batch_size/(N+1), 1).
+ * _label: labels[n] = argmax_k (x_n.c_k/|x_n| - |c_k|^2/2) (= argmin |xhat_n - c_k|^2, lowest k on ties), result[0] = inertia =
+ *   sum_n |xhat_n - c_label|^2, result[1+k] = pixels of centre k (spherical_kmeans.py:298-300 _labels_inertia); workspace
+ *   sis_skm_label_workspace_doubles(B*HW) doubles, result 33 doubles. */
+int sis_skm_state_doubles(void);
+int sis_skm_gather(float* out, const float* x, const int* idx, int64_t n_rows, int batch, int channels, int hw, void* stream);
+int sis_skm_loop(double* state, float* centres, int* last_labels, const float* rows, const int* picks, int n_fits, int channels,
+                 int batch_size, int iters, double alpha, int max_no_improvement, double reassignment_ratio, int64_t max_iterations,
+                 void* stream);
+int64_t sis_skm_label_workspace_doubles(int64_t n_pixels);
+int sis_skm_label(int64_t* labels, double* result, double* workspace, const float* x, const float* centres, int batch, int channels,
+                  int hw, int n_centres, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,7 @@ F32, F64, F16, BF16 = 0, 1, 2, 3
 _DTYPE_CODE = {torch.float32: F32, torch.float64: F64, torch.float16: F16, torch.bfloat16: BF16}
 
 _vp, _i, _i64, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+_d = ctypes.c_double
 
 _SIGNATURES = {
     "sis_version": ([], _i),
@@ -162,6 +163,11 @@ _SIGNATURES = {
     "sis_adam_clip_step": ([_vp, _i, _vp, _vp, _vp, _vp], _i),
     "sis_pixel_ensemble_project": ([_vp, _i, _i, _i, _vp], _i),
     "sis_pixel_ensemble_head": ([_vp, _vp, _i] + [_vp] * 10 + [_i] * 5 + [_vp], _i),
+    "sis_skm_state_doubles": ([], _i),
+    "sis_skm_gather": ([_vp, _vp, _vp, _i64, _i, _i, _i, _vp], _i),
+    "sis_skm_loop": ([_vp] * 5 + [_i] * 4 + [_d, _i, _d, _i64, _vp], _i),
+    "sis_skm_label_workspace_doubles": ([_i64], _i64),
+    "sis_skm_label": ([_vp] * 5 + [_i] * 4 + [_vp], _i),
 }
 
 
@@ -1128,6 +1134,71 @@ def make_image_u8(x):
     with torch.cuda.device(x.device):
         _check(lib().sis_make_image_u8(_ptr(out), _ptr(x), b, ch, h * w, _stream()), "sis_make_image_u8")
     return out
+
+
+# ------------------------------------------------------------------------------ spherical k-means fit (csrc/spherical_kmeans.hip)
+SKM_KMAX, SKM_BMAX = 32, 256   # centre rows per fit in the centres tensor, label slots per fit in last_labels
+
+
+def skm_gather(x, idx):
+    """[B,C,H,W] activation, int32 [n] rows of partial_flat(x) -> [n,C] unit rows (a zero row stays zero)."""
+    x = _f32(x, "X")
+    require_device(idx, "idx")
+    if idx.dtype != torch.int32:
+        raise RuntimeError(f"idx must be int32, got {idx.dtype}")
+    idx = idx.contiguous()
+    b, ch, h, w = x.shape
+    out = torch.empty((idx.numel(), ch), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(_launch("skm_gather_kernel", 3.0 * idx.numel() * ch, 8.0 * idx.numel() * ch,
+                       lambda: lib().sis_skm_gather(_ptr(out), _ptr(x), _ptr(idx), idx.numel(), b, ch, h * w, _stream())),
+               "sis_skm_gather")
+    return out
+
+
+def skm_new_state(ks, device):
+    """float64 [len(ks), sis_skm_state_doubles()] start state (zero counts, iteration 0) for fits with ks[i] clusters."""
+    state = torch.zeros((len(ks), lib().sis_skm_state_doubles()), dtype=torch.float64)
+    state[:, 6] = torch.as_tensor(list(ks), dtype=torch.float64)
+    return state.to(device)
+
+
+def skm_loop(state, centres, last_labels, rows, picks, batch_size, iters, alpha, max_no_improvement, reassignment_ratio,
+             max_iterations):
+    """Advance every unfinished fit by up to ``iters`` mini-batch iterations, in place (state float64 [F,40], centres float32
+    [F,32,C], last_labels int32 [F,256], rows float32 [>= iters*batch_size, C], picks int32 [>= iters, 32])."""
+    for t, name, dt in ((state, "state", torch.float64), (centres, "centres", torch.float32), (last_labels, "last_labels", torch.int32),
+                        (rows, "rows", torch.float32), (picks, "picks", torch.int32)):
+        require_device(t, name)
+        if t.dtype != dt or not t.is_contiguous():
+            raise RuntimeError(f"{name} must be a contiguous {dt} tensor")
+    f, _, ch = centres.shape
+    if (centres.shape[1] != SKM_KMAX or state.shape != (f, lib().sis_skm_state_doubles()) or last_labels.shape != (f, SKM_BMAX)
+            or rows.numel() < iters * batch_size * ch or picks.numel() < iters * 32):
+        raise RuntimeError("skm_loop: tensor shapes do not match (F fits, 32 centre rows, iters * batch_size rows, iters * 32 picks)")
+    with torch.cuda.device(centres.device):
+        _check(_launch("skm_loop_kernel", 2.0 * f * iters * batch_size * ch * SKM_KMAX, 4.0 * f * iters * batch_size * ch * 2,
+                       lambda: lib().sis_skm_loop(_ptr(state), _ptr(centres), _ptr(last_labels), _ptr(rows), _ptr(picks), f, ch,
+                                                  int(batch_size), int(iters), float(alpha), int(max_no_improvement),
+                                                  float(reassignment_ratio), int(max_iterations), _stream())), "sis_skm_loop")
+
+
+def skm_label(x, centres):
+    """[B,C,H,W] activation, [K,C] centres -> (int64 [B*H*W] labels of the unit-normalised pixels, float64 [33] device tensor:
+    inertia, then the pixel count of each centre)."""
+    x = _f32(x, "X")
+    c = _f32(centres, "cluster_centers")
+    b, ch, h, w = x.shape
+    if c.dim() != 2 or c.shape[1] != ch:
+        raise RuntimeError(f"centres {tuple(c.shape)} do not match {ch} channels")
+    labels = torch.empty(b * h * w, dtype=torch.int64, device=x.device)
+    result = torch.empty(33, dtype=torch.float64, device=x.device)
+    ws = torch.empty(lib().sis_skm_label_workspace_doubles(b * h * w), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(_launch("skm_label_kernel", 2.0 * b * ch * h * w * 32, 4.0 * x.numel() + 8.0 * labels.numel(),
+                       lambda: lib().sis_skm_label(_ptr(labels), _ptr(result), _ptr(ws), _ptr(x), _ptr(c), b, ch, h * w, c.shape[0],
+                                                   _stream())), "sis_skm_label")
+    return labels, result
 
 
 # ------------------------------------------------------------------------------ fp32 pointwise convolution (matrix cores, NCHW)
