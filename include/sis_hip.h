@@ -763,6 +763,31 @@ int64_t sis_skm_label_workspace_doubles(int64_t n_pixels);
 int sis_skm_label(int64_t* labels, double* result, double* workspace, const float* x, const float* centres, int batch, int channels,
                   int hw, int n_centres, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Page evaluation (csrc/page_ops.hip, csrc/contour_ops.hip): what the reference's
+ * segmentation/evaluation/analyze_image_segments.py does per page besides running the network.
+ * sis_assemble_vote: VotingAssemblySegmenter.assemble_predictions (segmentation/analysis_segmenter.py:198-223); arguments as
+ *   sis_assemble_max.  out[c][y][x] = (sum over the covering patches, row-major) / (sum of that over c), 0 where the divisor
+ *   is 0; labels (optional) uint8 first maximal class of out.
+ * sis_confusion_matrix: matrix[t][p] += #{pixels with ground truth t and predicted class p} (int64 [classes][classes] on the
+ *   device, accumulated: the caller zeroes it once per run).  prediction: confidences [classes][pixels] (first maximal class)
+ *   or null, then labels uint8 [pixels] is read.  classes <= 16.
+ * sis_color_to_class: out[i] = id of the LAST of `count` colours equal to image[i] (uint8 [pixels][3]), else background_id;
+ *   colors / ids are HOST arrays ([count][3] r, g, b; [count]), count <= 64.
+ * sis_remove_small_contours: BaseSegmenter.postprocess (networks/base_segmenter.py:25-52) on pred [batch][classes][p][p]:
+ *   confidence threshold, then every region of a non-background plane whose contour area is below min_contour_area is zeroed.
+ *   Exact definition (mask, 5x5 closing, outside, regions, area through 2x2 blocks): DESIGN.md §10.  p <= 1024; workspace of
+ *   sis_contour_workspace_bytes(batch*classes, p) bytes, 4-byte aligned; fixed launch sequence, no host sync, bit-reproducible. */
+int sis_assemble_vote(float* out, uint8_t* labels, const float* pred, const int* xs, const int* ys, int nx, int ny, int classes,
+                      int height, int width, int patch, void* stream);
+int sis_confusion_matrix(int64_t* matrix, const float* prediction, const uint8_t* labels, const uint8_t* ground_truth,
+                         int64_t pixels, int classes, void* stream);
+int sis_color_to_class(uint8_t* out, const uint8_t* image, int64_t pixels, int background_id, const uint8_t* colors,
+                       const uint8_t* ids, int count, void* stream);
+int64_t sis_contour_workspace_bytes(int planes, int p);
+int sis_remove_small_contours(float* out, const float* pred, void* workspace, int64_t workspace_bytes, int batch, int classes,
+                              int p, float min_confidence, int min_contour_area, int background_class_id, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,10 +1,10 @@
 """Common base of the segmentation networks (reference: networks/base_segmenter.py:11-65).
 
 On the hot path only two things matter: it is the nn.Module base class of EMANet / TransUNet, and
-``predict_classes`` yields the argmax label map.  The reference's inference-time clean-up (confidence
-threshold, then OpenCV contour removal below ``min_contour_area``) is CPU post-processing outside the
-training step; the threshold is kept (pure tensor op), contour removal is not reimplemented and raises if
-requested.
+``predict_classes`` yields the argmax label map.  The reference's inference-time clean-up is a confidence
+threshold, then OpenCV contour removal below ``min_contour_area`` on the host, per patch and per class.  Here
+the threshold alone is a tensor op; with ``min_contour_area > 0`` both run in ``sis_hip.remove_small_contours``
+(csrc/contour_ops.hip) on the device.  There is no host implementation: CPU tensors raise.
 """
 from typing import Any
 
@@ -24,7 +24,11 @@ class BaseSegmenter(nn.Module):
 
     def postprocess(self, predictions: torch.Tensor) -> torch.Tensor:
         if self.min_contour_area > 0:
-            raise NotImplementedError("contour-area filtering is OpenCV post-processing (out of the hot path)")
+            if not predictions.is_cuda:
+                raise NotImplementedError("contour-area filtering runs on the device only (sis_hip.remove_small_contours)")
+            import sis_hip
+            return sis_hip.remove_small_contours(predictions, self.min_confidence, self.min_contour_area,
+                                                 self.background_class_id)
         return torch.where(predictions < self.min_confidence, torch.zeros_like(predictions), predictions)
 
     def predict(self, x: torch.Tensor) -> torch.Tensor:

@@ -18,9 +18,9 @@ On a HIP device with float32 tensors the forward runs through the autograd Funct
 CPU tensors and other dtypes run the reference's plain torch forward (on a HIP device through ``sis_hip.library_call``).
 
 Differences from the reference: ``BatchNorm2d.num_batches_tracked`` is not advanced on the HIP path (it only matters for
-``momentum=None``, which DocUFCN does not use).  ``min_contour_area`` keeps the reference default of 55, but the port's
-``BaseSegmenter.predict`` raises for a non-zero area (OpenCV contour filtering is not part of this port): callers of
-``predict`` / ``predict_classes`` set it to 0.  Input height and width must be multiples of 8 (three poolings); on the HIP
+``momentum=None``, which DocUFCN does not use).  ``min_contour_area`` keeps the reference default of 55; on a HIP
+device ``BaseSegmenter.predict`` removes such contours with ``sis_hip.remove_small_contours``, which wants
+square inputs up to 1024 x 1024; on CPU tensors a non-zero area raises.  Input height and width must be multiples of 8 (three poolings); on the HIP
 path also (H / 8) * (W / 8) must be a multiple of 4 (the BatchNorm kernels move float4 rows of every map): any H, W that are
 multiples of 16 qualify, 72 x 72 does not.
 """

@@ -5,6 +5,8 @@ changes is where the work happens.  The reference crops PIL patches on the host,
 the predictions with one ``torch.maximum`` slice assignment per patch.  Here the page is uploaded once as uint8,
 ``sis_crop_patches_u8`` produces every normalised patch in one pass, the network predicts ``batch_size`` patches at a
 time, and ``sis_assemble_max`` gathers the per-pixel maximum (and, for ``segment_labels``, the label map) in one pass.
+``VotingAssemblySegmenter`` (reference :198-223, the class the evaluation tool uses) differs in the merge only: the covering
+patches' confidences are added and normalised over the classes (``sis_assemble_vote``).
 
 The constructor takes the network itself (the reference builds it from a checkpoint's config through its train
 builder -- `load_network`, :73-81 -- which is checkpoint / config-file IO outside the hot path).
@@ -120,3 +122,13 @@ class AnalysisSegmenter:
         page = self._page_tensor(image)
         predictions = self.predict_patches(self.crop_and_batch_patches(page))
         return self.assemble_predictions(predictions, (page.shape[1], page.shape[0]), with_labels=True)[1]
+
+
+class VotingAssemblySegmenter(AnalysisSegmenter):
+    """Overlapping patches vote: their confidences are added per pixel and class in the reference's patch order, then divided
+    by the sum over the classes; a pixel whose confidences were all removed by the post-processing gets 0 everywhere."""
+
+    def assemble_predictions(self, predictions: torch.Tensor, output_size: Sequence[int], with_labels: bool = False):
+        width, height = output_size
+        xs, ys = self.patch_grid(width, height)
+        return sis_hip.assemble_vote(predictions, xs, ys, height, width, with_labels=with_labels)

@@ -168,6 +168,11 @@ _SIGNATURES = {
     "sis_skm_loop": ([_vp] * 5 + [_i] * 4 + [_d, _i, _d, _i64, _vp], _i),
     "sis_skm_label_workspace_doubles": ([_i64], _i64),
     "sis_skm_label": ([_vp] * 5 + [_i] * 4 + [_vp], _i),
+    "sis_assemble_vote": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
+    "sis_confusion_matrix": ([_vp, _vp, _vp, _vp, _i64, _i, _vp], _i),
+    "sis_color_to_class": ([_vp, _vp, _i64, _i, _vp, _vp, _i, _vp], _i),
+    "sis_contour_workspace_bytes": ([_i, _i], _i64),
+    "sis_remove_small_contours": ([_vp, _vp, _vp, _i64, _i, _i, _i, _f, _i, _i, _vp], _i),
 }
 
 
@@ -2220,6 +2225,90 @@ def assemble_max(pred, xs, ys, height, width, with_labels=False):
         _check(lib().sis_assemble_max(_ptr(out), _ptr(labels), _ptr(pred), _ptr(xs), _ptr(ys), xs.numel(), ys.numel(), c,
                                       height, width, p, _stream()), "sis_assemble_max")
     return (out, labels) if with_labels else out
+
+
+def assemble_vote(pred, xs, ys, height, width, with_labels=False):
+    """[N,C,P,P] patch predictions -> [C,height,width] confidences summed over the covering patches (row-major patch order) and
+    divided by their sum over the classes, 0 where that sum is 0 (+ uint8 label map, first maximal class)."""
+    pred = _f32(pred, "predictions")
+    n, c, p, p2 = pred.shape
+    xs, ys = _grid(xs, ys, pred.device)
+    if p != p2 or n != xs.numel() * ys.numel():
+        raise RuntimeError(f"predictions {tuple(pred.shape)} do not match a {ys.numel()} x {xs.numel()} patch grid")
+    out = torch.empty((c, height, width), dtype=torch.float32, device=pred.device)
+    labels = torch.empty((height, width), dtype=torch.uint8, device=pred.device) if with_labels else None
+    with torch.cuda.device(pred.device):
+        _check(lib().sis_assemble_vote(_ptr(out), _ptr(labels), _ptr(pred), _ptr(xs), _ptr(ys), xs.numel(), ys.numel(), c,
+                                       height, width, p, _stream()), "sis_assemble_vote")
+    return (out, labels) if with_labels else out
+
+
+def confusion_matrix(prediction, ground_truth, num_classes, out=None):
+    """int64 [C,C] on the device, rows ground truth, columns prediction.  ``prediction``: float32 confidences [C,H,W] (first
+    maximal class) or a uint8 label map [H,W]; ``ground_truth``: uint8 [H,W].  ``out``: a matrix to accumulate into (a run over
+    many pages then crosses to the host once); a fresh zeroed one otherwise."""
+    require_device(prediction, "prediction")
+    require_device(ground_truth, "ground_truth")
+    if ground_truth.dtype != torch.uint8 or ground_truth.dim() != 2:
+        raise RuntimeError("ground_truth must be a uint8 [H, W] tensor")
+    gt = ground_truth.contiguous()
+    if prediction.dim() == 3:
+        conf, labels = _f32(prediction, "prediction"), None
+        if conf.shape[0] != num_classes:
+            raise RuntimeError(f"prediction has {conf.shape[0]} classes, expected {num_classes}")
+    elif prediction.dim() == 2 and prediction.dtype == torch.uint8:
+        conf, labels = None, prediction.contiguous()
+    else:
+        raise RuntimeError("prediction must be float32 [C, H, W] confidences or a uint8 [H, W] label map")
+    if tuple(prediction.shape[-2:]) != tuple(gt.shape):
+        raise RuntimeError("Shapes of prediction and ground truth do not match")
+    if out is None:
+        out = torch.zeros((num_classes, num_classes), dtype=torch.int64, device=gt.device)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (num_classes, num_classes) or not out.is_contiguous() or out.device != gt.device:
+        raise RuntimeError("out must be a contiguous int64 [C, C] tensor on the device of the inputs")
+    with torch.cuda.device(gt.device):
+        _check(lib().sis_confusion_matrix(_ptr(out), _ptr(conf), _ptr(labels), _ptr(gt), gt.numel(), int(num_classes), _stream()),
+               "sis_confusion_matrix")
+    return out
+
+
+def color_to_class(image, colors, ids, background_id=0):
+    """uint8 [H,W,3] image on the device -> uint8 [H,W] class ids: ``ids[k]`` where the pixel equals ``colors[k]`` (r, g, b; the
+    last match wins), ``background_id`` elsewhere."""
+    require_device(image, "image")
+    if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3:
+        raise RuntimeError("image must be a uint8 [H, W, 3] tensor")
+    image = image.contiguous()
+    n = len(ids)
+    flat = [int(v) for color in colors for v in color]
+    if len(flat) != 3 * n or any(not 0 <= v <= 255 for v in flat) or any(not 0 <= int(i) <= 255 for i in ids):
+        raise RuntimeError("colors must be (r, g, b) byte triples, one per id")
+    out = torch.empty(image.shape[:2], dtype=torch.uint8, device=image.device)
+    c_colors, c_ids = (ctypes.c_uint8 * max(3 * n, 1))(*flat), (ctypes.c_uint8 * max(n, 1))(*[int(i) for i in ids])
+    with torch.cuda.device(image.device):
+        _check(lib().sis_color_to_class(_ptr(out), _ptr(image), out.numel(), int(background_id), c_colors, c_ids, n, _stream()),
+               "sis_color_to_class")
+    return out
+
+
+def remove_small_contours(pred, min_confidence, min_contour_area, background_class_id=0):
+    """BaseSegmenter.postprocess on the device: pred [B,C,P,P] float32 -> pred below ``min_confidence`` zeroed, then every
+    region (outermost contour, holes filled) of a non-background plane with a contour area below ``min_contour_area`` zeroed
+    (DESIGN.md §10).  One read of ``pred``; the scratch is a torch allocation, so the call can be captured in a graph."""
+    pred = _f32(pred, "predictions")
+    if pred.dim() != 4 or pred.shape[2] != pred.shape[3]:
+        raise RuntimeError(f"predictions must be [B, C, P, P], got {tuple(pred.shape)}")
+    b, c, p, _ = pred.shape
+    out = torch.empty_like(pred)
+    nbytes = int(lib().sis_contour_workspace_bytes(b * c, p))
+    ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=pred.device)
+    with torch.cuda.device(pred.device):
+        _check(_launch("contour_filter", 0.0, 8.0 * pred.numel(),
+                       lambda: lib().sis_remove_small_contours(_ptr(out), _ptr(pred), _ptr(ws), ws.numel() * 4, b, c, p,
+                                                               float(min_confidence), int(min_contour_area),
+                                                               int(background_class_id), _stream())),
+               "sis_remove_small_contours")
+    return out
 
 
 # ------------------------------------------------------------------------------ fused batch norm
