@@ -18,17 +18,24 @@
 // GEMM view: M = output channels, N = 2 x 2 position BLOCKS, K = input channels, 25 accumulator planes.  25 planes of a
 // 32 x 32 tile (400 registers) leave one wave per SIMD; on v_mfma_f32_16x16x4_f32 (same rate: 64 FLOP/clk/SIMD, exact fp32) a
 // wave holds 32 channels x 16 blocks x 25 planes in 200 registers and two waves share a SIMD.  Workgroup = 4 waves =
-// 64 channels x 32 blocks (128 positions), 4 input channels per chunk, 58 KB of LDS: TWO workgroups per CU, one wave of each
+// 64 channels x 32 blocks (128 positions), 4 input channels per chunk, 46 080 B of LDS (52 224 B for 128 x 128 maps): TWO workgroups per CU, one wave of each
 // on every SIMD, so that one's barrier, patch transform, fragment reads, prologue and epilogue fall under the other's MFMAs
 // (the 8-wave / 64-block / 8-channel tile, SIS_UPFIR_WAVES=8, has both waves of a SIMD behind the same barrier: 5.22 -> 4.94 ms
 // on the three large layers).  Lane l of a wave: block l & 15, input channel (l >> 4) of the 4-deep MFMA step.
 //
-// Blocks are numbered row-major over (sample, block row, block column) -- (H/2 + 1) x (W/2 + 1) per sample: the transposed
-// convolution has H + 1 position rows, the last block row / column holds one valid position -- and a workgroup takes 64
-// CONSECUTIVE blocks (no tile classes: 0.2 % of the blocks of a 64 x 64 layer are padding).  Its input tile is the run of
-// image rows those blocks touch, each staged whole as [4 zeros | W pixels | 4 zeros] by LDS-DMA through a buffer descriptor
-// whose out-of-range lanes write the zeros (rows -1 and H, H + 1 and the pad columns alike); "virtual" row v of sample b,
-// v = h + 1 in [0, H + 3), has index b (H + 3) + v, so a run that crosses from one sample into the next is still one range.
+// The transposed convolution has H + 1 position rows and W + 1 position columns.  Two passes, one C call:
+//   interior: the (H/2) x (W/2) blocks of positions (0 .. H-1) x (0 .. W-1) per sample, all 25 products (this kernel): T rows
+//             0 .. 2H - 1, columns 0 .. 2W - 1;
+//   edge:     position row H and position column W (modconv_upfir_edge_kernel below): T row 2H, T column 2W, the pad columns.
+// A block of the edge has zero padding for two of its three patch rows (columns), so 20 of its 25 products (24 in the corner)
+// would multiply zeros; numbering (H/2 + 1) x (W/2 + 1) blocks through this kernel, as it once did, also left every layer of
+// Generator(256) half a round of workgroups past a whole number of rounds ("Up-convolution").
+// Interior blocks are numbered row-major over (sample, block row, block column) and a workgroup takes 8 NW CONSECUTIVE blocks
+// (no tile classes; H W / 4 per sample: a multiple of 32 for every layer of the generator, no padding blocks).  Its input tile
+// is the run of image rows those blocks touch -- a 32-block tile of a 64 x 64 map is one block row, 3 image rows -- each staged
+// whole as [4 zeros | W pixels | 4 zeros] by LDS-DMA through a buffer descriptor whose out-of-range lanes write the zeros
+// (row -1 and the pad columns alike); "virtual" row v of sample b, v = h + 1 in [0, H + 1), has index b (H + 1) + v, so a run
+// that crosses from one sample into the next is still one range.
 // Staging: one input channel per wave and chunk, wave w moves channel w (4 pieces of weights: 16 planes x 64 channels, and
 // <= 4 pieces of input rows), double-buffered, one barrier per chunk (as modconv_mfma2.hip).  The style factor s[b, ci] multiplies the
 // raw patch values after their LDS read; demodulation in the epilogue; noise / bias / activation belong to the blur kernel
@@ -42,7 +49,7 @@ typedef float uf_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int UF_MBLK = 64;                           // output channels per workgroup
 // NW = waves per workgroup (8 or 4): NW input channels per chunk (one channel's DMA per wave) and 8 NW position blocks per
-// workgroup.  NW = 4 halves the tile and the chunk (58 KB of LDS): TWO workgroups share a CU, one wave of each per SIMD, and
+// workgroup.  NW = 4 halves the tile and the chunk (46 - 52 KB of LDS): TWO workgroups share a CU, one wave of each per SIMD, and
 // one's barrier / transform / epilogue falls under the other's MFMAs.
 constexpr int UF_PLANES = 16;
 constexpr int UF_WROW = UF_PLANES * UF_MBLK + 32;     // floats per channel row of the weight stage [8 plane pairs][64 co][2]:
@@ -55,7 +62,7 @@ struct UpFirParams {
     const float* x; const float* u; const float* s; const float* dscale; float* out;
     int B, Cin, Cout, H, W, OH, ORS;
     int nbw, bps, total_blocks;    // block columns per row, blocks per sample, blocks in the batch
-    int vr;                        // virtual rows per sample = H + 3
+    int vr;                        // virtual rows per sample = H + 1
     int rw4;                       // float4 per staged row = W / 4 + 2
     int xs;                        // floats per channel of the staged tile (multiple of 256)
 };
@@ -368,8 +375,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
             }
             float* oc = ob + (int64_t)co * OHW;
 #pragma unroll
-            for (int ro = 0; ro < 4; ++ro) {
-                if (4 * ebh + ro >= p.OH) continue;
+            for (int ro = 0; ro < 4; ++ro) {   // (interior blocks: rows 4 bh .. 4 bh + 3 <= 2H - 1 all exist)
                 float4 v;
                 if (ro == 0) v = make_float4(cs[0][0] + cs[1][0], cs[0][1] + cs[1][1], cs[0][2] + cs[1][2], cs[0][3] + cs[1][3]);
                 else if (ro == 1) v = make_float4(cs[3][0], cs[3][1], cs[3][2], cs[3][3]);
@@ -378,6 +384,163 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
                 *reinterpret_cast<float4*>(oc + ro * p.ORS) = make_float4(v.x * d, v.y * d, v.z * d, v.w * d);
             }
         }
+}
+
+// ---- Edge pass: position row H (T row 2H, corner included) and position column W (T column 2W, rows 0 .. 2H - 1).
+// In the block numbering over (H/2 + 1) x (W/2 + 1) these are the last block row and column, where patch rows (columns) 1 and 2
+// are zero padding: of the 25 products only p = 0 (bottom row: t[0][j] = cm0[j] - 0, planes (0, v)) or q = 0 (right column:
+// column transform d0 - 0, planes (u, 0)) multiply anything but zeros.  A wave takes 16 edge blocks of one kind x 16 output
+// channels, 5 accumulators, the same MFMA, the same channel order (ascending, lane group kq = channel ci0 + kq of the step) and the
+// same output sums as the 25-product kernel, whose operations on these blocks it repeats one for one (the "+ 0.f" stand for its
+// sums with the all-zero products: they turn a -0 into +0 as there).  The NWV waves of a workgroup share the 16 blocks: the
+// column pass reads ONE float per image row (a cache line each), so the patch values and the style factor
+// (x0, x1, x2, s) of a 64-channel chunk are gathered once per workgroup into the LDS, one chunk ahead through registers, and every wave
+// reads its MFMA operand from there; weights by plain loads, a chunk ahead as well.  One barrier per chunk.  The 16-byte store at
+// column 2W also writes the pad columns 2W+1 .. 2W+3.
+#ifndef UF_EDGE_WAVES
+#define UF_EDGE_WAVES 8                               // (development builds: -DUF_EDGE_WAVES=4 = 64 output channels per edge workgroup everywhere)
+#endif
+constexpr int UE_KC = 64;                             // channels per chunk of the edge pass: 16 MFMA steps
+
+template <bool ROWK, int NWV>
+__device__ __forceinline__ void upfir_edge_tile(const UpFirParams& p, int tile, int cgb, float4* Dl) {
+    constexpr int CSTEP = 4 * NWV, NR = UE_KC / CSTEP;  // staging: thread = (block tid & 15, channel (tid >> 4) + k CSTEP), k < NR
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l15 = lane & 15, kq = lane >> 4, sc = tid >> 4;
+    const int co0 = (cgb * NWV + wave) * 16;
+    const int per = ROWK ? p.W / 2 + 1 : p.H / 2;         // edge blocks of this kind per sample
+    const int n_items = p.B * per;
+    const int it = tile * 16 + l15;                       // (the same block in the staging and in the MFMA role: tid & 15 == lane & 15)
+    const int itc = it < n_items ? it : n_items - 1;
+    const int b = itc / per, j = itc - b * per;           // block column (ROWK) or block row
+    const int HW = p.H * p.W;
+    // the three patch values that are not padding: row H - 1, columns 2 j - 1 .. 2 j + 1 (ROWK); column W - 1, rows 2 j - 1 .. 2 j + 1
+    // (32-bit element offsets: the plan keeps x and u below 2 GiB; padding: address clamped, value dropped after the load)
+    unsigned xo[3];
+    bool ok[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const int pos = 2 * j - 1 + r;
+        ok[r] = pos >= 0 && pos < (ROWK ? p.W : p.H);
+        xo[r] = (unsigned)(b * p.Cin * HW + (!ok[r] ? 0 : (ROWK ? (p.H - 1) * p.W + pos : pos * p.W + p.W - 1)));
+    }
+    const unsigned uo = (unsigned)(kq * UF_PLANES * p.Cout + (co0 + l15) * 2);   // u[ci][plane pair][co][2]
+
+    float raw[NR][3], sv[NR];
+    auto load_patch = [&](int c0) {      // (channels past Cin: clamped, their steps are not computed)
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {
+            const int ci = min(c0 + sc + k * CSTEP, p.Cin - 1);
+            sv[k] = p.s[b * p.Cin + ci];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) raw[k][r] = p.x[xo[r] + (unsigned)(ci * HW)];
+        }
+    };
+    auto store_patch = [&](int buf) {
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {
+            Dl[(buf * UE_KC + sc + k * CSTEP) * 16 + l15] =
+                make_float4(ok[0] ? raw[k][0] : 0.f, ok[1] ? raw[k][1] : 0.f, ok[2] ? raw[k][2] : 0.f, sv[k]);
+        }
+    };
+    auto load_w = [&](int c0, float (&w)[16][4]) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const float* uc = p.u + (int64_t)min(c0 + 4 * k, p.Cin - 4) * UF_PLANES * p.Cout;   // (wave-uniform)
+            if constexpr (ROWK) {     // planes (0, 0 .. 3): pairs 0 and 1
+                const f2 w0 = *reinterpret_cast<const f2*>(uc + uo), w1 = *reinterpret_cast<const f2*>(uc + 2 * p.Cout + uo);
+                w[k][0] = w0[0]; w[k][1] = w0[1]; w[k][2] = w1[0]; w[k][3] = w1[1];
+            } else {                  // planes (0 .. 3, 0): first plane of pairs 0, 2, 4, 6
+#pragma unroll
+                for (int u = 0; u < 4; ++u) w[k][u] = (uc + u * 4 * p.Cout)[uo];
+            }
+        }
+    };
+
+    uf_f32x4 acc[5];
+#pragma unroll
+    for (int a = 0; a < 5; ++a) acc[a] = uf_f32x4{0.f, 0.f, 0.f, 0.f};
+    float wc[16][4], wn[16][4];
+    load_patch(0);
+    load_w(0, wc);
+    store_patch(0);
+    __syncthreads();
+    for (int c0 = 0, buf = 0; c0 < p.Cin; c0 += UE_KC, buf ^= 1) {
+        const bool more = c0 + UE_KC < p.Cin;
+        if (more) { load_patch(c0 + UE_KC); load_w(c0 + UE_KC, wn); }
+        const int ns = min(16, (p.Cin - c0) >> 2);
+        auto step = [&](int k) {
+            {
+#pragma clang fp contract(off)
+                const float4 dv = Dl[(buf * UE_KC + 4 * k + kq) * 16 + l15];
+                // The data transform, operation for operation as the compiler emits it for the 25-product kernel (its source says
+                // d = raw * s; o0 = d0 - d1; o2 = d2 - d1 and is contracted to d1 = s x1, o0 = fma(s, x0, -d1), o2 = fma(s, x2, -d1)),
+                // with the padding's zeros put in: explicit fma, contraction off, so that this kernel cannot be contracted
+                // another way.  z = s * 0 is a padding value after the style factor (a signed zero).
+                const float sf = dv.w, z = sf * 0.f;
+                float t[4];
+                if constexpr (ROWK) {     // patch row 0 = (x0, x1, x2), rows 1 and 2 padding: t[0][j] = cm0[j] - t[1][j], t[1] = (+0, z, +0, z)
+                    const float d1 = sf * dv.y, d2 = sf * dv.z;
+                    t[0] = __builtin_fmaf(sf, dv.x, -d1); t[1] = d1 - z; t[2] = __builtin_fmaf(sf, dv.z, -d1); t[3] = d2 - z;
+                } else {                  // patch column 0 = three rows' x, columns 1 and 2 padding: c_r = fma(s, x_r, -z), then the row transform
+                    const float e0 = __builtin_fmaf(sf, dv.x, -z), e1 = __builtin_fmaf(sf, dv.y, -z), e2 = __builtin_fmaf(sf, dv.z, -z);
+                    t[0] = e0 - e1; t[1] = e1; t[2] = e2 - e1; t[3] = e2;
+                }
+                // products 0 .. 4: plane pu = (0, 1, 2, 3, 3) x data dp = (0, 1, 2, 1, 3)
+                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[k][0], t[0], acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[k][1], t[1], acc[1], 0, 0, 0);
+                acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[k][2], t[2], acc[2], 0, 0, 0);
+                acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[k][3], t[1], acc[3], 0, 0, 0);
+                acc[4] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[k][3], t[3], acc[4], 0, 0, 0);
+            }
+        };
+        if (ns == 16) {               // a whole chunk: one block of code, the LDS reads ahead of the MFMAs
+#pragma unroll
+            for (int k = 0; k < 16; ++k) step(k);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                if (k < ns) step(k);
+        }
+        if (more) {
+            store_patch(buf ^ 1);     // (last read in the chunk before this one: behind that chunk's barrier)
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+#pragma unroll
+                for (int u = 0; u < 4; ++u) wc[k][u] = wn[k][u];
+        }
+        __syncthreads();
+    }
+    if (it >= n_items) return;
+    const int OHW = p.OH * p.ORS;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int co = co0 + 4 * kq + r;
+        const float dm = p.dscale[(int64_t)b * p.Cout + co];
+        float* oc = p.out + ((int64_t)b * p.Cout + co) * OHW;
+        if constexpr (ROWK) {     // T row 2H, columns 4 j .. 4 j + 3 (j = W/2: column 2W and the three pad columns, zeros)
+            const float v0 = (acc[0][r] + acc[1][r]) + 0.f, v1 = acc[3][r] + 0.f, v2 = (acc[1][r] + acc[2][r]) + 0.f, v3 = acc[4][r] + 0.f;
+            *reinterpret_cast<float4*>(oc + (int64_t)(2 * p.H) * p.ORS + 4 * j) = make_float4(v0 * dm, v1 * dm, v2 * dm, v3 * dm);
+        } else {                  // T column 2W, rows 4 j .. 4 j + 3
+            const float c0 = acc[0][r] + 0.f, c1 = acc[1][r] + 0.f, c2 = acc[2][r] + 0.f, c3 = acc[3][r] + 0.f, c4 = acc[4][r] + 0.f;
+            const float v[4] = {c0 + c1, c3, c1 + c2, c4};
+            const float z = 0.f * dm;
+#pragma unroll
+            for (int ro = 0; ro < 4; ++ro)
+                *reinterpret_cast<float4*>(oc + (int64_t)(4 * j + ro) * p.ORS + 2 * p.W) = make_float4(v[ro] * dm, z, z, z);
+        }
+    }
+}
+
+// workgroup = NWV waves = one tile of 16 edge blocks x 16 NWV output channels: channel block fastest, bottom-row tiles first
+template <int NWV>
+__global__ __launch_bounds__(64 * NWV) void modconv_upfir_edge_kernel(const UpFirParams p, int n_row_tiles) {
+    __shared__ float4 Dl[2 * UE_KC * 16];
+    const int n_cgb = p.Cout / (16 * NWV);
+    const int tile = blockIdx.x / n_cgb, cgb = blockIdx.x - tile * n_cgb;
+    if (tile < n_row_tiles) upfir_edge_tile<true, NWV>(p, tile, cgb, Dl);
+    else upfir_edge_tile<false, NWV>(p, tile - n_row_tiles, cgb, Dl);
 }
 
 // u[ci][plane pair 2 pu + pv / 2][co][pv % 2] = sum_{ky in K(pu), kx in K(pv)} w[co][ci][ky][kx]
@@ -411,12 +574,13 @@ bool upfir_plan(UpFirParams& p, int batch, int cin, int cout, int h, int w, int 
     if ((row_stride & 3) || row_stride < 2 * w + 4) return false;
     if ((int64_t)batch * cin * h * w * 4 >= (1LL << 31) || (int64_t)cin * UF_PLANES * cout * 4 >= (1LL << 31)) return false;
     p.B = batch; p.Cin = cin; p.Cout = cout; p.H = h; p.W = w; p.OH = 2 * h + 1; p.ORS = row_stride;
-    p.nbw = w / 2 + 1;
-    const int nbh = h / 2 + 1;
+    // interior blocks only: position row H and position column W belong to the edge pass
+    p.nbw = w / 2;
+    const int nbh = h / 2;
     p.bps = nbh * p.nbw;
     if (p.bps < UF_NBLK) return false;      // a tile spans at most two samples
     p.total_blocks = batch * p.bps;
-    p.vr = h + 3;
+    p.vr = h + 1;
     p.rw4 = w / 4 + 2;
     const int n_tiles = sis_cdiv(p.total_blocks, UF_NBLK);
     int rows_max = 0;
@@ -515,6 +679,11 @@ extern "C" int sis_modconv2d_up_fir(float* t, const float* x, const float* u, co
     else if (pipe == 3) hipLaunchKernelGGL(modconv_upfir_kernel<3>, dim3((unsigned)grid), dim3(UF_THREADS), lds, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(modconv_upfir_kernel<1>, dim3((unsigned)grid), dim3(UF_THREADS), lds, (hipStream_t)stream, p);
     SIS_CHECK_LAUNCH("modconv_upfir_kernel");
+    // edge pass: T row 2H and T column 2W (and the pad columns), disjoint from the interior's outputs
+    const int n_row_tiles = sis_cdiv(batch * (w / 2 + 1), 16), n_tiles = n_row_tiles + sis_cdiv(batch * (h / 2), 16);
+    if (cout % 128 == 0 && UF_EDGE_WAVES == 8) hipLaunchKernelGGL(modconv_upfir_edge_kernel<8>, dim3((unsigned)(n_tiles * (cout / 128))), dim3(512), 0, (hipStream_t)stream, p, n_row_tiles);
+    else hipLaunchKernelGGL(modconv_upfir_edge_kernel<4>, dim3((unsigned)(n_tiles * (cout / 64))), dim3(256), 0, (hipStream_t)stream, p, n_row_tiles);
+    SIS_CHECK_LAUNCH("modconv_upfir_edge_kernel");
     sis_kernel_name = "modconv_upfir_kernel";
     return 0;
 }
