@@ -788,6 +788,27 @@ int64_t sis_contour_workspace_bytes(int planes, int p);
 int sis_remove_small_contours(float* out, const float* pred, void* workspace, int64_t workspace_bytes, int batch, int classes,
                               int p, float min_confidence, int min_contour_area, int background_class_id, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Cluster-based dataset labelling (csrc/cluster_segment.hip): what the reference's
+ * BlackWhiteHandwrittenPrintedTextDatasetSegmenter.create_segmentation_image does per batch after FactorCatalog.predict
+ * (segmentation/black_white_handwritten_printed_text_segmenter.py:31-99 on top of
+ * segmentation/base_cluster_based_dataset_segmenter.py:119-450: class merging, nearest resize, keys_to_merge, dilation,
+ * external contours, merging across layers, classification of the fine-grained contours, area filter, drop decision,
+ * rendering), instead of Python loops over OpenCV calls on the host.
+ * sis_cluster_segment: cluster_maps is a HOST array of num_keys device pointers (int64 [batch][resolutions[k]]^2, a cluster id
+ *   outside 0..255 belongs to no class), lut is on the DEVICE ([num_keys][256], bit c: the cluster belongs to non-background
+ *   class c).  determination_sources / fine_sources (HOST, one byte per key of the step): bit k set = cluster map k is OR-ed
+ *   into that key's masks (keys_to_merge resolved by the caller).  class_ids / colours (HOST, [classes + 1] / [classes + 1][3]):
+ *   entry 0 is the background, entry 1 + c non-background class c.  Outputs class_map uint8 [batch][size]^2, colour uint8
+ *   [batch][size]^2[3], drop uint8 [batch].  size <= 1024, num_keys and keys per step <= 8, classes <= 7; workspace of
+ *   sis_cluster_segment_workspace_bytes(...) bytes, 16-byte aligned; fixed launch sequence, no host sync, bit-reproducible. */
+int64_t sis_cluster_segment_workspace_bytes(int batch, int size, int num_determination, int num_fine, int classes);
+int sis_cluster_segment(uint8_t* class_map, uint8_t* colour, uint8_t* drop, const int64_t* const* cluster_maps,
+                        const int* resolutions, int num_keys, const uint8_t* lut, const uint8_t* determination_sources,
+                        int num_determination, const uint8_t* fine_sources, int num_fine, int classes, int fine_class,
+                        const uint8_t* class_ids, const uint8_t* colours, int batch, int size, int only_keep_overlapping,
+                        int min_class_contour_area, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

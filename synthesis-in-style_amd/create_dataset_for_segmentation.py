@@ -6,10 +6,18 @@ intermediate activations on the MI355X kernels -> nearest k-means centre per pix
 layers on the device (FactorCatalog.predict) -> uint8 images on the device -> side-by-side ``[image | label]`` PNGs
 in the reference's directory layout ``<id // 100000>/<id // 1000>/<id>.png`` (save_image, :84-90).
 
-Not reproduced (CPU post-processing outside the hot path): class merging, OpenCV contour
-extraction / filtering / rendering of the label image, COCO ground truth, train/val split.  The label half of the
-PNG is therefore the raw cluster-id map of ``label_layer`` (id * 255 // (K-1) grey levels) instead of the rendered
-class colours.
+Without a ``segmenter_type`` the label half of the PNG is the raw cluster-id map of ``label_layer``
+(id * 255 // (K-1) grey levels).  Not reproduced: COCO ground truth, train/val split, debug images.
+
+``segmenter_type: "black_white_handwritten_printed"`` (the reference's default labeller, :52-65, with its config keys
+``class_to_color_map``, ``keys_for_class_determination``, ``keys_for_finegrained_segmentation``, ``keys_to_merge``,
+``only_keep_overlapping``, ``min_class_contour_area``, and ``--num-clusters K`` / ``-ssd DIR`` naming
+``DIR/catalogs/K.json`` and ``DIR/merged_classes_K.json``): class merging, contour extraction, merging across layers,
+classification, area filter and rendering of the reference's BlackWhiteHandwrittenPrintedTextDatasetSegmenter run on the
+device (csrc/cluster_segment.hip, DESIGN.md §11 with the stated differences) on the label side stream; the label half of
+the PNG is the class-colour image.  Images the labeller flags (a class with a region taller and one wider than 95 % of the
+image) are not written: their ids stay unused, so that the bytes behind an id do not depend on batch or world size (the
+reference shifts the later ids instead).
 
 ``segmenter_type: "dataset_gan"`` in the config (with ``class_to_color_map`` and ``--classifier-path``, as the
 reference's :52-81) labels every image with a trained PixelEnsembleClassifier instead
@@ -43,11 +51,12 @@ def save_image(image: numpy.ndarray, image_id: int, base_dir: Path, name_format:
     Image.fromarray(image).save(str(dest))
 
 
-def save_generated_images(generated_images, label_images, first_id: int, base_dir: Path, num_images: int):
+def save_generated_images(generated_images, label_images, first_id: int, base_dir: Path, num_images: int, keep=None):
     images = numpy.concatenate([generated_images, label_images], axis=2)
     fmt = f"{{id:0{max(4, len(str(num_images)))}d}}.png"
     for idx, image in enumerate(images):
-        save_image(image, first_id + idx, base_dir, name_format=fmt)
+        if keep is None or keep[idx]:
+            save_image(image, first_id + idx, base_dir, name_format=fmt)
 
 
 def load_generator(checkpoint, size, latent_size, n_mlp, channel_multiplier, device):
@@ -71,6 +80,23 @@ def dataset_gan_segmenter(g, classifier_path, creation_config, mean_latent, devi
                                upsamplers=dataset_gan_upsamplers(acts, g.size))
 
 
+def cluster_based_segmenter(args, creation_config, image_size):
+    """The 'black_white_handwritten_printed' branch of the reference's get_dataset_segmenter (:52-65, :76-81)."""
+    from segmentation.black_white_handwritten_printed_text_segmenter import BlackWhiteHandwrittenPrintedTextDatasetSegmenter
+    if 'only_keep_overlapping' not in creation_config:
+        raise ValueError('The key "only_keep_overlapping" must be specified in the config file.')
+    num_clusters, base_dir = getattr(args, 'num_clusters', -1), getattr(args, 'semantic_segmentation_base_dir', None)
+    if num_clusters is None or num_clusters < 1 or base_dir is None:
+        raise ValueError('segmenter_type "black_white_handwritten_printed" needs --num-clusters and '
+                         '-ssd/--semantic-segmentation-base-dir (catalogs/K.json and merged_classes_K.json)')
+    return BlackWhiteHandwrittenPrintedTextDatasetSegmenter(
+        base_dir=Path(base_dir), image_size=image_size, class_to_color_map=creation_config['class_to_color_map'],
+        keys_to_merge=creation_config.get('keys_to_merge', {}), only_keep_overlapping=creation_config['only_keep_overlapping'],
+        keys_for_class_determination=creation_config['keys_for_class_determination'],
+        keys_for_finegrained_segmentation=creation_config['keys_for_finegrained_segmentation'],
+        num_clusters=num_clusters, min_class_contour_area=creation_config['min_class_contour_area'])
+
+
 def build_dataset(args, creation_config, rank=0, world_size=1):
     device = torch.device('cuda', rank % max(torch.cuda.device_count(), 1))
     torch.cuda.set_device(device)
@@ -84,7 +110,11 @@ def build_dataset(args, creation_config, rank=0, world_size=1):
     dataset_gan = None
     if creation_config.get('segmenter_type') == 'dataset_gan':
         dataset_gan = dataset_gan_segmenter(g, getattr(args, 'classifier_path', None), creation_config, mean_latent, device)
+    cluster_segmenter = None
+    if creation_config.get('segmenter_type') == 'black_white_handwritten_printed':
+        cluster_segmenter = cluster_based_segmenter(args, creation_config, g.size)
     lo, hi = shard_range(args.num_images, rank, world_size)
+    dropped = []
     save_dir = Path(args.save_to) if args.save_to else None
     torch.random.manual_seed(creation_config.get('seed', 1))
     done = 0
@@ -94,10 +124,16 @@ def build_dataset(args, creation_config, rank=0, world_size=1):
         first_id, pixels, labels, ready = job
         if ready is not None:
             ready.synchronize()
+        keep = None
+        if cluster_segmenter is not None:
+            keep = ~labels["cluster_segmenter"][2].cpu().numpy().astype(bool)
+            dropped.extend(first_id + int(i) for i in numpy.nonzero(~keep)[0])
         if save_dir is None:
             return
         rgb = pixels.cpu().numpy()
-        if dataset_gan is not None:
+        if cluster_segmenter is not None:
+            lab_img = labels["cluster_segmenter"][1].cpu().numpy()
+        elif dataset_gan is not None:
             lab_img = labels["dataset_gan"].cpu().numpy()
         elif label_layer in labels:
             k = catalogs[label_layer].cluster_centers.shape[0]
@@ -108,7 +144,7 @@ def build_dataset(args, creation_config, rank=0, world_size=1):
             lab_img = numpy.repeat(grey[..., None], 3, axis=3)
         else:
             lab_img = numpy.zeros_like(rgb)
-        save_generated_images(rgb, lab_img, first_id, save_dir, args.num_images)
+        save_generated_images(rgb, lab_img, first_id, save_dir, args.num_images, keep)
 
     pending = None
     with torch.no_grad():
@@ -127,7 +163,10 @@ def build_dataset(args, creation_config, rank=0, world_size=1):
             if (a, b) != (first, first + n):
                 image = image[a - first:b - first]
                 acts = {k: v[a - first:b - first] for k, v in acts.items()}
-            job = (a,) + label_and_encode(image, acts, catalogs, dataset_gan)  # side stream; the next batch's forward is issued first
+            # side stream; the next batch's forward is issued first.  Without a cluster-based labeller the call is the one it
+            # always was (callers wrap label_and_encode with its earlier signature).
+            extra = {} if cluster_segmenter is None else {"cluster_segmenter": cluster_segmenter}
+            job = (a,) + label_and_encode(image, acts, catalogs, dataset_gan, **extra)
             if pending is not None:
                 flush(pending)
             pending = job
@@ -135,6 +174,7 @@ def build_dataset(args, creation_config, rank=0, world_size=1):
         if pending is not None:
             flush(pending)
     torch.cuda.synchronize()
+    args.dropped_image_ids = dropped   # the labeller's drop decisions of this rank (empty without a cluster-based labeller)
     return done, (lo, hi)
 
 
@@ -142,7 +182,10 @@ def main(args):
     creation_config = json.load(open(args.config)) if args.config else {}
     rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))
     done, (lo, hi) = build_dataset(args, creation_config, rank, world)
-    print(f"rank {rank}/{world}: generated image ids [{lo}, {hi}) = {done} images", flush=True)
+    note = ""
+    if creation_config.get('segmenter_type') == 'black_white_handwritten_printed':
+        note = f", {len(args.dropped_image_ids)} of them dropped by the labeller and not written"
+    print(f"rank {rank}/{world}: generated image ids [{lo}, {hi}) = {done} images{note}", flush=True)
 
 
 if __name__ == "__main__":
@@ -155,4 +198,8 @@ if __name__ == "__main__":
     parser.add_argument("-b", "--batch-size", default=10, type=int)
     parser.add_argument("--truncate", action='store_true', default=False, help="truncation trick (psi 0.7, mean of 4096 latents)")
     parser.add_argument("--classifier-path", help="trained PixelEnsembleClassifier checkpoint (segmenter_type \"dataset_gan\")")
+    parser.add_argument("--num-clusters", type=int, default=-1, help="K of catalogs/K.json and merged_classes_K.json "
+                        "(segmenter_type \"black_white_handwritten_printed\")")
+    parser.add_argument("-ssd", "--semantic-segmentation-base-dir", type=Path, help="directory that holds catalogs/ and "
+                        "merged_classes_K.json, as create_semantic_segmentation.py and the annotation step leave it")
     main(parser.parse_args())

@@ -173,6 +173,8 @@ _SIGNATURES = {
     "sis_color_to_class": ([_vp, _vp, _i64, _i, _vp, _vp, _i, _vp], _i),
     "sis_contour_workspace_bytes": ([_i, _i], _i64),
     "sis_remove_small_contours": ([_vp, _vp, _vp, _i64, _i, _i, _i, _f, _i, _i, _vp], _i),
+    "sis_cluster_segment_workspace_bytes": ([_i] * 5, _i64),
+    "sis_cluster_segment": ([_vp] * 5 + [_i, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp], _i),
 }
 
 
@@ -2309,6 +2311,48 @@ def remove_small_contours(pred, min_confidence, min_contour_area, background_cla
                                                                int(background_class_id), _stream())),
                "sis_remove_small_contours")
     return out
+
+
+def cluster_segment(cluster_maps, lut, determination_sources, fine_sources, fine_class, class_ids, colours, size,
+                    only_keep_overlapping, min_class_contour_area):
+    """The cluster-based labeller on the device: ``cluster_maps`` int64 [B, r_k, r_k] tensors (FactorCatalog.predict),
+    ``lut`` uint8 [len(cluster_maps), 256] on the device (bit c: the cluster belongs to non-background class c),
+    ``determination_sources`` / ``fine_sources`` one bitmask over ``cluster_maps`` per key of the step, ``class_ids`` /
+    ``colours`` with the background first.  Returns (class_map uint8 [B,S,S], colour uint8 [B,S,S,3], drop uint8 [B]) on the
+    device; nothing is read back and the scratch is a torch allocation, so the call can be captured in a graph."""
+    maps = []
+    for m in cluster_maps:
+        require_device(m, "cluster maps")
+        if m.dtype != torch.int64 or m.dim() != 3 or m.shape[1] != m.shape[2] or m.shape[0] != cluster_maps[0].shape[0]:
+            raise RuntimeError(f"cluster maps must be int64 [B, r, r], got {m.dtype} {tuple(m.shape)}")
+        if m.shape[1] > size:
+            raise ValueError(f"a cluster map of edge {m.shape[1]} is larger than the image size {size}")
+        maps.append(m.contiguous())
+    device, b, classes = maps[0].device, maps[0].shape[0], len(class_ids) - 1
+    if lut.dtype != torch.uint8 or tuple(lut.shape) != (len(maps), 256) or lut.device != device or not lut.is_contiguous():
+        raise RuntimeError("lut must be a contiguous uint8 [keys, 256] tensor on the cluster maps' device")
+    if len(colours) != classes + 1 or any(len(c) != 3 for c in colours):
+        raise RuntimeError("colours must be one (r, g, b) triple per class id")
+    class_map = torch.empty((b, size, size), dtype=torch.uint8, device=device)
+    colour = torch.empty((b, size, size, 3), dtype=torch.uint8, device=device)
+    drop = torch.empty((b,), dtype=torch.uint8, device=device)
+    nd, nf = len(determination_sources), len(fine_sources)
+    nbytes = int(lib().sis_cluster_segment_workspace_bytes(b, size, nd, nf, classes))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)   # the caching allocator aligns to 512 bytes
+    c_maps = (ctypes.c_void_p * len(maps))(*[m.data_ptr() for m in maps])
+    c_res = (ctypes.c_int * len(maps))(*[m.shape[1] for m in maps])
+    c_det = (ctypes.c_uint8 * max(nd, 1))(*[int(s) for s in determination_sources])
+    c_fine = (ctypes.c_uint8 * max(nf, 1))(*[int(s) for s in fine_sources])
+    c_ids = (ctypes.c_uint8 * (classes + 1))(*[int(i) for i in class_ids])
+    c_col = (ctypes.c_uint8 * (3 * (classes + 1)))(*[int(v) for c in colours for v in c])
+    with torch.cuda.device(device):
+        _check(_launch("cluster_segment", 0.0, 4.0 * class_map.numel(),
+                       lambda: lib().sis_cluster_segment(_ptr(class_map), _ptr(colour), _ptr(drop), c_maps, c_res, len(maps),
+                                                         _ptr(lut), c_det, nd, c_fine, nf, classes, int(fine_class), c_ids,
+                                                         c_col, b, int(size), int(bool(only_keep_overlapping)),
+                                                         int(min_class_contour_area), _ptr(ws), ws.numel(), _stream())),
+               "sis_cluster_segment")
+    return class_map, colour, drop
 
 
 # ------------------------------------------------------------------------------ fused batch norm

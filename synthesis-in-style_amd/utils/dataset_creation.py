@@ -64,8 +64,8 @@ def generate_images(batch: Latents, autoencoder, device='cuda', mean_latent: Opt
 _LABEL_STREAMS = {}  # device -> side stream of the label / uint8 pass
 
 
-def label_and_encode(image: torch.Tensor, activations: Dict[int, torch.Tensor], catalogs: Dict, dataset_gan=None) \
-        -> Tuple[torch.Tensor, Dict, Optional[torch.cuda.Event]]:
+def label_and_encode(image: torch.Tensor, activations: Dict[int, torch.Tensor], catalogs: Dict, dataset_gan=None,
+                     cluster_segmenter=None) -> Tuple[torch.Tensor, Dict, Optional[torch.cuda.Event]]:
     """What the reference does with a batch after ``generate_images`` (create_dataset_for_segmentation.py:131-135 ->
     ``predict_clusters`` -> ``FactorCatalog.predict``; ``make_image``): nearest-centre label maps of the catalogued
     activation layers and the uint8 NHWC image, here issued on a side stream.  Both passes are HBM-bound
@@ -73,13 +73,17 @@ def label_and_encode(image: torch.Tensor, activations: Dict[int, torch.Tensor], 
     leave most compute units idle.  Returns (pixels u8 [B,H,W,3], {layer: labels}, event): wait for / synchronise on
     the event before touching the results from another stream or the host.  SIS_LABEL_STREAM=0 keeps everything on the
     current stream (event None).  ``dataset_gan``: a DatasetGANSegmenter whose fused pass also runs there; its uint8
-    [B,H,W,3] class-colour image is returned under the key "dataset_gan"."""
+    [B,H,W,3] class-colour image is returned under the key "dataset_gan".  ``cluster_segmenter``: a cluster-based labeller
+    (segmentation/black_white_handwritten_printed_text_segmenter.py) whose device pass runs there too; its
+    (class map, colour image, drop flags) triple is returned under the key "cluster_segmenter"."""
     device = image.device
 
     def labels_of():
         labels = {k: cat.predict(activations[k]) for k, cat in catalogs.items()}
         if dataset_gan is not None:
             labels["dataset_gan"] = dataset_gan.label_activations(activations)[1]
+        if cluster_segmenter is not None:
+            labels["cluster_segmenter"] = cluster_segmenter.label_activations(activations)
         return labels
 
     if os.environ.get("SIS_LABEL_STREAM", "1") == "0" or not image.is_cuda:
@@ -91,7 +95,8 @@ def label_and_encode(image: torch.Tensor, activations: Dict[int, torch.Tensor], 
     with torch.cuda.stream(side):
         labels = labels_of()
         pixels = sis_hip.make_image_u8(image)
-    read = list(activations.values()) if dataset_gan is not None else [activations[k] for k in catalogs]
+    read = list(activations.values()) if dataset_gan is not None or cluster_segmenter is not None \
+        else [activations[k] for k in catalogs]
     for t in [image] + read:
         t.record_stream(side)  # the caching allocator must not hand these blocks out again before the side pass has read them
     return pixels, labels, side.record_event()
