@@ -809,6 +809,34 @@ int sis_cluster_segment(uint8_t* class_map, uint8_t* colour, uint8_t* drop, cons
                         const uint8_t* class_ids, const uint8_t* colours, int batch, int size, int only_keep_overlapping,
                         int min_class_contour_area, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training-time augmentation of a device-resident [image | label] dataset (csrc/augment.hip): what the
+ * reference's augment_image (utils/augment_dataset.py:33-59: SomeOf(elastic, ShearX, CropAndPad, translate), Rot90 / Rotate,
+ * GammaContrast / Invert) and AugmentedSegmentationDataset.__getitem__ (data/segmentation_dataset.py:80-107: augment, ToTensor,
+ * Normalize(0.5, 0.5), colours -> class ids, resize to image_size) do per sample with imgaug and PIL on the host, for a batch.
+ * The augmentation is stated exactly in DESIGN.md §12 and is NOT pinned against imgaug.
+ * sis_augment_warp (utils/augment_dataset.py:33-59, data/segmentation_dataset.py:80-107): one launch per batch.  pixels uint8
+ *   [n_samples][height][width][3] and classes uint8 [n_samples][height][width] are the resident dataset; slot b of the batch
+ *   reads sample index[b] (an id outside 0..n_samples-1 yields a zero image / background).  For output pixel (x, y) of slot b:
+ *   q = minv[b] (row-major 2x3) * (x, y, 1); with f = field_slot[b] in 0..num_fields-1, s = q + (field[f][0], field[f][1])
+ *   sampled bilinearly at q with edge clamp (field [num_fields][2][height][width], component 0 = x), else s = q; image value =
+ *   sum over the four bilinear taps around s of w * lut[b][source byte], a tap outside the source contributing 0; with
+ *   `quantize` rounded half-to-even to a byte; then / 255, - 0.5, / 0.5 in true divisions (as sis_crop_patches_u8) into images
+ *   float32 [batch][3][out_h][out_w]; segmented int64 [batch][1][out_h][out_w] = the source class at (floor(s_x + 0.5),
+ *   floor(s_y + 0.5)), background_id outside.  All device pointers; no host sync.
+ * sis_elastic_field (utils/augment_dataset.py:35, iaa.ElasticTransformation): field[f][c] = alpha[f] * (G * noise[f][c]), G the
+ *   separable Gaussian of sigma[f] with radius floor(4 sigma + 0.5), weights normalised to sum 1, mirror boundary
+ *   (scipy.ndimage.gaussian_filter(mode="mirror", truncate=4.0)).  noise (device, [num_fields][2][height][width]) when given,
+ *   else uniform in [-1, 1) from the counter hash of (seeds[f], c, y * width + x) stated in DESIGN.md §12; noise_out (optional,
+ *   same shape) receives the noise used.  alpha / sigma / seeds are HOST arrays; sigma in (0, 9], num_fields <= 64, height and
+ *   width above the radius; workspace: num_fields * 2 * height * width floats. */
+int sis_augment_warp(float* images, int64_t* segmented, const uint8_t* pixels, const uint8_t* classes, const int* index,
+                     const float* minv, const uint8_t* lut, const int* field_slot, const float* field, int64_t n_samples,
+                     int batch, int height, int width, int num_fields, int background_id, int out_h, int out_w, int quantize,
+                     void* stream);
+int sis_elastic_field(float* field, float* workspace, float* noise_out, const float* noise, const float* alpha, const float* sigma,
+                      const uint32_t* seeds, int num_fields, int height, int width, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

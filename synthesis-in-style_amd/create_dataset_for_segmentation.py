@@ -7,7 +7,14 @@ layers on the device (FactorCatalog.predict) -> uint8 images on the device -> si
 in the reference's directory layout ``<id // 100000>/<id // 1000>/<id>.png`` (save_image, :84-90).
 
 Without a ``segmenter_type`` the label half of the PNG is the raw cluster-id map of ``label_layer``
-(id * 255 // (K-1) grey levels).  Not reproduced: COCO ground truth, train/val split, debug images.
+(id * 255 // (K-1) grey levels).  Not reproduced: COCO ground truth (``coco_gt.json``), the per-image class listing, debug images.
+
+Train / validation split (the reference's :180-202): after a normal run with ``--save-to`` (rank 0), or alone behind
+``--only-create-train-val-split``, the PNGs below the save directory are shuffled with ``random.seed(config['seed'])`` and
+written as ``train.json`` (90 %) / ``val.json`` (10 %), lists of ``{"file_name": path relative to the save directory}`` --
+what ``train.py --images train.json --val-images val.json`` reads (data/segmentation_dataset.py).  The files are listed in
+sorted order before the shuffle, so that the split depends on the seed and not on the file system.  With several ranks the
+split is not written (the ranks do not synchronise): run it alone afterwards.
 
 ``segmenter_type: "black_white_handwritten_printed"`` (the reference's default labeller, :52-65, with its config keys
 ``class_to_color_map``, ``keys_for_class_determination``, ``keys_for_finegrained_segmentation``, ``keys_to_merge``,
@@ -33,6 +40,7 @@ size: the union over ranks equals the single-GPU dataset (tests/test_dataset_ops
 import argparse
 import json
 import os
+import random
 from pathlib import Path
 
 import numpy
@@ -178,10 +186,35 @@ def build_dataset(args, creation_config, rank=0, world_size=1):
     return done, (lo, hi)
 
 
+def create_train_val_split(image_save_base_dir: Path, seed: int):
+    """train.json / val.json below ``image_save_base_dir``: seeded shuffle of its PNGs, the first 90 % train, the rest validation."""
+    image_save_base_dir = Path(image_save_base_dir)
+    generated_images = sorted(image_save_base_dir.glob('**/*.png'))
+    random.seed(seed)
+    random.shuffle(generated_images)
+    n_train = len(generated_images) * 9 // 10   # nine tenths train, the rest validation (floor, as int(0.9 n))
+    parts = {'train.json': generated_images[:n_train], 'val.json': generated_images[n_train:]}
+    for name, paths in parts.items():
+        with (image_save_base_dir / name).open('w') as f:
+            json.dump([{"file_name": str(path.relative_to(image_save_base_dir))} for path in paths], f)
+    return len(parts['train.json']), len(parts['val.json'])
+
+
 def main(args):
     creation_config = json.load(open(args.config)) if args.config else {}
     rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))
+    if getattr(args, 'only_create_train_val_split', False):
+        if not args.save_to:
+            raise ValueError('--only-create-train-val-split needs --save-to (the directory that holds the PNG pairs)')
+        n_train, n_val = create_train_val_split(Path(args.save_to), creation_config.get('seed', 1))
+        print(f"split: {n_train} training and {n_val} validation images", flush=True)
+        return
     done, (lo, hi) = build_dataset(args, creation_config, rank, world)
+    if args.save_to and world == 1:
+        create_train_val_split(Path(args.save_to), creation_config.get('seed', 1))
+    elif args.save_to and rank == 0:   # no collective in this tool: the other ranks may still be writing
+        print("several ranks: train.json / val.json are NOT written; run --only-create-train-val-split once all ranks are done",
+              flush=True)
     note = ""
     if creation_config.get('segmenter_type') == 'black_white_handwritten_printed':
         note = f", {len(args.dropped_image_ids)} of them dropped by the labeller and not written"
@@ -196,6 +229,8 @@ if __name__ == "__main__":
     parser.add_argument("-n", "--num-images", type=int, default=100)
     parser.add_argument("-s", "--save-to", help="directory for the PNG pairs (omit: generate only)")
     parser.add_argument("-b", "--batch-size", default=10, type=int)
+    parser.add_argument("--only-create-train-val-split", action='store_true', default=False,
+                        help="do not create a dataset: build train.json / val.json from the PNG pairs below --save-to")
     parser.add_argument("--truncate", action='store_true', default=False, help="truncation trick (psi 0.7, mean of 4096 latents)")
     parser.add_argument("--classifier-path", help="trained PixelEnsembleClassifier checkpoint (segmenter_type \"dataset_gan\")")
     parser.add_argument("--num-clusters", type=int, default=-1, help="K of catalogs/K.json and merged_classes_K.json "

@@ -8,9 +8,14 @@ int64 ``[1, S, S]``.  PNG is lossless, so the batch the trainer sees is a pure f
 label map that ``utils.dataset_creation.label_and_encode`` leaves ON THE DEVICE.  ``encode_batch`` is that function
 (same arithmetic, same order, bit for bit -- tests/test_dataset_ops_gpu.py round-trips a PNG through PIL against it)
 and ``SynthesisSegmentationLoader`` feeds an updater straight from a generator: no PNG, no PIL, no host copy.
-"""
-from typing import Dict, Iterator, Optional
 
+``DeviceSegmentationLoader`` is the loader of the written dataset: batches of a device-resident ``SegmentationDataset`` /
+``AugmentedSegmentationDataset`` (data/segmentation_dataset.py), one ``sis_hip.augment_warp`` launch each, in the place of the
+reference's ``DataLoader`` + ``DistributedSampler`` (utils/data_loading.py:52-75).
+"""
+from typing import Dict, Iterator, List, Optional
+
+import numpy
 import torch
 import torch.nn.functional as F
 
@@ -41,10 +46,17 @@ class SynthesisSegmentationLoader:
     uint8 pixels on the side stream -> ``encode_batch``.  Everything after the latents stays in HBM."""
 
     def __init__(self, generator, catalogs: Dict, label_layer: int, batch_size: int, class_of_cluster=None,
-                 image_size: Optional[int] = None, seed: int = 1, truncation_latent=None, num_batches: Optional[int] = None):
+                 image_size: Optional[int] = None, seed: int = 1, truncation_latent=None, num_batches: Optional[int] = None,
+                 num_augmentations: Optional[int] = None):
         self.generator, self.catalogs, self.label_layer = generator, catalogs, label_layer
         self.batch_size, self.class_of_cluster, self.image_size = batch_size, class_of_cluster, image_size
         self.seed, self.truncation_latent, self.num_batches = seed, truncation_latent, num_batches
+        # the reference trains on ``num_augmentations * N`` indices of which N are originals (segmentation_dataset.py:77-95):
+        # a slot stays unaugmented with probability 1 / num_augmentations.  None: no augmentation, the batches of before.
+        # Every slot of an augmenting loader goes through the warp, whose resize to ``image_size`` is bilinear for the image and
+        # pixel-centre nearest for the labels: its unaugmented slots equal the plain loader's only when ``image_size`` is the
+        # generator's size (the plain loader never resizes the image and resizes labels with F.interpolate's nearest).
+        self.num_augmentations = num_augmentations
 
     def __len__(self):
         return self.num_batches if self.num_batches is not None else 1 << 30
@@ -53,6 +65,7 @@ class SynthesisSegmentationLoader:
         g = self.generator
         device = g.input.input.device
         rng = torch.Generator().manual_seed(self.seed)
+        augment_rng = numpy.random.default_rng([self.seed, 0x617567]) if self.num_augmentations is not None else None
         i = 0
         while self.num_batches is None or i < self.num_batches:
             z = torch.randn(self.batch_size, g.style_dim, generator=rng).to(device, non_blocking=True)
@@ -64,8 +77,64 @@ class SynthesisSegmentationLoader:
                                                          {self.label_layer: self.catalogs[self.label_layer]})
                 if ready is not None:
                     torch.cuda.current_stream(device).wait_event(ready)
-                batch = encode_batch(pixels, labels[self.label_layer], self.class_of_cluster, self.image_size)
+                if augment_rng is None:
+                    batch = encode_batch(pixels, labels[self.label_layer], self.class_of_cluster, self.image_size)
+                else:
+                    batch = self._augmented(pixels, labels[self.label_layer], augment_rng)
             # yielded OUTSIDE the no_grad block: a generator suspended inside it would leave grad mode off in the consumer
             # (the updater keeps this iterator alive across its forward / backward)
             yield batch
             i += 1
+
+    def _augmented(self, pixels, labels, rng):
+        from utils.augment_dataset import augment_batch
+        classes = labels if self.class_of_cluster is None else self.class_of_cluster.to(labels.device)[labels]
+        if tuple(classes.shape[-2:]) != tuple(pixels.shape[1:3]):   # the label layer's resolution -> the image's, nearest
+            classes = F.interpolate(classes.unsqueeze(1).to(torch.float32), tuple(pixels.shape[1:3])).squeeze(1)
+        keep = rng.random(self.batch_size) < 1.0 / self.num_augmentations
+        return augment_batch(pixels.contiguous(), classes.to(torch.uint8).contiguous(), list(range(self.batch_size)), rng,
+                             out_size=self.image_size, augment=[not k for k in keep])
+
+
+def epoch_indices(length: int, epoch: int, shuffle: bool, seed: int, rank: int = 0, world_size: int = 1) -> List[int]:
+    """The dataset indices of one rank in one epoch, as ``DistributedSampler`` deals them: a permutation seeded by (seed, epoch)
+    -- the same on every rank --, padded from its own start to a multiple of the world size, split by stride."""
+    order = numpy.random.default_rng([seed, epoch]).permutation(length) if shuffle else numpy.arange(length)
+    total = -(-length // world_size) * world_size
+    order = numpy.resize(order, total)   # repeats from the start, as the sampler's padding
+    return [int(i) for i in order[rank:total:world_size]]
+
+
+class DeviceSegmentationLoader:
+    """Iterable of {"images", "segmented"} batches of a device-resident dataset; one pass is one epoch, and every new pass
+    takes the next epoch's permutation and augmentation draws."""
+
+    def __init__(self, dataset, batch_size: int, shuffle: bool = True, drop_last: bool = True, rank: int = 0, world_size: int = 1,
+                 seed: int = 0):
+        if not 0 <= rank < world_size:
+            raise ValueError(f"rank {rank} outside 0..{world_size - 1}")
+        self.dataset, self.batch_size, self.shuffle, self.drop_last = dataset, batch_size, shuffle, drop_last
+        self.rank, self.world_size, self.seed, self.epoch = rank, world_size, seed, 0
+
+    def set_epoch(self, epoch: int):
+        self.epoch = epoch
+
+    def indices(self, epoch: Optional[int] = None) -> List[int]:
+        return epoch_indices(len(self.dataset), self.epoch if epoch is None else epoch, self.shuffle, self.seed, self.rank,
+                             self.world_size)
+
+    def __len__(self):
+        per_rank = -(-len(self.dataset) // self.world_size)
+        return per_rank // self.batch_size if self.drop_last else -(-per_rank // self.batch_size)
+
+    def __iter__(self) -> Iterator[Dict[str, torch.Tensor]]:
+        epoch, self.epoch = self.epoch, self.epoch + 1
+        order = self.indices(epoch)
+        for lo in range(0, len(order), self.batch_size):
+            chunk = order[lo:lo + self.batch_size]
+            if len(chunk) < self.batch_size and self.drop_last:
+                break
+            with torch.no_grad():
+                batch = self.dataset.get_batch(chunk, epoch=epoch, seed=self.seed)
+            # yielded OUTSIDE the no_grad block, as SynthesisSegmentationLoader does and for the same reason
+            yield batch

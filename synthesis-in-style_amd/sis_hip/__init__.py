@@ -175,6 +175,8 @@ _SIGNATURES = {
     "sis_remove_small_contours": ([_vp, _vp, _vp, _i64, _i, _i, _i, _f, _i, _i, _vp], _i),
     "sis_cluster_segment_workspace_bytes": ([_i] * 5, _i64),
     "sis_cluster_segment": ([_vp] * 5 + [_i, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp], _i),
+    "sis_augment_warp": ([_vp] * 9 + [_i64] + [_i] * 8 + [_vp], _i),
+    "sis_elastic_field": ([_vp] * 7 + [_i, _i, _i, _vp], _i),
 }
 
 
@@ -2696,3 +2698,95 @@ def pixel_ensemble_label(full, groups, w1f, b1, w2t, b2, w3t, b3, classes, hidde
                                                              members, classes, hidden1, _stream())),
                "sis_pixel_ensemble_head")
     return labels, rgb, logits
+
+
+# ------------------------------------------------------------------------------ training-time augmentation
+
+ELASTIC_MAX_FIELDS = 64   # per launch of sis_elastic_field; the binding splits longer lists
+ELASTIC_MAX_SIGMA = 9.0
+
+
+def elastic_radius(sigma):
+    """floor(4 sigma + 0.5) in float32, the filter radius the kernel uses (scipy: int(truncate * sigma + 0.5))."""
+    import numpy
+    return int(numpy.float32(4.0) * numpy.float32(sigma) + numpy.float32(0.5))
+
+
+def elastic_field(height, width, sigma, alpha, seeds=None, noise=None, device=None, return_noise=False):
+    """Displacement fields [F, 2, H, W] float32 (component 0 = x) for F = len(sigma) elastic draws: alpha * (Gaussian of sigma,
+    mirror boundary, radius floor(4 sigma + 0.5)) * noise.  ``seeds``: F 32-bit words for the counter hash of DESIGN.md §12;
+    ``noise``: a float32 [F, 2, H, W] device tensor to blur instead (tests).  An image that is not larger than a filter radius,
+    or a sigma above 9, is refused with ``ValueError`` before anything is launched."""
+    sigma, alpha = [float(v) for v in sigma], [float(v) for v in alpha]
+    n = len(sigma)
+    if n == 0 or len(alpha) != n:
+        raise ValueError("elastic_field: one alpha per sigma, at least one field")
+    for sg in sigma:
+        if not 0.0 < sg <= ELASTIC_MAX_SIGMA:
+            raise ValueError(f"elastic_field: sigma {sg} outside (0, {ELASTIC_MAX_SIGMA}]")
+        if min(height, width) <= elastic_radius(sg):
+            raise ValueError(f"elastic_field: a {height}x{width} image is not larger than the filter radius "
+                             f"{elastic_radius(sg)} of sigma {sg}")
+    if noise is not None:
+        noise = _f32(noise, "noise")
+        if tuple(noise.shape) != (n, 2, height, width):
+            raise RuntimeError(f"noise must be [{n}, 2, {height}, {width}], got {tuple(noise.shape)}")
+        device = noise.device
+    elif seeds is None or len(seeds) != n:
+        raise ValueError("elastic_field: one seed word per field, or a noise tensor")
+    device = torch.device(device if device is not None else "cuda")
+    if device.type != "cuda":
+        raise RuntimeError("device must be a CUDA tensor")
+    field = torch.empty((n, 2, height, width), dtype=torch.float32, device=device)
+    ws = torch.empty_like(field)
+    used = torch.empty_like(field) if return_noise else None
+    with torch.cuda.device(device):
+        for lo in range(0, n, ELASTIC_MAX_FIELDS):
+            m = min(ELASTIC_MAX_FIELDS, n - lo)
+            c_alpha, c_sigma = (ctypes.c_float * m)(*alpha[lo:lo + m]), (ctypes.c_float * m)(*sigma[lo:lo + m])
+            c_seeds = None if seeds is None else (ctypes.c_uint32 * m)(*[int(v) & 0xFFFFFFFF for v in seeds[lo:lo + m]])
+            _check(_launch("elastic_field", 0.0, 16.0 * m * 2 * height * width,
+                           lambda: lib().sis_elastic_field(_ptr(field[lo:]), _ptr(ws[lo:]), None if used is None else _ptr(used[lo:]),
+                                                           None if noise is None else _ptr(noise[lo:]), c_alpha, c_sigma, c_seeds,
+                                                           m, height, width, _stream())), "sis_elastic_field")
+    return (field, used) if return_noise else field
+
+
+def augment_warp(pixels, classes, index, minv, lut, field_slot, field=None, background_id=0, out_size=None, quantize=True):
+    """One batch of the reference loaders' contract from the resident dataset (csrc/augment.hip): pixels uint8
+    [N, H, W, 3], classes uint8 [N, H, W], index int32 [B], minv float32 [B, 2, 3], lut uint8 [B, 256], field_slot int32 [B]
+    (-1: no elastic), field float32 [F, 2, H, W] or None, all on one device -> {"images": float32 [B, 3, S, S], "segmented":
+    int64 [B, 1, S, S]}.  ``out_size``: S, or (height, width); default: the source size."""
+    for t, name, dtype in ((pixels, "pixels", torch.uint8), (classes, "classes", torch.uint8), (index, "index", torch.int32),
+                           (minv, "minv", torch.float32), (lut, "lut", torch.uint8), (field_slot, "field_slot", torch.int32)):
+        require_device(t, name)
+        if t.dtype != dtype or not t.is_contiguous() or t.device != pixels.device:
+            raise RuntimeError(f"{name} must be a contiguous {dtype} tensor on the device of pixels")
+    if pixels.dim() != 4 or pixels.shape[3] != 3 or tuple(classes.shape) != tuple(pixels.shape[:3]):
+        raise RuntimeError("pixels must be [N, H, W, 3] and classes [N, H, W]")
+    n, h, w, _ = pixels.shape
+    b = index.numel()
+    if tuple(minv.shape) != (b, 2, 3) or tuple(lut.shape) != (b, 256) or field_slot.numel() != b:
+        raise RuntimeError("minv must be [B, 2, 3], lut [B, 256] and field_slot [B] for index [B]")
+    num_fields = 0
+    if field is not None:
+        field = _f32(field, "field")
+        if field.dim() != 4 or tuple(field.shape[1:]) != (2, h, w) or field.device != pixels.device:
+            raise RuntimeError(f"field must be [F, 2, {h}, {w}] on the device of pixels")
+        num_fields = field.shape[0]
+    if out_size is None:
+        out_h, out_w = h, w
+    elif isinstance(out_size, int):
+        out_h = out_w = out_size
+    else:
+        out_h, out_w = (int(v) for v in out_size)
+    images = torch.empty((b, 3, out_h, out_w), dtype=torch.float32, device=pixels.device)
+    segmented = torch.empty((b, 1, out_h, out_w), dtype=torch.int64, device=pixels.device)
+    with torch.cuda.device(pixels.device):
+        # per output pixel: 12 + 8 bytes written, 4 taps of 3 source bytes and 1 class byte read (fields: 8 more taps of 4 bytes)
+        _check(_launch("augment_warp_kernel", 0.0, 33.0 * images.numel() / 3,
+                       lambda: lib().sis_augment_warp(_ptr(images), _ptr(segmented), _ptr(pixels), _ptr(classes), _ptr(index),
+                                                      _ptr(minv), _ptr(lut), _ptr(field_slot), _ptr(field), n, b, h, w, num_fields,
+                                                      int(background_id), out_h, out_w, int(bool(quantize)), _stream())),
+               "sis_augment_warp")
+    return {"images": images, "segmented": segmented}

@@ -14,6 +14,7 @@ import json
 import logging
 import os
 import time
+from pathlib import Path
 
 import torch
 import torch.distributed as dist
@@ -68,10 +69,17 @@ def get_scheduler(config: dict, iterations_per_epoch: int, optimizers: dict):
     return {name: ClampedCosineAnnealingLR(opt, end, eta_min=eta_min) for name, opt in optimizers.items()}
 
 
-def get_data_loader(config: dict, rank: int, device):
-    if config.get('train_json') and not config.get('synthetic'):
-        raise NotImplementedError("the JSON/PNG + imgaug input pipeline is host-side and out of the hot path; "
-                                  "pass --synthetic or supply your own iterable of {'images','segmented'} batches")
+def get_data_loader(config: dict, rank: int, device, args: argparse.Namespace = None, world_size: int = 1,
+                    validation: bool = False):
+    """--images / --val-images: the JSON-listed PNG pairs, resident on the device and augmented there (utils/data_loading.py,
+    reference train.py:86-93); --synthetic, or no json: random batches."""
+    json_path = config.get('validation_json' if validation else 'train_json')
+    if json_path and not config.get('synthetic'):
+        from utils.data_loading import get_data_loader as get_png_loader
+        return get_png_loader(Path(json_path), config.get('dataset', 'wpi'), args, config, validation=validation, rank=rank,
+                              world_size=world_size, device=device)
+    if validation:
+        return None
     return SyntheticSegmentationLoader(config['batch_size'], config['image_size'], config['num_classes'],
                                        seed=1234 + rank, device=device, num_batches=config.get('iterations_per_epoch'))
 
@@ -84,8 +92,9 @@ def main(rank: int, args: argparse.Namespace, world_size: int):
     device = torch.device('cuda', rank % torch.cuda.device_count()) if torch.cuda.is_available() else torch.device('cpu')
     if device.type == 'cuda':
         torch.cuda.set_device(device)
-    loader = get_data_loader(config, rank, device)
-    builder = get_train_builder_class(config)(config, loader, None, rank=rank, world_size=world_size)
+    loader = get_data_loader(config, rank, device, args, world_size)
+    val_loader = get_data_loader(config, rank, device, args, world_size, validation=True)
+    builder = get_train_builder_class(config)(config, loader, val_loader, rank=rank, world_size=world_size)
     updater = builder.get_updater()
     per_epoch = config.get('iterations_per_epoch') or len(loader)
     max_iter = config['max_iter'] if 'max_iter' in config and config['max_iter'] else config['epochs'] * per_epoch
@@ -118,6 +127,8 @@ def parse_args(argv=None):
     parser.add_argument('config', help='path to config with common train settings, such as LR')
     parser.add_argument('--images', dest='train_json', help='path to json file with train images')
     parser.add_argument('--val-images', dest='validation_json', help='path to json file with validation images')
+    parser.add_argument('--class-to-color-map', help='path to json file with class color map (class name -> colour of the label '
+                        'halves of --images; required with --images)')
     parser.add_argument('--mpi-backend', default='nccl', choices=['nccl', 'gloo'], help='torch.distributed backend')
     parser.add_argument('--fine-tune', dest='fine_tune', help='Path to model to finetune from')
     parser.add_argument('-l', '--log-dir', default='logs', help='where to write snapshots')
