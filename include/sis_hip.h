@@ -685,6 +685,7 @@ int sis_ce_dice_bwd(void* grad_logits, const void* logits, int dtype, const int6
  *                          counter stream (seed word, site, quad e / 4), mask (sis_bn_mask_words int64 words, or NULL) = one bit
  *                          per element: (relu output > 0) & kept.  eval = 1: invstd_or_var is the running variance, no dropout.
  *   sis_bn_drop_bwd        dx, dgamma, dbeta from dy (batch stride dy_batch_stride) + dy2 (contiguous, or NULL) and the mask.
+ *                          workspace: sis_bn_drop_bwd_workspace_floats floats, 16-byte aligned (the per-channel sums are kept in double).
  *   sis_weighted_ce_fwd    loss[0] = sum w[y] nll / sum w[y] (nn.CrossEntropyLoss(weight=w)); stats[0] = sum w[y]; weight NULL = 1.
  *   sis_weighted_ce_bwd    grad_logits = grad_loss[0] * d loss / d logits.
  *   sis_adam_clip_step     clip_grad_norm_(all gradients of the table, max_norm) then torch.optim.Adam (L2 weight decay added to the

@@ -300,30 +300,60 @@ __device__ __forceinline__ void bn_drop_grad4(const BnDropBwdArgs& a, int b, int
     }
 }
 
-// partial[c][s] = (sum g', sum g' * xhat) over slice s of channel c
-__global__ __launch_bounds__(256) void bn_drop_bwd_reduce_kernel(float* __restrict__ partial, BnDropBwdArgs a, int S) {
-    __shared__ float red[4];
+__device__ __forceinline__ double dc_block_sum_f64(double v, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// partial[c][s] = (sum g', sum g' * xhat) over slice s of channel c, in double: sum of the gated g, and of g * (x - mean), with
+// exact products, scaled by keep_scale (and invstd) once at the end.  dgamma[c] and dbeta[c] are sums of gradients of both signs
+// that cancel to a small part of sum |terms|: an fp32 running sum over fp32-rounded terms left ~1e-8 - 6e-8 sum |terms|, which is
+// more than 1e-5 of the result on the channels that cancel to 1e-3 (a few per thousand).  Summed this way dbeta is exact up to its
+// final rounding, and dgamma up to the fp32 statistics it is given.  The kernel is bound by its loads.
+__global__ __launch_bounds__(256) void bn_drop_bwd_reduce_kernel(double* __restrict__ partial, BnDropBwdArgs a, int S) {
+    __shared__ double red[4];
     const int c = blockIdx.x / S, s = blockIdx.x % S;
     const int64_t n4 = (int64_t)a.B * a.HW4, lo = (int64_t)s * BD_SLICE4, hi = min(n4, lo + BD_SLICE4);
-    float s0 = 0.f, s1 = 0.f;
+    const double m = a.mean[c];
+    double s0 = 0., s1 = 0.;
     for (int64_t j = lo + threadIdx.x; j < hi; j += 256) {
         const int b = (int)(j / a.HW4), r4 = (int)(j % a.HW4);
-        float g[4], xh[4];
-        bn_drop_grad4(a, b, c, r4, g, xh);
+        const int64_t i = ((int64_t)b * a.C + c) * a.HW4 + r4;
+        const float4 g1 = *reinterpret_cast<const float4*>(a.dy1 + b * a.dy1_bstride + ((int64_t)c * a.HW4 + r4) * 4);
+        float g[4] = {g1.x, g1.y, g1.z, g1.w};
+        if (a.dy2) {   // the same fp32 sum as bn_drop_grad4: the gradient the apply kernel uses
+            const float4 g2 = reinterpret_cast<const float4*>(a.dy2)[i];
+            g[0] += g2.x; g[1] += g2.y; g[2] += g2.z; g[3] += g2.w;
+        }
+        const float4 xv = reinterpret_cast<const float4*>(a.x)[i];
+        const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { s0 += g[q]; s1 = __builtin_fmaf(g[q], xh[q], s1); }
+        for (int q = 0; q < 4; ++q) {
+            const bool on = (a.mask[((i >> 6) << 2) + q] >> (i & 63)) & 1ull;
+            const double gq = on ? (double)g[q] : 0.;
+            s0 += gq;
+            s1 += gq * ((double)xs[q] - m);
+        }
     }
-    s0 = dc_block_sum(s0, red);
-    s1 = dc_block_sum(s1, red);
-    if (threadIdx.x == 0) { partial[2 * blockIdx.x] = s0; partial[2 * blockIdx.x + 1] = s1; }
+    s0 = dc_block_sum_f64(s0, red);
+    s1 = dc_block_sum_f64(s1, red);
+    if (threadIdx.x == 0) {
+        partial[2 * blockIdx.x] = s0 * (double)a.keep_scale;
+        partial[2 * blockIdx.x + 1] = s1 * (double)a.keep_scale * (double)a.invstd[c];
+    }
 }
 
 __global__ void bn_drop_bwd_finish_kernel(float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ coef,
-                                          const float* __restrict__ partial, int C, int S, float inv_n) {
+                                          const double* __restrict__ partial, int C, int S, float inv_n) {
     const int c = blockIdx.x * 64 + threadIdx.x;
     if (c >= C) return;
-    float s0 = 0.f, s1 = 0.f;
-    for (int s = 0; s < S; ++s) { s0 += partial[2 * (c * S + s)]; s1 += partial[2 * (c * S + s) + 1]; }
+    double d0 = 0., d1 = 0.;
+    for (int s = 0; s < S; ++s) { d0 += partial[2 * (c * S + s)]; d1 += partial[2 * (c * S + s) + 1]; }
+    const float s0 = (float)d0, s1 = (float)d1;
     dbeta[c] = s0;
     dgamma[c] = s1;
     coef[2 * c] = s0 * inv_n;
@@ -587,7 +617,8 @@ extern "C" int sis_transpose2d(float* out, const float* in, int rows, int cols, 
 }
 
 extern "C" int64_t sis_bn_drop_bwd_workspace_floats(int batch, int channels, int hw) {
-    return (int64_t)channels * sis_cdiv((int64_t)batch * hw / 4, BD_SLICE4) * 2 + 2 * (int64_t)channels;
+    // [C][S][2] double partials (4 floats each pair), then [C][2] float coefficients
+    return (int64_t)channels * sis_cdiv((int64_t)batch * hw / 4, BD_SLICE4) * 4 + 2 * (int64_t)channels;
 }
 
 extern "C" int sis_bn_drop_fwd(float* y, int64_t y_batch_stride, const float* x, const float* mean, const float* invstd_or_var,
@@ -614,18 +645,19 @@ extern "C" int sis_bn_drop_bwd(float* dx, float* dgamma, float* dbeta, const flo
     if (batch <= 0) return 0;
     SIS_REQUIRE(dx && dgamma && dbeta && dy && x && mean && invstd && mask && workspace, "sis_bn_drop_bwd: null pointer");
     SIS_REQUIRE(hw % 4 == 0 && dy_batch_stride % 4 == 0, "sis_bn_drop_bwd: H*W and the batch stride must be multiples of 4");
-    SIS_REQUIRE((((uintptr_t)dx | (uintptr_t)dy | (uintptr_t)dy2 | (uintptr_t)x) & 15) == 0, "sis_bn_drop_bwd: 16-byte alignment");
+    SIS_REQUIRE((((uintptr_t)dx | (uintptr_t)dy | (uintptr_t)dy2 | (uintptr_t)x | (uintptr_t)workspace) & 15) == 0, "sis_bn_drop_bwd: 16-byte alignment");
     SIS_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "sis_bn_drop_bwd: dropout probability %f", drop_p);
     BnDropBwdArgs a;
     a.dy1 = dy; a.dy1_bstride = dy_batch_stride; a.dy2 = dy2; a.x = x; a.mean = mean; a.invstd = invstd;
     a.mask = (const unsigned long long*)mask; a.keep_scale = sis_drop_scale(sis_drop_thr16(drop_p));
     a.B = batch; a.C = channels; a.HW4 = hw / 4;
     const int S = sis_cdiv((int64_t)batch * hw / 4, BD_SLICE4);
-    float* coef = workspace + (int64_t)channels * S * 2;
+    double* partial = reinterpret_cast<double*>(workspace);
+    float* coef = workspace + (int64_t)channels * S * 4;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(bn_drop_bwd_reduce_kernel, dim3(channels * S), dim3(256), 0, st, workspace, a, S);
+    hipLaunchKernelGGL(bn_drop_bwd_reduce_kernel, dim3(channels * S), dim3(256), 0, st, partial, a, S);
     SIS_CHECK_LAUNCH("bn_drop_bwd_reduce_kernel");
-    hipLaunchKernelGGL(bn_drop_bwd_finish_kernel, dim3(sis_cdiv(channels, 64)), dim3(64), 0, st, dgamma, dbeta, coef, workspace,
+    hipLaunchKernelGGL(bn_drop_bwd_finish_kernel, dim3(sis_cdiv(channels, 64)), dim3(64), 0, st, dgamma, dbeta, coef, partial,
                        channels, S, 1.f / (float)((int64_t)batch * hw));
     SIS_CHECK_LAUNCH("bn_drop_bwd_finish_kernel");
     const int64_t total4 = (int64_t)batch * channels * hw / 4;

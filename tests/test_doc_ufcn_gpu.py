@@ -263,8 +263,14 @@ def _step_parity(cls, batch, size, tol_logits=1e-4, median_check=True, **kw):
         # moves one element's gradient by O(1); 3e-2 caps such an outlier
         assert own[-1] < max(3e-2, 8 * lib[-1]), (name, own[-1], lib[-1])
     # systematic precision: the own path's typical error is that of the fp32 library step (each kernel alone is at ~1e-7).
-    # Held at the configuration shape.  At B = 2, 64^2 it is NOT held (open): there the own path's median
-    # gradient error is 3.4e-3 with dropout (library 2e-6) and 1.0e-2 without (library 4.5e-3), cause not found yet.
+    # Held at the configuration shape.  At B = 2, 64^2 it is not asserted (median_check=False; DESIGN.md §7,
+    # profiles/doc_ufcn_small_shape_localisation.txt): of the step's 3 031 040 ReLU gates, up to four in the own step and up to
+    # two in the library step fall on the other side of zero than in float64 (pre-activations within fp32 rounding of zero), each
+    # turns one element's gradient on or off, and every layer upstream inherits ~1 / sqrt(elements): without dropout medians of
+    # 1.0e-2 (own) and 4.5e-3 - 9.0e-3 (library, by machine), in the own step 9.7e-6 once the float64 model's gates are forced on
+    # its kernels; with dropout 3e-6 when no gate flips and 2e-3 when one does, by seed word.  Which gates flip differs between two
+    # correct fp32 implementations, so 2x the library's median is not a property of the kernels at this shape; they are pinned
+    # call by call, on the step's own tensors, by tests/test_doc_ufcn_layouts_gpu.py::test_step_kernels_at_their_in_step_inputs.
     if median_check:
         assert np.median(own) < max(1e-3, 2.0 * np.median(lib)), (np.median(own), np.median(lib))
     for (name, b), (_, c) in zip(net.named_buffers(), ref.named_buffers()):
