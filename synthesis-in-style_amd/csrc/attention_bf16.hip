@@ -26,13 +26,6 @@
 
 namespace {
 
-typedef unsigned short u16;
-typedef sis_bf16x8 bf16x8;
-typedef sis_bf16x4 bf16x4;
-typedef sis_f32x16 f32x16;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
-
 constexpr int HD = 64;               // head size
 constexpr int TILE_BYTES = 64 * 128;
 constexpr int STAGE_BYTES = 2 * TILE_BYTES;
@@ -40,11 +33,11 @@ constexpr int LDS_BYTES = 2 * STAGE_BYTES;
 [[maybe_unused]] constexpr float NEG_BIG = -1e30f;
 
 struct AttnParams {
-    const u16* qkv;      // [B, N, 3 * H * 64]: q | k | v, head h at columns h * 64
-    const u16* ctx;      // [B, N, H * 64] forward output (backward input)
-    const u16* d_ctx;    // [B, N, H * 64] gradient of the context
-    u16* out_ctx;        // forward
-    u16* d_qkv;          // backward
+    const sis_u16* qkv;      // [B, N, 3 * H * 64]: q | k | v, head h at columns h * 64
+    const sis_u16* ctx;      // [B, N, H * 64] forward output (backward input)
+    const sis_u16* d_ctx;    // [B, N, H * 64] gradient of the context
+    sis_u16* out_ctx;        // forward
+    sis_u16* d_qkv;          // backward
     float* lse;          // [B, H, N] log-sum-exp of the scaled scores
     float* delta;        // [B, H, N] rowsum(dO o O)
     int B, N, H, blocks; // blocks = ceil(N / 128)
@@ -63,9 +56,9 @@ __device__ __forceinline__ float other_half(float x) {
 __device__ __forceinline__ float half_max(float x) { return fmaxf(x, other_half(x)); }
 __device__ __forceinline__ float half_sum(float x) { return x + other_half(x); }
 
-__device__ __forceinline__ bf16x8 pack8(const float* v) {
-    const u32x4 u = {sis_pack_bf16x2(v[0], v[1]), sis_pack_bf16x2(v[2], v[3]), sis_pack_bf16x2(v[4], v[5]), sis_pack_bf16x2(v[6], v[7])};
-    return __builtin_bit_cast(bf16x8, u);
+__device__ __forceinline__ sis_bf16x8 pack8(const float* v) {
+    const sis_u32x4 u = {sis_pack_bf16x2(v[0], v[1]), sis_pack_bf16x2(v[2], v[3]), sis_pack_bf16x2(v[4], v[5]), sis_pack_bf16x2(v[6], v[7])};
+    return __builtin_bit_cast(sis_bf16x8, u);
 }
 
 // Everything a wave needs to stage tiles and read fragments; `lane` dependent parts are computed once.
@@ -99,27 +92,27 @@ __device__ __forceinline__ void tile_io_init(TileIo& io, int lane, int wave, int
 __device__ __forceinline__ void tile_dma(__amdgpu_buffer_rsrc_t rs, unsigned char* dst, const int* src_off, int wave, int base_bytes) {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(dst + (wave + 4 * i) * 1024), 16, src_off[i], base_bytes, 0, 0);
+        sis_buffer_load_lds16(rs, dst + (wave + 4 * i) * 1024, src_off[i], base_bytes);
 }
 
-__device__ __forceinline__ bf16x8 row_frag(const unsigned char* tile, const TileIo& io, int rb, int ks) {
-    return *reinterpret_cast<const bf16x8*>(tile + rb * 4096 + io.roff[ks]);
+__device__ __forceinline__ sis_bf16x8 row_frag(const unsigned char* tile, const TileIo& io, int rb, int ks) {
+    return *reinterpret_cast<const sis_bf16x8*>(tile + rb * 4096 + io.roff[ks]);
 }
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* tile, const TileIo& io, int db, int kbase16) {
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(tile + kbase16 * 2048 + io.toff[db][0]));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(tile + kbase16 * 2048 + io.toff[db][1]));
+__device__ __forceinline__ sis_bf16x8 tr_frag(const unsigned char* tile, const TileIo& io, int db, int kbase16) {
+    const sis_bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) sis_bf16x4*)(tile + kbase16 * 2048 + io.toff[db][0]));
+    const sis_bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) sis_bf16x4*)(tile + kbase16 * 2048 + io.toff[db][1]));
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
 // B-operand fragments of the wave's own 32 rows (lane = row, 16 k per step) straight from global memory
-__device__ __forceinline__ void own_frags(bf16x8* f, const u16* base, int row, int ld, int lane) {
-    const u16* p = base + (long long)row * ld + 8 * (lane >> 5);
+__device__ __forceinline__ void own_frags(sis_bf16x8* f, const sis_u16* base, int row, int ld, int lane) {
+    const sis_u16* p = base + (long long)row * ld + 8 * (lane >> 5);
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) f[ks] = *reinterpret_cast<const bf16x8*>(p + 16 * ks);
+    for (int ks = 0; ks < 4; ++ks) f[ks] = *reinterpret_cast<const sis_bf16x8*>(p + 16 * ks);
 }
 
 // write a wave's 32 x 64 result held as X^T (rows d in the registers, own row on the lane) through LDS as whole 128-B rows
-__device__ __forceinline__ void store_rows(unsigned char* scratch, const f32x16* acc, float mul, u16* gbase, int ld, int row0, int n_rows,
+__device__ __forceinline__ void store_rows(unsigned char* scratch, const sis_f32x16* acc, float mul, sis_u16* gbase, int ld, int row0, int n_rows,
                                            int lane) {
     const int r32 = lane & 31, h = lane >> 5;
 #pragma unroll
@@ -160,11 +153,11 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(AttnParams p) {
     const int r32 = lane & 31, h = lane >> 5;
     const int ldq = 3 * p.H * HD, ldo = p.H * HD;
     const int q0 = blk * 128 + wave * 32;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(p.qkv), 0, p.qkv_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = sis_buffer_rsrc(p.qkv, p.qkv_bytes);
     TileIo io;
     tile_io_init(io, lane, wave, ldq);
 
-    bf16x8 qf[4];
+    sis_bf16x8 qf[4];
     own_frags(qf, p.qkv + ((long long)b * p.N) * ldq + hd * HD, min(q0 + r32, p.N - 1), ldq, lane);
 
     const int tiles = (p.N + 63) >> 6;
@@ -176,7 +169,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(AttnParams p) {
 
     const float c = p.scale * 1.4426950408889634f;
     float m_run = NEG_BIG, l_run = 0.f;
-    f32x16 oacc[2];
+    sis_f32x16 oacc[2];
 #pragma unroll
     for (int i = 0; i < 16; ++i) { oacc[0][i] = 0.f; oacc[1][i] = 0.f; }
 
@@ -190,8 +183,8 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(AttnParams p) {
         // Every fragment of a phase is requested before the phase's first MFMA (left to itself the compiler reads one fragment,
         // waits for it, multiplies, reads the next: eight exposed LDS latencies per product); the V^T fragments of the second
         // product are requested before the softmax arithmetic, which does not need them, and land underneath it.
-        f32x16 s[2];
-        bf16x8 kfr[2][4];
+        sis_f32x16 s[2];
+        sis_bf16x8 kfr[2][4];
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -204,7 +197,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(AttnParams p) {
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[kb][ks], qf[ks], s[kb], 0, 0, 0);
         }
-        bf16x8 vfr[2][4];
+        sis_bf16x8 vfr[2][4];
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -228,7 +221,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(AttnParams p) {
         const float mc = c * m_new;
         m_run = m_new;
         float sum = 0.f;
-        bf16x8 pf[2][2];
+        sis_bf16x8 pf[2][2];
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -271,17 +264,17 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(AttnParams p) {
     const int r32 = lane & 31, h = lane >> 5;
     const int ldq = 3 * p.H * HD, ldo = p.H * HD;
     const int q0 = blk * 128 + wave * 32;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(p.qkv), 0, p.qkv_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = sis_buffer_rsrc(p.qkv, p.qkv_bytes);
     TileIo io;
     tile_io_init(io, lane, wave, ldq);
 
     const int qc = min(q0 + r32, p.N - 1);
-    bf16x8 qf[4], gf[4];
+    sis_bf16x8 qf[4], gf[4];
     own_frags(qf, p.qkv + ((long long)b * p.N) * ldq + hd * HD, qc, ldq, lane);
     own_frags(gf, p.d_ctx + ((long long)b * p.N) * ldo + hd * HD, qc, ldo, lane);
     float dl = 0.f;
     {
-        bf16x8 of[4];
+        sis_bf16x8 of[4];
         own_frags(of, p.ctx + ((long long)b * p.N) * ldo + hd * HD, qc, ldo, lane);
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks)
@@ -300,7 +293,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(AttnParams p) {
         tile_dma(rs, lds + stage * STAGE_BYTES, io.src_off, wave, k_base + t * 64 * ldq * 2);
         tile_dma(rs, lds + stage * STAGE_BYTES + TILE_BYTES, io.src_off, wave, v_base + t * 64 * ldq * 2);
     };
-    f32x16 dq[2];
+    sis_f32x16 dq[2];
 #pragma unroll
     for (int i = 0; i < 16; ++i) { dq[0][i] = 0.f; dq[1][i] = 0.f; }
 
@@ -311,13 +304,13 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(AttnParams p) {
         if (t + 1 < tiles) issue(t + 1, (t + 1) & 1);
         const unsigned char* kt = lds + (t & 1) * STAGE_BYTES;
         const unsigned char* vt = kt + TILE_BYTES;
-        bf16x8 dsf[2][2];
+        sis_bf16x8 dsf[2][2];
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
-            f32x16 s, dp;
+            sis_f32x16 s, dp;
 #pragma unroll
             for (int i = 0; i < 16; ++i) { s[i] = s_init; dp[i] = -dl; }
-            bf16x8 kfr[4], vfr[4];   // all eight row fragments of this key block before its first MFMA
+            sis_bf16x8 kfr[4], vfr[4];   // all eight row fragments of this key block before its first MFMA
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) { kfr[ks] = row_frag(kt, io, kb, ks); vfr[ks] = row_frag(vt, io, kb, ks); }
             __builtin_amdgcn_sched_barrier(0);
@@ -339,7 +332,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(AttnParams p) {
                 dsf[kb][sx] = pack8(e);
             }
         }
-        bf16x8 ktr[2][4];   // K^T fragments of the third product, all requested first
+        sis_bf16x8 ktr[2][4];   // K^T fragments of the third product, all requested first
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -369,14 +362,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnParams p) {
     const int r32 = lane & 31, h = lane >> 5;
     const int ldq = 3 * p.H * HD, ldo = p.H * HD;
     const int k0 = blk * 128 + wave * 32;
-    const __amdgpu_buffer_rsrc_t rsq = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(p.qkv), 0, p.qkv_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(p.d_ctx), 0, p.ctx_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsq = sis_buffer_rsrc(p.qkv, p.qkv_bytes);
+    const __amdgpu_buffer_rsrc_t rso = sis_buffer_rsrc(p.d_ctx, p.ctx_bytes);
     TileIo io, io_o;
     tile_io_init(io, lane, wave, ldq);
     tile_io_init(io_o, lane, wave, ldo);   // (only the DMA offsets differ: same LDS image)
 
     const int kc = min(k0 + r32, p.N - 1);
-    bf16x8 kf[4], vf[4];
+    sis_bf16x8 kf[4], vf[4];
     own_frags(kf, p.qkv + ((long long)b * p.N) * ldq + p.H * HD + hd * HD, kc, ldq, lane);
     own_frags(vf, p.qkv + ((long long)b * p.N) * ldq + 2 * p.H * HD + hd * HD, kc, ldq, lane);
     const long long stat = ((long long)b * p.H + hd) * p.N;
@@ -388,7 +381,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnParams p) {
         tile_dma(rsq, lds + stage * STAGE_BYTES, io.src_off, wave, q_base + t * 64 * ldq * 2);
         tile_dma(rso, lds + stage * STAGE_BYTES + TILE_BYTES, io_o.src_off, wave, g_base + t * 64 * ldo * 2);
     };
-    f32x16 dk[2], dv[2];
+    sis_f32x16 dk[2], dv[2];
 #pragma unroll
     for (int i = 0; i < 16; ++i) { dk[0][i] = 0.f; dk[1][i] = 0.f; dv[0][i] = 0.f; dv[1][i] = 0.f; }
 
@@ -402,7 +395,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnParams p) {
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
             // accumulators start at the row constants: -lse / scale and -delta of the query each register row belongs to
-            f32x16 s, dp;
+            sis_f32x16 s, dp;
             const int qrow = t * 64 + 32 * qb + 4 * h;   // register i: query qrow + (i & 3) + 8 * (i >> 2)
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
@@ -420,7 +413,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnParams p) {
                 s[4 * g4] = -l4.x * inv_scale; s[4 * g4 + 1] = -l4.y * inv_scale; s[4 * g4 + 2] = -l4.z * inv_scale; s[4 * g4 + 3] = -l4.w * inv_scale;
                 dp[4 * g4] = -d4.x; dp[4 * g4 + 1] = -d4.y; dp[4 * g4 + 2] = -d4.z; dp[4 * g4 + 3] = -d4.w;
             }
-            bf16x8 qfr[4], gfr[4];   // all eight row fragments of this query block before its first MFMA
+            sis_bf16x8 qfr[4], gfr[4];   // all eight row fragments of this query block before its first MFMA
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) { qfr[ks] = row_frag(qt, io, qb, ks); gfr[ks] = row_frag(gt, io, qb, ks); }
             __builtin_amdgcn_sched_barrier(0);
@@ -428,14 +421,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnParams p) {
             for (int ks = 0; ks < 4; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qfr[ks], kf[ks], s, 0, 0, 0);
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gfr[ks], vf[ks], dp, 0, 0, 0);
-            bf16x8 gtr[2][2], qtr[2][2];   // the transposed fragments of the two gradient products: requested before the
+            sis_bf16x8 gtr[2][2], qtr[2][2];   // the transposed fragments of the two gradient products: requested before the
 #pragma unroll                                // exponentials, which do not need them
             for (int db = 0; db < 2; ++db)
 #pragma unroll
                 for (int sx = 0; sx < 2; ++sx) { gtr[db][sx] = tr_frag(gt, io, db, 2 * qb + sx); qtr[db][sx] = tr_frag(qt, io, db, 2 * qb + sx); }
             __builtin_amdgcn_sched_barrier(0);
             const bool partial = t * 64 + 64 > p.N;
-            bf16x8 pf[2], dsf[2];
+            sis_bf16x8 pf[2], dsf[2];
 #pragma unroll
             for (int sx = 0; sx < 2; ++sx) {
                 float e[8], f[8];
@@ -460,7 +453,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnParams p) {
         }
     }
     __builtin_amdgcn_s_barrier();
-    u16* gk = p.d_qkv + ((long long)b * p.N) * ldq + p.H * HD + hd * HD;
+    sis_u16* gk = p.d_qkv + ((long long)b * p.N) * ldq + p.H * HD + hd * HD;
     store_rows(lds + wave * 4096, dk, p.scale, gk, ldq, k0, p.N, lane);
     store_rows(lds + 16384 + wave * 4096, dv, 1.f, gk + p.H * HD, ldq, k0, p.N, lane);
 #endif
@@ -471,7 +464,7 @@ int attn_params(AttnParams& p, const void* qkv, int batch, int n, int heads, con
     const int64_t qe = (int64_t)batch * n * 3 * heads * HD;
     if (qe * 2 >= (1LL << 31)) return sis_fail("%s: the fused projection exceeds 2 GiB", who);
     if (((uintptr_t)qkv) & 15) return sis_fail("%s: pointers must be 16-byte aligned", who);
-    p.qkv = (const u16*)qkv; p.B = batch; p.N = n; p.H = heads; p.blocks = sis_cdiv(n, 128);
+    p.qkv = (const sis_u16*)qkv; p.B = batch; p.N = n; p.H = heads; p.blocks = sis_cdiv(n, 128);
     p.qkv_bytes = (unsigned)(qe * 2); p.ctx_bytes = (unsigned)(qe * 2 / 3);
     p.scale = 0.125f;   // 1 / sqrt(64)
     p.ctx = p.d_ctx = nullptr; p.out_ctx = p.d_qkv = nullptr; p.lse = p.delta = nullptr;
@@ -493,7 +486,7 @@ extern "C" int sis_attention_fwd(void* ctx, float* lse, const void* qkv, int bat
     AttnParams p;
     if (int rc = attn_params(p, qkv, batch, n, heads, "sis_attention_fwd")) return rc;
     SIS_REQUIRE(ctx && lse, "sis_attention_fwd: null pointer");
-    p.out_ctx = (u16*)ctx; p.lse = lse;
+    p.out_ctx = (sis_u16*)ctx; p.lse = lse;
     return attn_launch(attn_fwd_kernel, p, (hipStream_t)stream, "attn_fwd_kernel");
 }
 
@@ -503,7 +496,7 @@ extern "C" int sis_attention_bwd(void* d_qkv, float* delta, const void* d_ctx, c
     if (int rc = attn_params(p, qkv, batch, n, heads, "sis_attention_bwd")) return rc;
     SIS_REQUIRE(d_qkv && delta && d_ctx && ctx && lse, "sis_attention_bwd: null pointer");
     SIS_REQUIRE(((((uintptr_t)d_ctx) | ((uintptr_t)ctx) | ((uintptr_t)d_qkv)) & 15) == 0, "sis_attention_bwd: pointers must be 16-byte aligned");
-    p.d_qkv = (u16*)d_qkv; p.delta = delta; p.d_ctx = (const u16*)d_ctx; p.ctx = (const u16*)ctx; p.lse = const_cast<float*>(lse);
+    p.d_qkv = (sis_u16*)d_qkv; p.delta = delta; p.d_ctx = (const sis_u16*)d_ctx; p.ctx = (const sis_u16*)ctx; p.lse = const_cast<float*>(lse);
     if (int rc = attn_launch(attn_bwd_dq_kernel, p, (hipStream_t)stream, "attn_bwd_dq_kernel")) return rc;   // writes delta
     return attn_launch(attn_bwd_dkv_kernel, p, (hipStream_t)stream, "attn_bwd_dkv_kernel");
 }

@@ -19,27 +19,13 @@
 // (four 64-bit ballots per wave and float4 column: word (i / 64) * 4 + e, bit i % 64 for component e of float4 i), and both
 // backward passes then read 1/8 byte instead of 4 bytes per element for the gate: backward 4*(4 reads + 1 write) + 2/8.
 #include <cstdlib>
-#include "sis_common.h"
+#include "sis_device.h"
 
 namespace {
 
 constexpr int BN_SLICE = 16384;  // elements per (channel, slice) partial
 
 struct BnGeom { int B, C, HW, slices_per_plane_group, S; int64_t n; };
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wsum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // A channel's data = B planes of HW floats.  Slice s of channel c covers elements [s*BN_SLICE, (s+1)*BN_SLICE) of
 // the channel's B*HW logical elements (element e lives at plane e / HW, offset e % HW).  Lanes walk float4s; one
@@ -82,7 +68,7 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(float* __restrict__ parti
 #pragma unroll
     for (int k = 0; k < PER; ++k) sum += (v[k].x + v[k].y) + (v[k].z + v[k].w);
     const float cnt = (float)(hi - lo);
-    const float mean = block_sum(sum, red) / cnt;
+    const float mean = sis_block_sum4(sum, red) / cnt;
     float m2 = 0.f;
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
@@ -91,7 +77,7 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(float* __restrict__ parti
             m2 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
         }
     }
-    m2 = block_sum(m2, red);
+    m2 = sis_block_sum4(m2, red);
     if (threadIdx.x == 0) {
         float* o = partial + ((int64_t)c * S + s) * 3;
         o[0] = cnt; o[1] = mean; o[2] = m2;
@@ -202,8 +188,8 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(float* __restrict__ 
             s2 += (g.x * ((xv.x - mu) * is) + g.y * ((xv.y - mu) * is)) + (g.z * ((xv.z - mu) * is) + g.w * ((xv.w - mu) * is));
         }
     }
-    s1 = block_sum(s1, red);
-    s2 = block_sum(s2, red);
+    s1 = sis_block_sum4(s1, red);
+    s2 = sis_block_sum4(s2, red);
     if (threadIdx.x == 0) { partial[((int64_t)c * S + s) * 2] = s1; partial[((int64_t)c * S + s) * 2 + 1] = s2; }
 }
 
@@ -287,7 +273,7 @@ __global__ __launch_bounds__(256) void bn_fused_fwd_kernel(float* __restrict__ y
 #pragma unroll
     for (int k = 0; k < PER; ++k) sum += (v[k].x + v[k].y) + (v[k].z + v[k].w);
     const float cnt = (float)n;
-    const float mean = block_sum(sum, red) / cnt;
+    const float mean = sis_block_sum4(sum, red) / cnt;
     float m2 = 0.f;
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
@@ -296,7 +282,7 @@ __global__ __launch_bounds__(256) void bn_fused_fwd_kernel(float* __restrict__ y
             m2 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
         }
     }
-    m2 = block_sum(m2, red);
+    m2 = sis_block_sum4(m2, red);
     const float var = m2 / cnt;
     const float is = rsqrtf(var + eps);
     if (threadIdx.x == 0) {
@@ -371,8 +357,8 @@ __global__ __launch_bounds__(256) void bn_fused_bwd_kernel(float* __restrict__ d
         s1 += (g[k].x + g[k].y) + (g[k].z + g[k].w);
         s2 += (g[k].x * ((xv[k].x - mu) * is) + g[k].y * ((xv[k].y - mu) * is)) + (g[k].z * ((xv[k].z - mu) * is) + g[k].w * ((xv[k].w - mu) * is));
     }
-    s1 = block_sum(s1, red);
-    s2 = block_sum(s2, red);
+    s1 = sis_block_sum4(s1, red);
+    s2 = sis_block_sum4(s2, red);
     if (threadIdx.x == 0) { dbeta[c] = s1; dgamma[c] = s2; }
     const float inv_n = 1.f / (float)n;
     const float kk = (gamma ? gamma[c] : 1.f) * is;
@@ -415,18 +401,6 @@ struct ChanWalkWide {   // ChanWalk with a step of 4 * THREADS elements
     }
 };
 
-template <int THREADS = BN_WIDE_THREADS>
-__device__ __forceinline__ float block_sum_wide(float v, float* red) {   // THREADS / 64 waves, fixed order
-    v = wsum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = 0.f;
-#pragma unroll
-    for (int w = 0; w < THREADS / 64; ++w) s += red[w];
-    return s;
-}
-
 template <bool RELU, bool RES>
 __global__ __launch_bounds__(BN_WIDE_THREADS) void bn_wide_fwd_kernel(float* __restrict__ y, float* __restrict__ mean_out,
                                                                      float* __restrict__ invstd_out, float* __restrict__ running_mean,
@@ -449,7 +423,7 @@ __global__ __launch_bounds__(BN_WIDE_THREADS) void bn_wide_fwd_kernel(float* __r
 #pragma unroll
     for (int k = 0; k < BN_WIDE_PER; ++k) sum += (v[k].x + v[k].y) + (v[k].z + v[k].w);
     const float cnt = (float)n;
-    const float mean = block_sum_wide(sum, red) / cnt;
+    const float mean = sis_block_sum_waves<BN_WIDE_THREADS / 64>(sum, red) / cnt;
     float m2 = 0.f;
 #pragma unroll
     for (int k = 0; k < BN_WIDE_PER; ++k) {
@@ -458,7 +432,7 @@ __global__ __launch_bounds__(BN_WIDE_THREADS) void bn_wide_fwd_kernel(float* __r
             m2 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
         }
     }
-    m2 = block_sum_wide(m2, red);
+    m2 = sis_block_sum_waves<BN_WIDE_THREADS / 64>(m2, red);
     const float var = m2 / cnt;
     const float is = rsqrtf(var + eps);
     if (threadIdx.x == 0) {
@@ -536,8 +510,8 @@ __global__ __launch_bounds__(THREADS) void bn_wide_bwd_kernel(float* __restrict_
             w.next();
         }
     }
-    s1 = block_sum_wide<THREADS>(s1, red);
-    s2 = block_sum_wide<THREADS>(s2, red);
+    s1 = sis_block_sum_waves<THREADS / 64>(s1, red);
+    s2 = sis_block_sum_waves<THREADS / 64>(s2, red);
     if (threadIdx.x == 0) { dbeta[c] = s1; dgamma[c] = s2; }
     const float inv_n = 1.f / (float)n;
     const float kk = (gamma ? gamma[c] : 1.f) * is;

@@ -4,25 +4,11 @@
 // per row), the 4 waves take rows r, r+4, ...; the four per-wave sums are combined through LDS and written as one partial
 // row per slice.  Stage 2 adds the slices in fixed order (deterministic, no atomics).  ATen's generic reduction moves
 // ~2 TB/s on these shapes ([8192][768..3072] bf16) and rounds the result to bf16 first.
-#include "sis_common.h"
+#include "sis_device.h"
 
 namespace {
 
 constexpr int CS_COLS = 256;  // columns per workgroup (64 lanes x 4)
-
-template <typename T>
-__device__ __forceinline__ void cs_load4(const T* p, float* v) {
-    if constexpr (sizeof(T) == 4) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-        const uint2 q = *reinterpret_cast<const uint2*>(p);
-        T t[4];
-        __builtin_memcpy(t, &q, 8);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = sis_ld(t, e);
-    }
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void column_sum_partial_kernel(float* __restrict__ part, const T* __restrict__ x, int rows,
@@ -36,14 +22,14 @@ __global__ __launch_bounds__(256) void column_sum_partial_kernel(float* __restri
         int r = r_lo + wave;
         for (; r + 4 < r_hi; r += 8) {  // two independent loads in flight
             float a[4], b[4];
-            cs_load4(x + (int64_t)r * n + c, a);
-            cs_load4(x + (int64_t)(r + 4) * n + c, b);
+            sis_load4(x + (int64_t)r * n + c, a);
+            sis_load4(x + (int64_t)(r + 4) * n + c, b);
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc[e] += a[e] + b[e];
         }
         for (; r < r_hi; r += 4) {
             float a[4];
-            cs_load4(x + (int64_t)r * n + c, a);
+            sis_load4(x + (int64_t)r * n + c, a);
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc[e] += a[e];
         }

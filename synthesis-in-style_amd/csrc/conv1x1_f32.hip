@@ -13,14 +13,13 @@
 // 32-channel chunks, double-buffered, ONE barrier per 64 MFMAs per wave.
 #include <cstdlib>
 #include <type_traits>
-#include "sis_common.h"
+#include "sis_device.h"
 
 namespace {
 
 #ifndef PW_OCC
 #define PW_OCC 4  // waves per SIMD the register allocation aims at (2 workgroups per CU).  6 (three per CU, 80 VGPRs) measured 527 against 541 images/s on EMANet.
 #endif
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 template <int MT_, int NPIX_, int KC_>
 struct PwCfg {
@@ -45,11 +44,6 @@ struct PwParams {
     const float* accum; // [N][Mtot][HW] added to the result (data gradient + the skip connection's gradient) or null
     int N, K, M, HW, px_tiles;
 };
-
-__device__ __forceinline__ void glds16(const float* g, float* l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
 
 template <typename C, bool A_KMAJOR, bool HAS_BIAS, bool HAS_ACC = false>
 __global__ __launch_bounds__(512, C::OCC) void conv1x1_f32_kernel(PwParams p) {
@@ -78,7 +72,7 @@ __global__ __launch_bounds__(512, C::OCC) void conv1x1_f32_kernel(PwParams p) {
             const int e = piece * 256 + lane * 4;          // float index inside the [KC][NPIX] chunk
             const int row = e / C::NPIX, col = e % C::NPIX;
             if (p0 + col + 3 < p.HW)
-                glds16(xin + (int64_t)(chunk * C::KC + row) * p.HW + p0 + col, dst + piece * 256);
+                sis_global_load_lds16(xin + (int64_t)(chunk * C::KC + row) * p.HW + p0 + col, dst + piece * 256);
         }
     };
     auto dma_a = [&](int chunk, int stage) {  // k-major source: rows of Mtot floats
@@ -87,7 +81,7 @@ __global__ __launch_bounds__(512, C::OCC) void conv1x1_f32_kernel(PwParams p) {
             const int e = piece * 256 + lane * 4;
             const int row = e / C::MT, col = e % C::MT;
             if (m0 + col + 3 < p.M)
-                glds16(p.a + (int64_t)(chunk * C::KC + row) * p.M + m0 + col, dst + piece * 256);
+                sis_global_load_lds16(p.a + (int64_t)(chunk * C::KC + row) * p.M + m0 + col, dst + piece * 256);
         }
     };
     auto load_a = [&](int chunk) {  // m-major source: thread -> (m = e % MT, k quad = e / MT)
@@ -114,7 +108,7 @@ __global__ __launch_bounds__(512, C::OCC) void conv1x1_f32_kernel(PwParams p) {
         }
     };
 
-    f32x16 acc[C::MB][C::NB];
+    sis_f32x16 acc[C::MB][C::NB];
 #pragma unroll
     for (int mb = 0; mb < C::MB; ++mb)
 #pragma unroll

@@ -13,12 +13,9 @@
 // operand read is shared by them); split-K over the pixel stream writes slabs that an ordered pass adds (deterministic,
 // no atomics).
 #include <cstdlib>
-#include "sis_common.h"
+#include "sis_device.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int PK = 64;  // pixels per chunk (one 256-byte row piece per channel)
 
@@ -32,13 +29,6 @@ struct PwgParams {
     int jobs;             // > 0: grid.z layers of this shape: gy / x / out from the tables (out of layer z: its dW or its first slab)
     const float* gyj[PWG_JOBS_MAX]; const float* xj[PWG_JOBS_MAX]; float* outj[PWG_JOBS_MAX];
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t pwg_rsrc(const float* base) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0x7FFFFFFF, 0x00020000);
-}
-__device__ __forceinline__ void pwg_dma(__amdgpu_buffer_rsrc_t r, float* l, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)l, 16, voff, soff, 0, 0);
-}
 
 // WM x WN waves of MB stacked 32 x 32 tiles each: TM = 32 WM MB output channels, TN = 32 WN input channels
 template <int WM, int WN, int MB>
@@ -64,16 +54,16 @@ __global__ __launch_bounds__(512, 2) void conv1x1_wgrad_f32_kernel(const PwgPara
         const int row = 4 * v + (lane >> 4);
         voff[v] = (unsigned)(row * p.HW) * 4u + (unsigned)(((lane & 15) ^ (row & 15)) * 16);
     }
-    const __amdgpu_buffer_rsrc_t a_rsrc = pwg_rsrc(p.jobs ? p.gyj[blockIdx.z] : p.gy), b_rsrc = pwg_rsrc(p.jobs ? p.xj[blockIdx.z] : p.x);
+    const __amdgpu_buffer_rsrc_t a_rsrc = sis_buffer_rsrc(p.jobs ? p.gyj[blockIdx.z] : p.gy), b_rsrc = sis_buffer_rsrc(p.jobs ? p.xj[blockIdx.z] : p.x);
     auto stage = [&](int chunk, int buf) {
         const int b = chunk / blocks_per_sample, p0 = (chunk - b * blocks_per_sample) * PK;
         float* al = lds + buf * STAGE;
         float* bl = al + A_FLOATS;
         // rows of a piece group of 16 (= 4 pieces) are 16 * HW floats apart
         for (int q = wave; q < A_PIECES; q += 8)
-            pwg_dma(a_rsrc, al + q * 256, voff[q & 3], (unsigned)(((int64_t)(b * p.Cout + co0 + 16 * (q >> 2)) * p.HW + p0) * 4));
+            sis_buffer_load_lds16(a_rsrc, al + q * 256, voff[q & 3], (unsigned)(((int64_t)(b * p.Cout + co0 + 16 * (q >> 2)) * p.HW + p0) * 4));
         for (int q = wave; q < B_PIECES; q += 8)
-            pwg_dma(b_rsrc, bl + q * 256, voff[q & 3], (unsigned)(((int64_t)(b * p.Cin + ci0 + 16 * (q >> 2)) * p.HW + p0) * 4));
+            sis_buffer_load_lds16(b_rsrc, bl + q * 256, voff[q & 3], (unsigned)(((int64_t)(b * p.Cin + ci0 + 16 * (q >> 2)) * p.HW + p0) * 4));
     };
 
     // operand reads: row = tile row of this lane, 16-byte unit (2 j + half) ^ (row & 15), j = 0..7
@@ -87,7 +77,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_wgrad_f32_kernel(const PwgPara
     const int brow = wn * 32 + l31;
     const int b_base = A_FLOATS + brow * PK + (((half ^ brow) & 1) * 4), b_hi = brow & 14;
 
-    f32x16 acc[MB];
+    sis_f32x16 acc[MB];
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
@@ -100,11 +90,11 @@ __global__ __launch_bounds__(512, 2) void conv1x1_wgrad_f32_kernel(const PwgPara
     // sits in front of its LAST step's MFMAs -- that step's quads are in registers by then, nobody reads this buffer any more --
     // and the first quads of chunk + 1 are requested right behind it, under those MFMAs, instead of in front of the next chunk's
     // first MFMA (one workgroup per CU: nothing else covers that LDS round trip, which all eight waves start at once).
-    f32x4 bq[2], aq[2][MB];
+    sis_f32x4 bq[2], aq[2][MB];
     auto quads = [&](const float* st, int j, int set) {
-        bq[set] = *reinterpret_cast<const f32x4*>(st + b_base + ((2 * j) ^ b_hi) * 4);
+        bq[set] = *reinterpret_cast<const sis_f32x4*>(st + b_base + ((2 * j) ^ b_hi) * 4);
 #pragma unroll
-        for (int mb = 0; mb < MB; ++mb) aq[set][mb] = *reinterpret_cast<const f32x4*>(st + a_base[mb] + ((2 * j) ^ a_hi[mb]) * 4);
+        for (int mb = 0; mb < MB; ++mb) aq[set][mb] = *reinterpret_cast<const sis_f32x4*>(st + a_base[mb] + ((2 * j) ^ a_hi[mb]) * 4);
     };
     quads(lds, 0, 0);
     int buf = 0;

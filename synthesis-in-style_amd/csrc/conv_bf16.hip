@@ -24,13 +24,9 @@
 // stride-2 layers read their B fragments at a pixel stride of two units.
 #include <algorithm>
 #include <type_traits>
-#include "sis_common.h"
+#include "sis_device.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef unsigned short u16;
 
 template <int MT_, int NPIX_, int KC_, int KH_, int S_, int TW_>
 struct ConvCfg {
@@ -65,10 +61,10 @@ __host__ __device__ __forceinline__ int swz(int unit, int row, int units) {
 }
 
 struct ConvParams {
-    const u16* x;        // [N, Cin, H, W] bf16
-    const u16* wp;       // packed weights
+    const sis_u16* x;        // [N, Cin, H, W] bf16
+    const sis_u16* wp;       // packed weights
     const float* bias;   // [Cout] or null
-    u16* y;              // [N, Cout, Ho, Wo] bf16
+    sis_u16* y;              // [N, Cout, Ho, Wo] bf16
     int N, Cin, Cout, H, W, Ho, Wo;
     int tiles_x, tiles_y, co_tiles;
     int aligned;         // rows / planes / tile origins 8-byte aligned and no partially valid 4-pixel group
@@ -78,9 +74,9 @@ struct ConvParams {
 // w: [Mrole... see sis_conv_bf16_pack.  One thread per packed element.
 // (`out2` / `total2`: the adjoint packing of the same weight written by the same launch, MT2 = its M tile)
 template <typename T>
-__global__ __launch_bounds__(256) void conv_pack_kernel(u16* __restrict__ out, const T* __restrict__ w, int Cout, int Cin,
+__global__ __launch_bounds__(256) void conv_pack_kernel(sis_u16* __restrict__ out, const T* __restrict__ w, int Cout, int Cin,
                                                         int KH, int MT, int KC, int adjoint, int64_t total,
-                                                        u16* __restrict__ out2, int MT2, int64_t total2) {
+                                                        sis_u16* __restrict__ out2, int MT2, int64_t total2) {
     int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= total + total2) return;
     if (e >= total) { e -= total; out = out2; MT = MT2; adjoint = 1; }
@@ -103,7 +99,7 @@ __global__ __launch_bounds__(256) void conv_pack_kernel(u16* __restrict__ out, c
         else v = (float)w[(((int64_t)k * Cin + m) * KH + (KH - 1 - ky)) * KH + (KH - 1 - kx)];
     }
     __hip_bfloat16 b = __float2bfloat16(v);
-    out[e] = *reinterpret_cast<u16*>(&b);
+    out[e] = *reinterpret_cast<sis_u16*>(&b);
 }
 
 // Weight standardisation of ALL the StdConv2d layers of a network and the packing of the results in ONE launch
@@ -123,10 +119,10 @@ __global__ __launch_bounds__(256) void weight_std_pack_multi_kernel(const long l
     while (layer + 1 < n_layers && (int)blockIdx.x >= (int)table[(layer + 1) * WSP_FIELDS + 12]) ++layer;
     const long long* d = table + (int64_t)layer * WSP_FIELDS;
     const float* w = reinterpret_cast<const float*>(d[0]);
-    u16* what = reinterpret_cast<u16*>(d[1]);
+    sis_u16* what = reinterpret_cast<sis_u16*>(d[1]);
     float* invstd = reinterpret_cast<float*>(d[2]);
-    u16* packed = reinterpret_cast<u16*>(d[3]);
-    u16* adj = reinterpret_cast<u16*>(d[4]);
+    sis_u16* packed = reinterpret_cast<sis_u16*>(d[3]);
+    sis_u16* adj = reinterpret_cast<sis_u16*>(d[4]);
     const int Cout = (int)d[5], Cin = (int)d[6], KH = (int)d[7], MT = (int)d[8], KC = (int)d[9], MT2 = (int)d[10];
     const int co = (int)blockIdx.x - (int)d[12];
     const int taps = KH * KH, n = Cin * taps, units = KC / 8;
@@ -147,7 +143,7 @@ __global__ __launch_bounds__(256) void weight_std_pack_multi_kernel(const long l
         float s = 0.f;
         for (int i = threadIdx.x; i < n; i += 256) s += src[i];
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);   // written out: a call of sis_wave_sum here changes the generated code
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
         __syncthreads();
         mean = ((red[0] + red[1]) + (red[2] + red[3])) / (float)n;
@@ -155,7 +151,7 @@ __global__ __launch_bounds__(256) void weight_std_pack_multi_kernel(const long l
         float m2 = 0.f;
         for (int i = threadIdx.x; i < n; i += 256) { const float dd = src[i] - mean; m2 += dd * dd; }
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m2 += __shfl_xor(m2, o, 64);
+        for (int o = 32; o > 0; o >>= 1) m2 += __shfl_xor(m2, o, 64);   // written out: a call of sis_wave_sum here changes the generated code
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m2;
         __syncthreads();
         const float var = ((red[0] + red[1]) + (red[2] + red[3])) / (float)n;
@@ -166,7 +162,7 @@ __global__ __launch_bounds__(256) void weight_std_pack_multi_kernel(const long l
     const int nchunks2 = MT2 ? Cout / KC : 0, chunk2 = co / KC, unit2 = (co % KC) >> 3, j2 = co & 7;
     for (int i = threadIdx.x; i < n; i += 256) {
         __hip_bfloat16 b = __float2bfloat16(plain ? src[i] : (src[i] - mean) / sd);
-        const u16 v = *reinterpret_cast<u16*>(&b);
+        const sis_u16 v = *reinterpret_cast<sis_u16*>(&b);
         if (!plain) what[(int64_t)co * n + i] = v;
         const int ci = i / taps, tap = i - ci * taps;
         packed[fwd_pos(ci, tap)] = v;
@@ -190,40 +186,32 @@ __global__ __launch_bounds__(256) void weight_std_pack_multi_kernel(const long l
 // (as weight_std_bwd_kernel, w_hat recomputed from the fp32 master weight).  The gradient / result pointers change from step
 // to step, so they travel as kernel arguments (<= 64 layers per launch); everything static comes from the forward's table.
 constexpr int WSB_MAX = 64;
-struct WsBwdPtrs { const u16* g[WSB_MAX]; float* dw[WSB_MAX]; };
+struct WsBwdPtrs { const sis_u16* g[WSB_MAX]; float* dw[WSB_MAX]; };
 
 __global__ __launch_bounds__(256) void weight_std_bwd_multi_kernel(const long long* __restrict__ table, int layer0, int n_layers, WsBwdPtrs ptrs) {
     __shared__ float red[4];
-    auto block_sum = [&](float v) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-        __syncthreads();
-        return (red[0] + red[1]) + (red[2] + red[3]);
-    };
     const int base = (int)table[(int64_t)layer0 * WSP_FIELDS + 13];
     int layer = layer0;
     while (layer + 1 < layer0 + n_layers && (int)blockIdx.x + base >= (int)table[(int64_t)(layer + 1) * WSP_FIELDS + 13]) ++layer;
     const long long* d = table + (int64_t)layer * WSP_FIELDS;
-    const u16* g = ptrs.g[layer - layer0];
+    const sis_u16* g = ptrs.g[layer - layer0];
     float* dw = ptrs.dw[layer - layer0];
     if (!g) return;
     const int co = (int)blockIdx.x + base - (int)d[13];
     const int n = (int)d[6] * (int)d[7] * (int)d[7];
     const float* row = reinterpret_cast<const float*>(d[0]) + (int64_t)co * n;
-    const u16* grow = g + (int64_t)co * n;
+    const sis_u16* grow = g + (int64_t)co * n;
     float s = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) s += row[i];
-    const float mean = block_sum(s) / (float)n;
+    const float mean = sis_block_sum4(s, red) / (float)n;
     const float is = reinterpret_cast<const float*>(d[2])[co];
     float sg = 0.f, sgw = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) {
         const float gi = __builtin_bit_cast(float, (unsigned)grow[i] << 16), wh = (row[i] - mean) * is;
         sg += gi; sgw += gi * wh;
     }
-    const float mg = block_sum(sg) / (float)n;
-    const float mgw = block_sum(sgw) / (float)n;
+    const float mg = sis_block_sum4(sg, red) / (float)n;
+    const float mgw = sis_block_sum4(sgw, red) / (float)n;
     float* o = dw + (int64_t)co * n;
     for (int i = threadIdx.x; i < n; i += 256) {
         const float gi = __builtin_bit_cast(float, (unsigned)grow[i] << 16), wh = (row[i] - mean) * is;
@@ -253,8 +241,8 @@ __global__ __launch_bounds__(512, 2) void conv_bf16_kernel(ConvParams p) {
     const int ix0 = ox0 * C::S - C::HALO, iy0 = oy0 * C::S - C::PAD;
     const int nchunks = p.Cin / C::KC;
 
-    const u16* xin = p.x + (int64_t)n * p.Cin * p.H * p.W;
-    const u16* wsrc = p.wp + (int64_t)co_t * nchunks * (C::WBYTES / 2);
+    const sis_u16* xin = p.x + (int64_t)n * p.Cin * p.H * p.W;
+    const sis_u16* wsrc = p.wp + (int64_t)co_t * nchunks * (C::WBYTES / 2);
 
     // ---- staging tasks of this thread (fixed over the chunk loop): 8 channels x 4 pixels each
     int task_goff[C::NT];   // element offset of (channel 0 of the chunk's plane, row, first pixel) inside the image, or -1
@@ -283,12 +271,12 @@ __global__ __launch_bounds__(512, 2) void conv_bf16_kernel(ConvParams p) {
     uint2 xr[C::NT][8];  // staged pixels: [task][channel] = 4 bf16
 
     auto load_x = [&](int chunk) {
-        const u16* base = xin + (int64_t)chunk * C::KC * p.H * p.W;
+        const sis_u16* base = xin + (int64_t)chunk * C::KC * p.H * p.W;
         const int plane = p.H * p.W;
 #pragma unroll
         for (int i = 0; i < C::NT; ++i) {
             if (task_goff[i] >= 0) {
-                const u16* g = base + task_goff[i];
+                const sis_u16* g = base + task_goff[i];
                 if constexpr (ALIGNED) {
 #pragma unroll
                     for (int c = 0; c < 8; ++c) xr[i][c] = *reinterpret_cast<const uint2*>(g + (int64_t)c * plane);
@@ -299,7 +287,7 @@ __global__ __launch_bounds__(512, 2) void conv_bf16_kernel(ConvParams p) {
                         // from the address rounded down to 4 bytes, funnel-shifted by 16 bits when it was odd.
 #pragma unroll
                         for (int c = 0; c < 8; ++c) {
-                            const u16* gc = g + (int64_t)c * plane;
+                            const sis_u16* gc = g + (int64_t)c * plane;
                             const bool odd = (reinterpret_cast<uintptr_t>(gc) & 2) != 0;
                             const unsigned* d = reinterpret_cast<const unsigned*>(gc - (odd ? 1 : 0));
                             const unsigned d0 = d[0], d1 = d[1], d2 = d[2];
@@ -309,7 +297,7 @@ __global__ __launch_bounds__(512, 2) void conv_bf16_kernel(ConvParams p) {
                     } else {  // ragged group at a row end: element by element
 #pragma unroll
                         for (int c = 0; c < 8; ++c) {
-                            const u16* gc = g + (int64_t)c * plane;
+                            const sis_u16* gc = g + (int64_t)c * plane;
                             const unsigned e0 = (mask & 1) ? gc[0] : 0, e1 = (mask & 2) ? gc[1] : 0;
                             const unsigned e2 = (mask & 4) ? gc[2] : 0, e3 = (mask & 8) ? gc[3] : 0;
                             xr[i][c] = make_uint2(e0 | (e1 << 16), e2 | (e3 << 16));
@@ -353,8 +341,7 @@ __global__ __launch_bounds__(512, 2) void conv_bf16_kernel(ConvParams p) {
         const unsigned char* src = reinterpret_cast<const unsigned char*>(wsrc) + (int64_t)chunk * C::WBYTES;
         unsigned char* dst = lds + stage * C::STAGE;
         for (int piece = wave; piece < C::WDMA; piece += 8)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + piece * 1024 + lane * 16),
-                                             (__attribute__((address_space(3))) void*)(dst + piece * 1024), 16, 0, 0);
+            sis_global_load_lds16(src + piece * 1024 + lane * 16, dst + piece * 1024);
     };
 
     // ---- fragment addresses
@@ -375,7 +362,7 @@ __global__ __launch_bounds__(512, 2) void conv_bf16_kernel(ConvParams p) {
         b_off[nb] = C::WBYTES + (((h * C::RI) + ty * C::S) * C::LW + (tx + r) * C::S + C::HALO - C::PAD) * 16;
     }
 
-    f32x16 acc[C::MB][C::NB];
+    sis_f32x16 acc[C::MB][C::NB];
 #pragma unroll
     for (int mb = 0; mb < C::MB; ++mb)
 #pragma unroll
@@ -402,13 +389,13 @@ __global__ __launch_bounds__(512, 2) void conv_bf16_kernel(ConvParams p) {
             const int ky = tap / C::KW, kx = tap % C::KW;
 #pragma unroll
             for (int ks = 0; ks < C::KC / 16; ++ks) {
-                bf16x8 a[C::MB], b[C::NB];
+                sis_bf16x8 a[C::MB], b[C::NB];
 #pragma unroll
                 for (int mb = 0; mb < C::MB; ++mb)
-                    a[mb] = *reinterpret_cast<const bf16x8*>(st + tap * (C::MT * C::KC * 2) + a_off[mb][ks]);
+                    a[mb] = *reinterpret_cast<const sis_bf16x8*>(st + tap * (C::MT * C::KC * 2) + a_off[mb][ks]);
 #pragma unroll
                 for (int nb = 0; nb < C::NB; ++nb)
-                    b[nb] = *reinterpret_cast<const bf16x8*>(st + b_off[nb] + (ks * 2 * C::RI * C::LW + ky * C::LW + kx) * 16);
+                    b[nb] = *reinterpret_cast<const sis_bf16x8*>(st + b_off[nb] + (ks * 2 * C::RI * C::LW + ky * C::LW + kx) * 16);
 #pragma unroll
                 for (int mb = 0; mb < C::MB; ++mb)
 #pragma unroll
@@ -441,13 +428,13 @@ __global__ __launch_bounds__(512, 2) void conv_bf16_kernel(ConvParams p) {
                 const int blk = wn * C::NB + nb;
                 const int oy = oy0 + blk / (C::TW / 32), ox = ox0 + (blk % (C::TW / 32)) * 32 + r;
                 if (oy >= p.Ho || ox >= p.Wo) continue;
-                u16* yb = p.y + ((int64_t)n * p.Cout + co0) * plane + oy * p.Wo + ox;
+                sis_u16* yb = p.y + ((int64_t)n * p.Cout + co0) * plane + oy * p.Wo + ox;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
                     const int ro = (i & 3) + 8 * (i >> 2);
                     if (!decltype(checked)::value || co0 + ro < p.Cout) {
                         __hip_bfloat16 bvv = __float2bfloat16(acc[mb][nb][i] + bv[i]);
-                        yb[ro * plane] = *reinterpret_cast<u16*>(&bvv);
+                        yb[ro * plane] = *reinterpret_cast<sis_u16*>(&bvv);
                     }
                 }
             }
@@ -532,11 +519,11 @@ extern "C" int sis_conv_bf16_pack(void* packed, const void* weight, int weight_d
     hipStream_t st = (hipStream_t)stream;
     const int blocks = sis_cdiv(total, 256);
     if (weight_dtype == SIS_F32)
-        hipLaunchKernelGGL(conv_pack_kernel<float>, dim3(blocks), dim3(256), 0, st, (u16*)packed, (const float*)weight, cout, cin,
-                           ksize, pl.mt, pl.kc, adjoint, total, (u16*)nullptr, 0, (int64_t)0);
+        hipLaunchKernelGGL(conv_pack_kernel<float>, dim3(blocks), dim3(256), 0, st, (sis_u16*)packed, (const float*)weight, cout, cin,
+                           ksize, pl.mt, pl.kc, adjoint, total, (sis_u16*)nullptr, 0, (int64_t)0);
     else if (weight_dtype == SIS_BF16)
-        hipLaunchKernelGGL(conv_pack_kernel<__hip_bfloat16>, dim3(blocks), dim3(256), 0, st, (u16*)packed,
-                           (const __hip_bfloat16*)weight, cout, cin, ksize, pl.mt, pl.kc, adjoint, total, (u16*)nullptr, 0, (int64_t)0);
+        hipLaunchKernelGGL(conv_pack_kernel<__hip_bfloat16>, dim3(blocks), dim3(256), 0, st, (sis_u16*)packed,
+                           (const __hip_bfloat16*)weight, cout, cin, ksize, pl.mt, pl.kc, adjoint, total, (sis_u16*)nullptr, 0, (int64_t)0);
     else
         return sis_fail("sis_conv_bf16_pack: weights must be float32 or bfloat16");
     SIS_CHECK_LAUNCH("conv_pack_kernel");
@@ -554,11 +541,11 @@ extern "C" int sis_conv_bf16_pack_both(void* packed, void* packed_adjoint, const
     hipStream_t st = (hipStream_t)stream;
     const int blocks = sis_cdiv(total + total2, 256);
     if (weight_dtype == SIS_F32)
-        hipLaunchKernelGGL(conv_pack_kernel<float>, dim3(blocks), dim3(256), 0, st, (u16*)packed, (const float*)weight, cout, cin,
-                           ksize, pf.mt, pf.kc, 0, total, (u16*)packed_adjoint, pa.mt, total2);
+        hipLaunchKernelGGL(conv_pack_kernel<float>, dim3(blocks), dim3(256), 0, st, (sis_u16*)packed, (const float*)weight, cout, cin,
+                           ksize, pf.mt, pf.kc, 0, total, (sis_u16*)packed_adjoint, pa.mt, total2);
     else if (weight_dtype == SIS_BF16)
-        hipLaunchKernelGGL(conv_pack_kernel<__hip_bfloat16>, dim3(blocks), dim3(256), 0, st, (u16*)packed,
-                           (const __hip_bfloat16*)weight, cout, cin, ksize, pf.mt, pf.kc, 0, total, (u16*)packed_adjoint, pa.mt, total2);
+        hipLaunchKernelGGL(conv_pack_kernel<__hip_bfloat16>, dim3(blocks), dim3(256), 0, st, (sis_u16*)packed,
+                           (const __hip_bfloat16*)weight, cout, cin, ksize, pf.mt, pf.kc, 0, total, (sis_u16*)packed_adjoint, pa.mt, total2);
     else
         return sis_fail("sis_conv_bf16_pack_both: weights must be float32 or bfloat16");
     SIS_CHECK_LAUNCH("conv_pack_kernel");
@@ -573,7 +560,7 @@ extern "C" int sis_conv_bf16(void* y, const void* x, const void* packed, const f
     SIS_REQUIRE(conv_plan(batch, cin, cout, h, w, ksize, stride, &pl), "sis_conv_bf16: unsupported layer %d->%d k%d s%d", cin, cout, ksize, stride);
     const int pad = ksize / 2;
     ConvParams p;
-    p.x = (const u16*)x; p.wp = (const u16*)packed; p.bias = bias; p.y = (u16*)y;
+    p.x = (const sis_u16*)x; p.wp = (const sis_u16*)packed; p.bias = bias; p.y = (sis_u16*)y;
     p.N = batch; p.Cin = cin; p.Cout = cout;
     p.Ho = (h + 2 * pad - ksize) / stride + 1; p.Wo = (w + 2 * pad - ksize) / stride + 1;
     p.H = h; p.W = w;
@@ -637,7 +624,7 @@ extern "C" int sis_weight_std_bwd_multi(const void* table, const void* const* gr
         WsBwdPtrs ptrs;
         int rows = 0;
         for (int i = 0; i < WSB_MAX; ++i) {
-            ptrs.g[i] = i < nl ? (const u16*)grads[l0 + i] : nullptr;
+            ptrs.g[i] = i < nl ? (const sis_u16*)grads[l0 + i] : nullptr;
             ptrs.dw[i] = i < nl ? (float*)dw[l0 + i] : nullptr;
             SIS_REQUIRE(i >= nl || !ptrs.g[i] || ptrs.dw[i], "sis_weight_std_bwd_multi: layer %d has a gradient but no result", l0 + i);
             if (i < nl) rows += couts[l0 + i];

@@ -20,13 +20,9 @@
 // Split-K over (image, strip, row block): every unit writes its partial [tap][co][ci] tile to a slab; a second kernel
 // adds the slabs in unit order (deterministic, no atomics) and writes dW[co][ci][3][3].
 #include <algorithm>
-#include "sis_common.h"
+#include "sis_device.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef unsigned short u16;
 
 template <int WM_, int WN_, int KS_, int NWV_ = 8>
 struct WgCfg {
@@ -54,19 +50,19 @@ struct WgCfg {
 constexpr int WG_JOBS_MAX = 16;   // layers of one shape per launch (grid.z), operands through pointer tables
 
 struct WgParams {
-    const u16* x;    // [N, Cin, H, W]
-    const u16* gy;   // [N, Cout, H, W]
+    const sis_u16* x;    // [N, Cin, H, W]
+    const sis_u16* gy;   // [N, Cout, H, W]
     float* slab;     // [units][9][co_pad][ci_pad]
     int jobs;        // > 0: grid.z layers of this shape: x / gy from the tables, slab of layer z at slab + z * slab_job_stride
     long long slab_job_stride;
-    const u16* xj[WG_JOBS_MAX]; const u16* gyj[WG_JOBS_MAX];
+    const sis_u16* xj[WG_JOBS_MAX]; const sis_u16* gyj[WG_JOBS_MAX];
     int N, Cin, Cout, H, W;
     int strips, row_blocks, rows_per_block;
     int co_tiles, ci_tiles;
     int aligned;
 };
 
-__device__ __forceinline__ uint4 load_chunk(const u16* row, int x0, int W, bool row_ok, bool aligned) {
+__device__ __forceinline__ uint4 load_chunk(const sis_u16* row, int x0, int W, bool row_ok, bool aligned) {
     // 8 pixels [x0, x0 + 8) of a tensor row (zeros outside [0, W) or when the row itself is outside the image)
     uint4 v = make_uint4(0u, 0u, 0u, 0u);
     if (!row_ok) return v;
@@ -77,7 +73,7 @@ __device__ __forceinline__ uint4 load_chunk(const u16* row, int x0, int W, bool 
     if (x0 >= 0 && x0 + 8 <= W) {
         // whole group inside the row but on an arbitrary 2-byte boundary (127-wide maps): five dword loads from the address
         // rounded down to 4 bytes, funnel-shifted by 16 bits when it was odd
-        const u16* g = row + x0;
+        const sis_u16* g = row + x0;
         const bool odd = (reinterpret_cast<uintptr_t>(g) & 2) != 0;
         const unsigned* d = reinterpret_cast<const unsigned*>(g - (odd ? 1 : 0));
         const unsigned d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3], d4 = d[4];
@@ -92,14 +88,14 @@ __device__ __forceinline__ uint4 load_chunk(const u16* row, int x0, int W, bool 
 }
 
 // the three kx taps of one input row and one 16-pixel K-step: centre group as is, its two neighbours funnel-shifted in
-__device__ __forceinline__ void tap_row(f32x16 (&acc)[9], int ky, bf16x8 a, uint4 lft, uint4 c, uint4 rgt) {
+__device__ __forceinline__ void tap_row(sis_f32x16 (&acc)[9], int ky, sis_bf16x8 a, uint4 lft, uint4 c, uint4 rgt) {
     const unsigned t0 = __builtin_amdgcn_alignbit(c.x, lft.w, 16), t1 = __builtin_amdgcn_alignbit(c.y, c.x, 16);
     const unsigned t2 = __builtin_amdgcn_alignbit(c.z, c.y, 16), t3 = __builtin_amdgcn_alignbit(c.w, c.z, 16);
     const unsigned t4 = __builtin_amdgcn_alignbit(rgt.x, c.w, 16);
     const uint4 b0 = make_uint4(t0, t1, t2, t3), b2 = make_uint4(t1, t2, t3, t4);
-    acc[ky * 3 + 0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, b0), acc[ky * 3 + 0], 0, 0, 0);
-    acc[ky * 3 + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, c), acc[ky * 3 + 1], 0, 0, 0);
-    acc[ky * 3 + 2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, b2), acc[ky * 3 + 2], 0, 0, 0);
+    acc[ky * 3 + 0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(sis_bf16x8, b0), acc[ky * 3 + 0], 0, 0, 0);
+    acc[ky * 3 + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(sis_bf16x8, c), acc[ky * 3 + 1], 0, 0, 0);
+    acc[ky * 3 + 2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(sis_bf16x8, b2), acc[ky * 3 + 2], 0, 0, 0);
 }
 
 template <typename C, bool ALIGNED>
@@ -119,8 +115,8 @@ __global__ __launch_bounds__(C::THREADS, 2) void conv_wgrad_bf16_kernel(WgParams
     const int x0 = strip * C::SW;
     const int y_begin = rb * p.rows_per_block, y_end = min(p.H, y_begin + p.rows_per_block);
     const int64_t plane = (int64_t)p.H * p.W;
-    const u16* gy_base = (p.jobs ? p.gyj[blockIdx.z] : p.gy) + ((int64_t)n * p.Cout + co_t * C::MT) * plane;
-    const u16* x_base = (p.jobs ? p.xj[blockIdx.z] : p.x) + ((int64_t)n * p.Cin + ci_t * C::NT) * plane;
+    const sis_u16* gy_base = (p.jobs ? p.gyj[blockIdx.z] : p.gy) + ((int64_t)n * p.Cout + co_t * C::MT) * plane;
+    const sis_u16* x_base = (p.jobs ? p.xj[blockIdx.z] : p.x) + ((int64_t)n * p.Cin + ci_t * C::NT) * plane;
 
     uint4 dyr[C::NDY], xr[C::NX];
 
@@ -168,7 +164,7 @@ __global__ __launch_bounds__(C::THREADS, 2) void conv_wgrad_bf16_kernel(WgParams
         }
     };
 
-    f32x16 acc[9];
+    sis_f32x16 acc[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t)
 #pragma unroll
@@ -191,10 +187,10 @@ __global__ __launch_bounds__(C::THREADS, 2) void conv_wgrad_bf16_kernel(WgParams
             load_x(y + 2);
         }
         constexpr int KW = C::KS / C::WK;  // K-steps of this wave: wk, wk + WK, ...
-        bf16x8 a[KW];
+        sis_bf16x8 a[KW];
 #pragma unroll
         for (int i = 0; i < KW; ++i)
-            a[i] = *reinterpret_cast<const bf16x8*>(a_base + (y & 1) * C::DY_BUF + (wk + i * C::WK) * 32);
+            a[i] = *reinterpret_cast<const sis_bf16x8*>(a_base + (y & 1) * C::DY_BUF + (wk + i * C::WK) * 32);
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
             const int slot = (y + ky) & 3;  // image row y + ky - 1
@@ -316,9 +312,9 @@ struct PwCfg {
 };
 
 struct PwParams {
-    const u16* x; const u16* gy; float* slab;
+    const sis_u16* x; const sis_u16* gy; float* slab;
     int jobs; long long slab_job_stride;   // as WgParams
-    const u16* xj[WG_JOBS_MAX]; const u16* gyj[WG_JOBS_MAX];
+    const sis_u16* xj[WG_JOBS_MAX]; const sis_u16* gyj[WG_JOBS_MAX];
     int N, Cin, Cout, P;              // P = pixels per plane
     int units_per_image, unit_len;    // unit u: image u / units_per_image, pixels [k * unit_len, min(P, (k + 1) * unit_len))
     int co_tiles, ci_tiles;
@@ -333,8 +329,8 @@ __global__ __launch_bounds__(512, 2) void conv1x1_wgrad_bf16_kernel(PwParams p) 
     const int n = blockIdx.x / p.units_per_image, uk = blockIdx.x % p.units_per_image;
     const int co_t = blockIdx.y % p.co_tiles, ci_t = blockIdx.y / p.co_tiles;
     const int p_begin = uk * p.unit_len, p_end = min(p.P, p_begin + p.unit_len);
-    const u16* gy_base = (p.jobs ? p.gyj[blockIdx.z] : p.gy) + ((int64_t)n * p.Cout + co_t * C::MT) * p.P;
-    const u16* x_base = (p.jobs ? p.xj[blockIdx.z] : p.x) + ((int64_t)n * p.Cin + ci_t * C::NT) * p.P;
+    const sis_u16* gy_base = (p.jobs ? p.gyj[blockIdx.z] : p.gy) + ((int64_t)n * p.Cout + co_t * C::MT) * p.P;
+    const sis_u16* x_base = (p.jobs ? p.xj[blockIdx.z] : p.x) + ((int64_t)n * p.Cin + ci_t * C::NT) * p.P;
     const int stages = (p_end - p_begin + C::KP - 1) / C::KP;
 
     uint4 ar[C::NA], br[C::NB];
@@ -372,7 +368,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_wgrad_bf16_kernel(PwParams p) 
         }
     };
 
-    f32x16 acc[2][2];
+    sis_f32x16 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -390,10 +386,10 @@ __global__ __launch_bounds__(512, 2) void conv1x1_wgrad_bf16_kernel(PwParams p) 
 #pragma unroll
         for (int i = 0; i < C::KSW; ++i) {
             const int ks = wk + i * C::WK;
-            const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(st + a_off + ks * 32);
-            const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(st + a_off + 32 * C::PITCH + ks * 32);
-            const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(st + b_off + ks * 32);
-            const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(st + b_off + 32 * C::PITCH + ks * 32);
+            const sis_bf16x8 a0 = *reinterpret_cast<const sis_bf16x8*>(st + a_off + ks * 32);
+            const sis_bf16x8 a1 = *reinterpret_cast<const sis_bf16x8*>(st + a_off + 32 * C::PITCH + ks * 32);
+            const sis_bf16x8 b0 = *reinterpret_cast<const sis_bf16x8*>(st + b_off + ks * 32);
+            const sis_bf16x8 b1 = *reinterpret_cast<const sis_bf16x8*>(st + b_off + 32 * C::PITCH + ks * 32);
             acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[0][0], 0, 0, 0);
             acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[0][1], 0, 0, 0);
             acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[1][0], 0, 0, 0);
@@ -551,7 +547,7 @@ static int conv_wgrad_jobs(void* const* dw, int dw_dtype, const void* const* x, 
     SIS_REQUIRE(wgrad_plan(batch, cin, cout, h, w, workspace_bytes, &pl, n_jobs),
                 "%s: no tile plan for %d x (%d->%d @%dx%d) within %lld workspace bytes", who, n_jobs, cin, cout, h, w, (long long)workspace_bytes);
     WgParams p;
-    p.x = (const u16*)x[0]; p.gy = (const u16*)grad_y[0]; p.slab = (float*)workspace;
+    p.x = (const sis_u16*)x[0]; p.gy = (const sis_u16*)grad_y[0]; p.slab = (float*)workspace;
     p.N = batch; p.Cin = cin; p.Cout = cout; p.H = h; p.W = w;
     p.strips = pl.strips; p.row_blocks = pl.row_blocks; p.rows_per_block = pl.rows_per_block;
     p.co_tiles = pl.co_tiles; p.ci_tiles = pl.ci_tiles;
@@ -561,7 +557,7 @@ static int conv_wgrad_jobs(void* const* dw, int dw_dtype, const void* const* x, 
     WgDwTab tab = {};
     for (int j = 0; j < n_jobs; ++j) {
         SIS_REQUIRE(dw[j] && x[j] && grad_y[j], "%s: null pointer in layer %d", who, j);
-        p.xj[j] = (const u16*)x[j]; p.gyj[j] = (const u16*)grad_y[j]; tab.dw[j] = dw[j];
+        p.xj[j] = (const sis_u16*)x[j]; p.gyj[j] = (const sis_u16*)grad_y[j]; tab.dw[j] = dw[j];
         bits |= (uintptr_t)x[j] | (uintptr_t)grad_y[j];
     }
     p.aligned = (w % 8 == 0) && (bits & 15) == 0;
@@ -638,7 +634,7 @@ static int conv1x1_wgrad_jobs(void* const* dw, int dw_dtype, const void* const* 
     SIS_REQUIRE(pw_plan(batch, cin, cout, pixels, workspace_bytes, &pl, n_jobs),
                 "%s: no plan for %d x (%d->%d, %d pixels) within %lld workspace bytes", who, n_jobs, cin, cout, pixels, (long long)workspace_bytes);
     PwParams p;
-    p.x = (const u16*)x[0]; p.gy = (const u16*)grad_y[0]; p.slab = (float*)workspace;
+    p.x = (const sis_u16*)x[0]; p.gy = (const sis_u16*)grad_y[0]; p.slab = (float*)workspace;
     p.N = batch; p.Cin = cin; p.Cout = cout; p.P = pixels;
     p.units_per_image = pl.units_per_image; p.unit_len = pl.unit_len; p.co_tiles = pl.co_tiles; p.ci_tiles = pl.ci_tiles;
     p.jobs = n_jobs > 1 ? n_jobs : 0;
@@ -647,7 +643,7 @@ static int conv1x1_wgrad_jobs(void* const* dw, int dw_dtype, const void* const* 
     WgDwTab tab = {};
     for (int j = 0; j < n_jobs; ++j) {
         SIS_REQUIRE(dw[j] && x[j] && grad_y[j], "%s: null pointer in layer %d", who, j);
-        p.xj[j] = (const u16*)x[j]; p.gyj[j] = (const u16*)grad_y[j]; tab.dw[j] = dw[j];
+        p.xj[j] = (const sis_u16*)x[j]; p.gyj[j] = (const sis_u16*)grad_y[j]; tab.dw[j] = dw[j];
         bits |= (uintptr_t)x[j] | (uintptr_t)grad_y[j];
     }
     const bool aligned = (pixels % 8 == 0) && (bits & 15) == 0;

@@ -19,16 +19,12 @@
 // (deterministic) and applies G^T . G.
 #include <cstdlib>
 #include <type_traits>
-#include "sis_common.h"
+#include "sis_device.h"
 
 // Timing ablations (WRONG results): development builds only (-DSIS_ABLATIONS -DSIS_WG_NOLOAD ...), refused otherwise.
 #if !defined(SIS_ABLATIONS) && (defined(SIS_WG_NOTRANSFORM) || defined(SIS_WG_NOLOAD) || defined(SIS_WG_NOBARRIER))
 #error "SIS_WG_* ablation switches need -DSIS_ABLATIONS (development builds only)"
 #endif
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -68,16 +64,16 @@ __global__ __launch_bounds__(GTHR, 2) void conv_wgrad_wino_kernel(const WgradPar
     // Two register sets of raw tiles: while chunk c multiplies, set (c + 1) & 1 (loaded during chunk c - 1: a whole chunk of
     // latency cover) is transformed and written to LDS and set c & 1 is refilled with chunk c + 2.
     float xl[2][4], xh[2][4];  // input patch rows 2ty-1 .. 2ty+2: columns 2tx-1 and 2tx+2 ...
-    f32x2 xm[2][4];            // ... and the aligned pair (2tx, 2tx+1) between them
-    f32x2 gr[2][2];            // dY tile rows
+    sis_f32x2 xm[2][4];            // ... and the aligned pair (2tx, 2tx+1) between them
+    sis_f32x2 gr[2][2];            // dY tile rows
     // Tile t = chunk * GK + tk of the flattened (sample, tile row, tile column) order.  The two divisions go through the float
     // reciprocal with one correction step (exact: t < 2^24, host-checked).
     const float inv_tps = 1.f / (float)p.tiles_per_sample, inv_tpr = 1.f / (float)p.tiles_per_row;
     // Loads go through buffer descriptors: a masked element gets an out-of-range offset and the hardware returns 0 -- the mask
     // selects an ADDRESS, so nothing waits for loaded data before the transform a chunk later (a select on the loaded value is
     // a wait for every load in flight, at the slot where the load was issued).
-    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.jobs ? p.xj[blockIdx.z] : p.x), 0, 0x7FFFFFFF, 0x00020000);
-    const __amdgpu_buffer_rsrc_t g_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.jobs ? p.gyj[blockIdx.z] : p.gy), 0, 0x7FFFFFFF, 0x00020000);
+    const __amdgpu_buffer_rsrc_t x_rsrc = sis_buffer_rsrc(p.jobs ? p.xj[blockIdx.z] : p.x);
+    const __amdgpu_buffer_rsrc_t g_rsrc = sis_buffer_rsrc(p.jobs ? p.gyj[blockIdx.z] : p.gy);
     constexpr unsigned OOB = 0x80000000u;
     unsigned g_xo = 0, g_go = 0;  // byte offsets of (patch row 0, column 2tx) and of the dY tile
     bool g_left = false, g_right = false;
@@ -94,7 +90,7 @@ __global__ __launch_bounds__(GTHR, 2) void conv_wgrad_wino_kernel(const WgradPar
         if (!valid) g_go = OOB;
     };
     auto ld1 = [&](__amdgpu_buffer_rsrc_t rsrc, unsigned off) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0)); };
-    auto ld2 = [&](__amdgpu_buffer_rsrc_t rsrc, unsigned off) { return __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, off, 0, 0)); };
+    auto ld2 = [&](__amdgpu_buffer_rsrc_t rsrc, unsigned off) { return __builtin_bit_cast(sis_f32x2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, off, 0, 0)); };
     auto load_x = [&](auto setc, int r) {  // patch row r of the tile geo() described
         constexpr int S = decltype(setc)::value;
         const int y = g_y0 + r;
@@ -148,7 +144,7 @@ __global__ __launch_bounds__(GTHR, 2) void conv_wgrad_wino_kernel(const WgradPar
         vb[2 * XI_STRIDE] = tt[r][2] - tt[r][1]; vb[3 * XI_STRIDE] = tt[r][1] - tt[r][3];
     };
 
-    f32x16 acc[4][2];  // [row i of the 4x4 Winograd point grid][column jj of this wave's pair]
+    sis_f32x16 acc[4][2];  // [row i of the 4x4 Winograd point grid][column jj of this wave's pair]
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -173,8 +169,8 @@ __global__ __launch_bounds__(GTHR, 2) void conv_wgrad_wino_kernel(const WgradPar
     }
     __syncthreads();
     // operand pair of the chunk's first Winograd point: carried from chunk to chunk (requested behind the previous chunk's barrier)
-    f32x4 a = *reinterpret_cast<const f32x4*>(El + aoff + 2 * q * XI_STRIDE);
-    f32x4 b = *reinterpret_cast<const f32x4*>(Vl + boff + 2 * q * XI_STRIDE);
+    sis_f32x4 a = *reinterpret_cast<const sis_f32x4*>(El + aoff + 2 * q * XI_STRIDE);
+    sis_f32x4 b = *reinterpret_cast<const sis_f32x4*>(Vl + boff + 2 * q * XI_STRIDE);
 
     // One chunk: 32 MFMAs in eight groups (one Winograd point each: four steps from one float4 pair, the next group's pair
     // requested first), the side work of the chunk in the sixteen half-group slots between them: set P ^ 1 (chunk c + 1,
@@ -193,14 +189,14 @@ __global__ __launch_bounds__(GTHR, 2) void conv_wgrad_wino_kernel(const WgradPar
 #pragma unroll
         for (int g = 0; g < 8; ++g) {  // Winograd point xi = 4 (g >> 1) + 2 q + (g & 1)
             const int i = g >> 1, jj = g & 1;
-            f32x4 an = a, bn = b;
+            sis_f32x4 an = a, bn = b;
             if (g < 7) {
                 const int xin = 4 * ((g + 1) >> 1) + 2 * q + ((g + 1) & 1);
-                an = *reinterpret_cast<const f32x4*>(Eb + xin * XI_STRIDE);
-                bn = *reinterpret_cast<const f32x4*>(Vb + xin * XI_STRIDE);
+                an = *reinterpret_cast<const sis_f32x4*>(Eb + xin * XI_STRIDE);
+                bn = *reinterpret_cast<const sis_f32x4*>(Vb + xin * XI_STRIDE);
             } else {  // behind the chunk's barrier (below, after group 6): the first pair of chunk c + 1, under this chunk's last MFMAs
-                an = *reinterpret_cast<const f32x4*>(El + (P ^ 1) * IMG + aoff + xi0 * XI_STRIDE);
-                bn = *reinterpret_cast<const f32x4*>(Vl + (P ^ 1) * IMG + boff + xi0 * XI_STRIDE);
+                an = *reinterpret_cast<const sis_f32x4*>(El + (P ^ 1) * IMG + aoff + xi0 * XI_STRIDE);
+                bn = *reinterpret_cast<const sis_f32x4*>(Vl + (P ^ 1) * IMG + boff + xi0 * XI_STRIDE);
             }
             acc[i][jj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc[i][jj], 0, 0, 0);
             acc[i][jj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc[i][jj], 0, 0, 0);

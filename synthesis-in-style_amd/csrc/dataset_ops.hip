@@ -14,29 +14,27 @@
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
-#include "sis_common.h"
+#include "sis_device.h"
 
 namespace {
 
-typedef float km_f32x2 __attribute__((ext_vector_type(2)));
-typedef float km_f32x4 __attribute__((ext_vector_type(4)));
 // Packed fp32 forms of the three separately rounded operations of a k-means term, two pixels per instruction (IEEE add / mul
 // per half: the same bits as the scalar instructions; inline assembly, so no contraction either).  The centre is one half
 // of a register pair as ds_read_b128 delivers it, broadcast to both pixels by op_sel.
 template <int HI>
-__device__ __forceinline__ km_f32x2 km_sub_bcast(km_f32x2 x, km_f32x2 cpair) {  // x - cpair[HI]
-    km_f32x2 r;
+__device__ __forceinline__ sis_f32x2 km_sub_bcast(sis_f32x2 x, sis_f32x2 cpair) {  // x - cpair[HI]
+    sis_f32x2 r;
     if constexpr (HI == 0) asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(x), "v"(cpair));
     else asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(x), "v"(cpair));
     return r;
 }
-__device__ __forceinline__ km_f32x2 km_sq(km_f32x2 d) {
-    km_f32x2 r;
+__device__ __forceinline__ sis_f32x2 km_sq(sis_f32x2 d) {
+    sis_f32x2 r;
     asm("v_pk_mul_f32 %0, %1, %1" : "=v"(r) : "v"(d));
     return r;
 }
-__device__ __forceinline__ km_f32x2 km_add(km_f32x2 a, km_f32x2 b) {
-    km_f32x2 r;
+__device__ __forceinline__ sis_f32x2 km_add(sis_f32x2 a, sis_f32x2 b) {
+    sis_f32x2 r;
     asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
@@ -122,9 +120,9 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(int64_t* __restrict_
     const bool fast = !CASCADE && (C & 127) == 0;
     if (fast) {
         float xs[2][8][VEC];
-        km_f32x2 a2[KMAX], l2[KMAX], f2[KMAX];  // (VEC == 2: the accumulators as register pairs)
+        sis_f32x2 a2[KMAX], l2[KMAX], f2[KMAX];  // (VEC == 2: the accumulators as register pairs)
 #pragma unroll
-        for (int k = 0; k < KMAX; ++k) { a2[k] = km_f32x2{0.f, 0.f}; l2[k] = a2[k]; f2[k] = a2[k]; }
+        for (int k = 0; k < KMAX; ++k) { a2[k] = sis_f32x2{0.f, 0.f}; l2[k] = a2[k]; f2[k] = a2[k]; }
         constexpr bool PK = VEC == 2 && KMAX % 4 == 0;
         const int ng = rows >> 1;  // groups of eight steps per lane position
         auto chan = [&](int l, int p) { const int part = p / rows, r = p - part * rows; return (((r << 2) + part) << 3) + l; };
@@ -155,7 +153,7 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(int64_t* __restrict_
                 if (r == 0) {
 #pragma unroll
                     for (int k = 0; k < KMAX; ++k) {
-                        if constexpr (PK) a2[k] = km_f32x2{0.f, 0.f};
+                        if constexpr (PK) a2[k] = sis_f32x2{0.f, 0.f};
                         else
 #pragma unroll
                             for (int v = 0; v < VEC; ++v) acc0[k][v] = 0.f;
@@ -163,15 +161,15 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(int64_t* __restrict_
                 }
                 const float* cc = cen + ((((r << 2) + part) << 3) + l) * KMAX;
                 if constexpr (VEC == 2 && KMAX % 4 == 0) {  // two pixels per instruction
-                    const km_f32x2 xp = {xs[S][u][0], xs[S][u][1]};
+                    const sis_f32x2 xp = {xs[S][u][0], xs[S][u][1]};
 #pragma unroll
                     for (int k4 = 0; k4 < KMAX; k4 += 4) {
-                        const km_f32x4 c4 = *reinterpret_cast<const km_f32x4*>(cc + k4);
-                        const km_f32x2 c01 = {c4.x, c4.y}, c23 = {c4.z, c4.w};
+                        const sis_f32x4 c4 = *reinterpret_cast<const sis_f32x4*>(cc + k4);
+                        const sis_f32x2 c01 = {c4.x, c4.y}, c23 = {c4.z, c4.w};
 #pragma unroll
                         for (int kk = 0; kk < 4; ++kk) {
-                            const km_f32x2 cp = kk < 2 ? c01 : c23;
-                            const km_f32x2 d = (kk & 1) ? km_sub_bcast<1>(xp, cp) : km_sub_bcast<0>(xp, cp);
+                            const sis_f32x2 cp = kk < 2 ? c01 : c23;
+                            const sis_f32x2 d = (kk & 1) ? km_sub_bcast<1>(xp, cp) : km_sub_bcast<0>(xp, cp);
                             a2[k4 + kk] = km_add(a2[k4 + kk], km_sq(d));
                         }
                     }
@@ -278,8 +276,8 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(int64_t* __restrict_
 // in exact order, add for add as before: the label map stays bit-exact.  Unit-variance data, 24 random centres: 0.05 % (128
 // channels) to 0.4 % (512) of the pixels stay open -- at least one in most 512-pixel workgroups, hence the list: the block
 // form of the refinement (no workspace) would redo almost everything.
-__device__ __forceinline__ km_f32x2 km_fma_sq(km_f32x2 d, km_f32x2 acc) {   // acc + d * d, one rounding per half
-    km_f32x2 r;
+__device__ __forceinline__ sis_f32x2 km_fma_sq(sis_f32x2 d, sis_f32x2 acc) {   // acc + d * d, one rounding per half
+    sis_f32x2 r;
     asm("v_pk_fma_f32 %0, %1, %1, %2" : "=v"(r) : "v"(d), "v"(acc));
     return r;
 }
@@ -299,9 +297,9 @@ __global__ __launch_bounds__(256) void kmeans_fast_kernel(int64_t* __restrict__ 
     const int pix = (g * 256 + threadIdx.x) * 2;
     if (pix >= HW) return;
     const float* xb = x + (int64_t)b * C * HW + pix;
-    km_f32x2 run[KMAX], tot[KMAX];   // (four pixels per lane -- a channel's centres read once per 96 operations -- measured slower: 400 vs 300 us)
+    sis_f32x2 run[KMAX], tot[KMAX];   // (four pixels per lane -- a channel's centres read once per 96 operations -- measured slower: 400 vs 300 us)
 #pragma unroll
-    for (int k = 0; k < KMAX; ++k) { run[k] = km_f32x2{0.f, 0.f}; tot[k] = run[k]; }
+    for (int k = 0; k < KMAX; ++k) { run[k] = sis_f32x2{0.f, 0.f}; tot[k] = run[k]; }
     float2 xs[2][16];
     auto request = [&](auto setc, int c0) {
         constexpr int S = decltype(setc)::value;
@@ -313,12 +311,12 @@ __global__ __launch_bounds__(256) void kmeans_fast_kernel(int64_t* __restrict__ 
         request(std::integral_constant<int, S ^ 1>(), c0 + 16 < C ? c0 + 16 : c0);   // (past the end: this block again, unused)
 #pragma unroll
         for (int u = 0; u < 16; ++u) {
-            const km_f32x2 xp = {xs[S][u].x, xs[S][u].y};
+            const sis_f32x2 xp = {xs[S][u].x, xs[S][u].y};
             const float* cc = cen + (c0 + u) * KMAX;
 #pragma unroll
             for (int k4 = 0; k4 < KMAX; k4 += 4) {
-                const km_f32x4 c4 = *reinterpret_cast<const km_f32x4*>(cc + k4);
-                const km_f32x2 c01 = {c4.x, c4.y}, c23 = {c4.z, c4.w};
+                const sis_f32x4 c4 = *reinterpret_cast<const sis_f32x4*>(cc + k4);
+                const sis_f32x2 c01 = {c4.x, c4.y}, c23 = {c4.z, c4.w};
                 run[k4 + 0] = km_fma_sq(km_sub_bcast<0>(xp, c01), run[k4 + 0]);
                 run[k4 + 1] = km_fma_sq(km_sub_bcast<1>(xp, c01), run[k4 + 1]);
                 run[k4 + 2] = km_fma_sq(km_sub_bcast<0>(xp, c23), run[k4 + 2]);
@@ -326,7 +324,7 @@ __global__ __launch_bounds__(256) void kmeans_fast_kernel(int64_t* __restrict__ 
             }
         }
 #pragma unroll
-        for (int k = 0; k < KMAX; ++k) { tot[k] = km_add(tot[k], run[k]); run[k] = km_f32x2{0.f, 0.f}; }
+        for (int k = 0; k < KMAX; ++k) { tot[k] = km_add(tot[k], run[k]); run[k] = sis_f32x2{0.f, 0.f}; }
     };
     request(std::integral_constant<int, 0>(), 0);
     for (int c0 = 0; c0 < C; c0 += 32) {   // C % 16 == 0 (host-checked)
@@ -354,7 +352,6 @@ __global__ __launch_bounds__(256) void kmeans_fast_kernel(int64_t* __restrict__ 
     }
 }
 
-
 // First pass on the matrix cores (the shapes of the generator's catalogued layers: HW % 128 == 0, C % 16 == 0, K <= 32).
 // argmin_k |x - c_k|^2 = argmin_k (|c_k|^2 - 2 x.c_k): the dot products are a GEMM  S[k][pixel] = sum_c centres[k][c] x[c][pixel]
 // whose B operand is the NCHW activation as it lies in memory -- v_mfma_f32_32x32x2_f32 (exact fp32 products and sums) takes
@@ -366,8 +363,6 @@ __global__ __launch_bounds__(256) void kmeans_fast_kernel(int64_t* __restrict__ 
 // and the exact-order kernel's |d_exact - D| <= (C/32 + 32) u D <= (C/32 + 32) u 2 (|x|^2 + |c_k|^2).  A pixel whose two smallest
 // fast values differ by more than e_x |x|^2 + e_c max|c|^2 (twice the sum of both bounds, x 1.5) has the same argmin in exact
 // order and gets its label here; every other pixel (near-ties, NaN) is listed for kmeans_refine_kernel as before.
-typedef float km_f32x16 __attribute__((ext_vector_type(16)));
-
 __global__ __launch_bounds__(256) void kmeans_mfma_kernel(int64_t* __restrict__ labels, const float* __restrict__ x,
                                                           const float* __restrict__ centres, int C, int HW, int K, int tiles,
                                                           float e_x, float e_c, int* __restrict__ open_count,
@@ -404,17 +399,17 @@ __global__ __launch_bounds__(256) void kmeans_mfma_kernel(int64_t* __restrict__ 
     for (int t = blockIdx.x * 4 + wave; t < tiles; t += gridDim.x * 4) {
         const int b = t / tiles_per_sample, pix0 = (t - b * tiles_per_sample) << 7;
         const float* xb = x + ((int64_t)b * C + half) * HW + pix0 + 4 * l31;
-        km_f32x16 acc[4];
+        sis_f32x16 acc[4];
         float xx[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
-        km_f32x4 xs[2][U];
+        sis_f32x4 xs[2][U];
         auto request = [&](auto setc, int c0) {
             constexpr int S = decltype(setc)::value;
 #pragma unroll
-            for (int s = 0; s < U; ++s) xs[S][s] = *reinterpret_cast<const km_f32x4*>(xb + (int64_t)(c0 + 2 * s) * HW);
+            for (int s = 0; s < U; ++s) xs[S][s] = *reinterpret_cast<const sis_f32x4*>(xb + (int64_t)(c0 + 2 * s) * HW);
         };
         auto block = [&](auto setc, int c0) {
             constexpr int S = decltype(setc)::value;
@@ -422,7 +417,7 @@ __global__ __launch_bounds__(256) void kmeans_mfma_kernel(int64_t* __restrict__ 
 #pragma unroll
             for (int s = 0; s < U; ++s) {
                 const float a = ab[(c0 + 2 * s) * 32];
-                const km_f32x4 v = xs[S][s];
+                const sis_f32x4 v = xs[S][s];
                 acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, v.x, acc[0], 0, 0, 0);
                 acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, v.y, acc[1], 0, 0, 0);
                 acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, v.z, acc[2], 0, 0, 0);
@@ -463,9 +458,8 @@ __global__ __launch_bounds__(256) void kmeans_mfma_kernel(int64_t* __restrict__ 
         }
         if (half == 0) {
             int64_t* out = labels + (int64_t)b * HW + pix0 + 4 * l31;
-            typedef long long km_i64x2 __attribute__((ext_vector_type(2)));
-            *reinterpret_cast<km_i64x2*>(out) = km_i64x2{lab[0], lab[1]};
-            *reinterpret_cast<km_i64x2*>(out + 2) = km_i64x2{lab[2], lab[3]};
+            *reinterpret_cast<sis_i64x2*>(out) = sis_i64x2{lab[0], lab[1]};
+            *reinterpret_cast<sis_i64x2*>(out + 2) = sis_i64x2{lab[2], lab[3]};
             if (open_list) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j)

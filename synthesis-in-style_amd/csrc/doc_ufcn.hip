@@ -34,8 +34,6 @@ constexpr int DC_PAD = 4;    // LDS row padding (floats)
 
 // acc[j] of lane l holds C[row = 8 * (j / 4) + 4 * (l / 32) + j % 4][col = l % 32]; A operand A[m = l % 32][k = l / 32],
 // B operand B[k = l / 32][n = l % 32].
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
 template <int WM>   // waves along M (2: 64 x 64 tile, 1: 32 x 128 tile)
 __global__ __launch_bounds__(256) void dconv3x3_kernel(float* __restrict__ out, const float* __restrict__ x,
                                                        const float* __restrict__ w, const float* __restrict__ bias, int Cin,
@@ -54,7 +52,7 @@ __global__ __launch_bounds__(256) void dconv3x3_kernel(float* __restrict__ out, 
     const int ya = p0 / W, yb = plast / W;
     const int xa = ya == yb ? p0 % W : 0, xb_ = ya == yb ? plast % W : W - 1;
 
-    f32x16 acc;
+    sis_f32x16 acc;
 #pragma unroll
     for (int j = 0; j < 16; ++j) acc[j] = 0.f;
 
@@ -120,7 +118,7 @@ __global__ __launch_bounds__(256) void dconv3x3_wgrad_kernel(float* __restrict__
     const int n0 = blockIdx.x * 64, co0 = blockIdx.y * 64;
     const int64_t P = (int64_t)B * HW;
     const int64_t lo = blockIdx.z * per_slice, hi = min(P, lo + per_slice);
-    f32x16 acc;
+    sis_f32x16 acc;
 #pragma unroll
     for (int j = 0; j < 16; ++j) acc[j] = 0.f;
     for (int64_t q0 = lo; q0 < hi; q0 += DC_KC) {
@@ -172,15 +170,6 @@ __global__ void slice_sum_kernel(float* __restrict__ out, const float* __restric
     }
 }
 
-__device__ __forceinline__ float dc_block_sum(float v, float* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // db[c] = sum over b, p of dy[b][c][p] (rows of dy are `bstride` floats apart per sample)
 __global__ __launch_bounds__(256) void channel_sum_kernel(float* __restrict__ db, const float* __restrict__ dy, int B, int C,
                                                           int HW) {
@@ -191,7 +180,7 @@ __global__ __launch_bounds__(256) void channel_sum_kernel(float* __restrict__ db
         const float* row = dy + ((int64_t)b * C + c) * HW;
         for (int p = threadIdx.x; p < HW; p += 256) s += row[p];
     }
-    s = dc_block_sum(s, red);
+    s = sis_block_sum4(s, red);
     if (threadIdx.x == 0) db[c] = s;
 }
 
@@ -300,15 +289,6 @@ __device__ __forceinline__ void bn_drop_grad4(const BnDropBwdArgs& a, int b, int
     }
 }
 
-__device__ __forceinline__ double dc_block_sum_f64(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // partial[c][s] = (sum g', sum g' * xhat) over slice s of channel c, in double: sum of the gated g, and of g * (x - mean), with
 // exact products, scaled by keep_scale (and invstd) once at the end.  dgamma[c] and dbeta[c] are sums of gradients of both signs
 // that cancel to a small part of sum |terms|: an fp32 running sum over fp32-rounded terms left ~1e-8 - 6e-8 sum |terms|, which is
@@ -339,8 +319,8 @@ __global__ __launch_bounds__(256) void bn_drop_bwd_reduce_kernel(double* __restr
             s1 += gq * ((double)xs[q] - m);
         }
     }
-    s0 = dc_block_sum_f64(s0, red);
-    s1 = dc_block_sum_f64(s1, red);
+    s0 = sis_block_sum4(s0, red);
+    s1 = sis_block_sum4(s1, red);
     if (threadIdx.x == 0) {
         partial[2 * blockIdx.x] = s0 * (double)a.keep_scale;
         partial[2 * blockIdx.x + 1] = s1 * (double)a.keep_scale * (double)a.invstd[c];
@@ -409,8 +389,8 @@ __global__ __launch_bounds__(256) void wce_fwd_kernel(float* __restrict__ partia
         sl = __builtin_fmaf(w, nll, sl);
         sw += w;
     }
-    sl = dc_block_sum(sl, red);
-    sw = dc_block_sum(sw, red);
+    sl = sis_block_sum4(sl, red);
+    sw = sis_block_sum4(sw, red);
     if (threadIdx.x == 0) { partial[2 * blockIdx.x] = sl; partial[2 * blockIdx.x + 1] = sw; }
 }
 
@@ -461,7 +441,7 @@ __global__ __launch_bounds__(256) void adam_clip_norm_kernel(float* __restrict__
     const int n = (int)(row[4] & 0xffffffffll);
     float s = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) s = __builtin_fmaf(gr[i], gr[i], s);
-    s = dc_block_sum(s, red);
+    s = sis_block_sum4(s, red);
     if (threadIdx.x == 0) {
         partial[blockIdx.x] = s;
         if (blockIdx.x == 0) step[0] += 1;   // read by the update launch that follows (stream order)
@@ -475,7 +455,7 @@ __global__ __launch_bounds__(256) void adam_step_kernel(const int64_t* __restric
     // the total norm: every workgroup sums the same partials in the same order
     float s = 0.f;
     for (int i = threadIdx.x; i < n_chunks; i += 256) s += partial[i];
-    s = dc_block_sum(s, red);
+    s = sis_block_sum4(s, red);
     const float max_norm = hyper[20];
     const float coef = fminf(max_norm / (sqrtf(s) + 1e-6f), 1.f);
 

@@ -21,12 +21,9 @@
 //
 // MFMA operand convention used throughout (as csrc/gen_small_ops.hip): D = mfma(a, b): lane l supplies a = A[row l & 31][kk = l >> 5],
 // b = B[kk = l >> 5][col l & 31]; afterwards the lane holds column l & 31, rows (i & 3) + 8 (i >> 2) + 4 (l >> 5), i = 0..15.
-#include "sis_common.h"
+#include "sis_device.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;   // (staging registers: HIP's float4 struct arrays end up in scratch)
 
 constexpr int EK = 64;        // bases (the kernels are written for k = 64: two 32-wide MFMA tiles)
 constexpr int E_NS = 64;      // pixels per workgroup of the E and reconstruction kernels
@@ -75,24 +72,24 @@ __global__ __launch_bounds__(256) void emau_e_kernel(EmauParams p) {
     const float* mb = p.mu_in + (long long)b * p.mu_bstride;
     if (tid < EK) scale_s[tid] = l2_scale(p.sq_part, b, p.c / M_CS, tid);
 
-    f32x4 xr[4], mr[4];   // one chunk in flight: 64 channels x (64 pixels + 64 bases) = 2048 float4 over 256 threads
+    sis_f32x4 xr[4], mr[4];   // one chunk in flight: 64 channels x (64 pixels + 64 bases) = 2048 float4 over 256 threads
     auto load = [&](int c0) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int i = tid + 256 * j, row = i >> 4, q = i & 15;
-            xr[j] = *reinterpret_cast<const f32x4*>(xb + (long long)(c0 + row) * p.n + 4 * q);
-            mr[j] = *reinterpret_cast<const f32x4*>(mb + (long long)(c0 + row) * EK + 4 * q);
+            xr[j] = *reinterpret_cast<const sis_f32x4*>(xb + (long long)(c0 + row) * p.n + 4 * q);
+            mr[j] = *reinterpret_cast<const sis_f32x4*>(mb + (long long)(c0 + row) * EK + 4 * q);
         }
     };
     auto store = [&](int buf) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int i = tid + 256 * j, row = i >> 4, q = i & 15;
-            *reinterpret_cast<f32x4*>(&xs[buf][row][4 * q]) = xr[j];
-            *reinterpret_cast<f32x4*>(&ms[buf][row][4 * q]) = mr[j];
+            *reinterpret_cast<sis_f32x4*>(&xs[buf][row][4 * q]) = xr[j];
+            *reinterpret_cast<sis_f32x4*>(&ms[buf][row][4 * q]) = mr[j];
         }
     };
-    f32x16 acc;
+    sis_f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     const int chunks = p.c / E_CC;
@@ -170,7 +167,7 @@ __global__ __launch_bounds__(256) void emau_m_kernel(EmauParams p) {
         for (int i = 0; i < nslices; ++i) s += cp[i * EK];
         inv_s[tid] = 1.f / (1e-6f + s);
     }
-    f32x4 xr[2][2], zr[2][4];   // per n half: 32 channels x 64 pixels = 512 float4, 64 pixels x 64 bases = 1024 float4
+    sis_f32x4 xr[2][2], zr[2][4];   // per n half: 32 channels x 64 pixels = 512 float4, 64 pixels x 64 bases = 1024 float4
     auto load = [&](int nn) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -178,12 +175,12 @@ __global__ __launch_bounds__(256) void emau_m_kernel(EmauParams p) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const int i = tid + 256 * j, row = i >> 4, q = i & 15;
-                xr[h][j] = *reinterpret_cast<const f32x4*>(xb + (long long)row * p.n + nbase + 4 * q);
+                xr[h][j] = *reinterpret_cast<const sis_f32x4*>(xb + (long long)row * p.n + nbase + 4 * q);
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int i = tid + 256 * j;
-                zr[h][j] = *reinterpret_cast<const f32x4*>(zb + (long long)nbase * EK + 4 * i);
+                zr[h][j] = *reinterpret_cast<const sis_f32x4*>(zb + (long long)nbase * EK + 4 * i);
             }
         }
     };
@@ -199,11 +196,11 @@ __global__ __launch_bounds__(256) void emau_m_kernel(EmauParams p) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int i = tid + 256 * j;
-                *reinterpret_cast<f32x4*>(&zs[buf][h][0][0] + 4 * i) = zr[h][j];
+                *reinterpret_cast<sis_f32x4*>(&zs[buf][h][0][0] + 4 * i) = zr[h][j];
             }
         }
     };
-    f32x16 acc;
+    sis_f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     const int chunks = nhalf / M_NC;
@@ -291,7 +288,7 @@ __global__ __launch_bounds__(256) void emau_recon_kernel(EmauParams p) {
     for (int ch = 0; ch < chunks; ++ch) {
         const int buf = ch & 1;
         if (ch + 1 < chunks) load((ch + 1) * E_CC);
-        f32x16 acc;
+        sis_f32x16 acc;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
         const float* ap = &ms[buf][ct * 32 + l31][half];      // A[row = channel][kk = base]

@@ -33,11 +33,6 @@
 
 namespace {
 
-typedef unsigned short u16;
-typedef sis_bf16x8 bf16x8;
-typedef sis_f32x4 f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
 template <int NP_>
 struct G256Cfg {
     static constexpr int NP = NP_, NB = 3 * NP_, NS = 4;
@@ -82,8 +77,8 @@ __global__ __launch_bounds__(C::THREADS) void gemm256_kernel(G256Params p) {
 #endif
     G256_STAMP(0);
 
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.A), 0, p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.B), 0, p.b_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsA = sis_buffer_rsrc(p.A, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t rsB = sis_buffer_rsrc(p.B, p.b_bytes);
 
     // ---- LDS-DMA source offsets of this lane (bytes from the operand base at K step 0); a 1 KiB piece = 16 rows x 64 B
     int a_src[C::PA], b_src[C::PB_MAX];
@@ -105,11 +100,11 @@ __global__ __launch_bounds__(C::THREADS) void gemm256_kernel(G256Params p) {
         const int koff = t * (C::BK * 2);
 #pragma unroll
         for (int i = 0; i < C::PA; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_void*)(dst + (wave + i * C::WAVES) * 1024), 16, a_src[i], koff, 0, 0);
+            sis_buffer_load_lds16(rsA, dst + (wave + i * C::WAVES) * 1024, a_src[i], koff);
 #pragma unroll
         for (int i = 0; i < C::PB_MAX - 1; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_void*)(dst + C::A_BYTES + (wave + i * C::WAVES) * 1024), 16, b_src[i], koff, 0, 0);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_void*)((b_last ? dst : lds) + last_dst), 16, b_src[C::PB_MAX - 1], koff, 0, 0);
+            sis_buffer_load_lds16(rsB, dst + C::A_BYTES + (wave + i * C::WAVES) * 1024, b_src[i], koff);
+        sis_buffer_load_lds16(rsB, (b_last ? dst : lds) + last_dst, b_src[C::PB_MAX - 1], koff);
     };
     // End of a K step: at most ONE step's DMA pieces of this wave stay in flight (the older step has landed), every LDS read
     // of this wave has returned (the stage read in this step may be overwritten after the barrier), then the barrier.  The two
@@ -128,28 +123,28 @@ __global__ __launch_bounds__(C::THREADS) void gemm256_kernel(G256Params p) {
     const int a_base = (wm * 64 + i16) * 64 + swz;
     const int b_base = C::A_BYTES + (wn * C::WNC + i16) * 64 + swz;
 
-    f32x4 acc[NB][4];   // [n block][m block]
+    sis_f32x4 acc[NB][4];   // [n block][m block]
 #pragma unroll
     for (int a = 0; a < NB; ++a)
 #pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < 4; ++b) acc[a][b] = sis_f32x4{0.f, 0.f, 0.f, 0.f};
 
-    bf16x8 fa0[4], fb0[3], fa1[4], fb1[3];   // the two register sets of the early fragments (A blocks, first panel of B)
-    auto read_early = [&](bf16x8* fa, bf16x8* fb, int t) {
+    sis_bf16x8 fa0[4], fb0[3], fa1[4], fb1[3];   // the two register sets of the early fragments (A blocks, first panel of B)
+    auto read_early = [&](sis_bf16x8* fa, sis_bf16x8* fb, int t) {
         const unsigned char* st = lds + (t % NS) * C::STAGE;
 #pragma unroll
-        for (int x = 0; x < 4; ++x) fa[x] = *reinterpret_cast<const bf16x8*>(st + a_base + x * 1024);
+        for (int x = 0; x < 4; ++x) fa[x] = *reinterpret_cast<const sis_bf16x8*>(st + a_base + x * 1024);
 #pragma unroll
-        for (int x = 0; x < 3; ++x) fb[x] = *reinterpret_cast<const bf16x8*>(st + b_base + x * 1024);
+        for (int x = 0; x < 3; ++x) fb[x] = *reinterpret_cast<const sis_bf16x8*>(st + b_base + x * 1024);
     };
 
     // One K step.  CUR / NXT: register sets; DMA: step t + 3 exists; NEXT: step t + 1 exists.
-    auto step = [&](bf16x8* fa, bf16x8* fb, bf16x8* fan, bf16x8* fbn, auto dma_t, auto next_t, int t) {
+    auto step = [&](sis_bf16x8* fa, sis_bf16x8* fb, sis_bf16x8* fan, sis_bf16x8* fbn, auto dma_t, auto next_t, int t) {
         constexpr bool DMA = decltype(dma_t)::value, NEXT = decltype(next_t)::value;
         const unsigned char* st = lds + (t % NS) * C::STAGE;
-        bf16x8 fl[NB > 3 ? NB - 3 : 1];   // the later panels' B fragments of THIS step
+        sis_bf16x8 fl[NB > 3 ? NB - 3 : 1];   // the later panels' B fragments of THIS step
 #pragma unroll
-        for (int x = 3; x < NB; ++x) fl[x - 3] = *reinterpret_cast<const bf16x8*>(st + b_base + x * 1024);
+        for (int x = 3; x < NB; ++x) fl[x - 3] = *reinterpret_cast<const sis_bf16x8*>(st + b_base + x * 1024);
         if constexpr (NEXT) read_early(fan, fbn, t + 1);
         if constexpr (DMA) issue(t + 3);
 #pragma unroll
@@ -289,12 +284,12 @@ __global__ __launch_bounds__(C::THREADS) void gemm256_kernel(G256Params p) {
                         {
                             const auto sx = __builtin_amdgcn_permlane16_swap(a0.x, b0.x, false, false);
                             const auto sy = __builtin_amdgcn_permlane16_swap(a0.y, b0.y, false, false);
-                            *reinterpret_cast<uint4*>((u16*)p.C + at) = make_uint4(sx[0], sy[0], sx[1], sy[1]);
+                            *reinterpret_cast<uint4*>((sis_u16*)p.C + at) = make_uint4(sx[0], sy[0], sx[1], sy[1]);
                         }
                         if constexpr (EPI == SIS_GEMM_EPI_BIAS_GELU_DROP) {
                             const auto sx = __builtin_amdgcn_permlane16_swap(a1.x, b1.x, false, false);
                             const auto sy = __builtin_amdgcn_permlane16_swap(a1.y, b1.y, false, false);
-                            *reinterpret_cast<uint4*>((u16*)p.C2 + at) = make_uint4(sx[0], sy[0], sx[1], sy[1]);
+                            *reinterpret_cast<uint4*>((sis_u16*)p.C2 + at) = make_uint4(sx[0], sy[0], sx[1], sy[1]);
                         }
                     }
                 }
@@ -309,8 +304,8 @@ __global__ __launch_bounds__(C::THREADS) void gemm256_kernel(G256Params p) {
                         uint2 hpre = make_uint2(0u, 0u), o0, o1;
                         if constexpr (EPI == SIS_GEMM_EPI_GELU_BWD) hpre = *reinterpret_cast<const uint2*>(p.pre + at);
                         block_bf16(tn, tm, m, n, bq, hpre, o0, o1);
-                        *reinterpret_cast<uint2*>((u16*)p.C + at) = o0;
-                        if constexpr (EPI == SIS_GEMM_EPI_BIAS_GELU_DROP) *reinterpret_cast<uint2*>((u16*)p.C2 + at) = o1;
+                        *reinterpret_cast<uint2*>((sis_u16*)p.C + at) = o0;
+                        if constexpr (EPI == SIS_GEMM_EPI_BIAS_GELU_DROP) *reinterpret_cast<uint2*>((sis_u16*)p.C2 + at) = o1;
                     }
                 }
                 return;
@@ -339,8 +334,8 @@ __global__ __launch_bounds__(C::THREADS) void gemm256_kernel(G256Params p) {
                     uint2 o0, o1;
                     block_bf16(tn, tm, m, n, bq, h[tm], o0, o1);
                     if (ok) {
-                        *reinterpret_cast<uint2*>((u16*)p.C + at) = o0;
-                        if constexpr (EPI == SIS_GEMM_EPI_BIAS_GELU_DROP) *reinterpret_cast<uint2*>((u16*)p.C2 + at) = o1;
+                        *reinterpret_cast<uint2*>((sis_u16*)p.C + at) = o0;
+                        if constexpr (EPI == SIS_GEMM_EPI_BIAS_GELU_DROP) *reinterpret_cast<uint2*>((sis_u16*)p.C2 + at) = o1;
                     }
                 } else {   // SIS_GEMM_EPI_BIAS_DROP_RESID: fp32 residual stream, 16 bytes per lane and block already
                     float keep[4] = {1.f, 1.f, 1.f, 1.f};

@@ -32,12 +32,6 @@
 
 namespace {
 
-typedef unsigned short u16;
-typedef sis_bf16x8 bf16x8;
-typedef sis_bf16x4 bf16x4;
-typedef sis_f32x4 f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
 enum { LAYOUT_NT = 0, LAYOUT_NN = 1, LAYOUT_TN = 2 };
 
 constexpr int GEMM_TAB_MAX = 16;
@@ -50,7 +44,7 @@ struct GemmParams {
     int M, N, K;
     void* C; void* C2; int ldc;
     const float* bias; const float* bias1; const float* bias2; int bias_seg;   // bias_seg > 0: columns [k * seg, (k + 1) * seg) take bias k
-    const float* resid; const u16* pre;
+    const float* resid; const sis_u16* pre;
     const unsigned long long* seed; unsigned site, drop_thr; float drop_scale;   // drop_thr: 16-bit threshold
     int m_tiles, n_tiles, splits, ksteps_per_split;
     long long slab_stride;        // elements between the fp32 partial slabs of a split-K run
@@ -115,7 +109,7 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmParams p) 
             const int cg = cs % groups, slice = cs / groups;
             const int c = cg * 256 + 4 * lane;
             const int r_lo = slice * p.cs_rows_per_slice, r_hi = min(p.K, r_lo + p.cs_rows_per_slice);
-            const u16* x = (const u16*)(p.ptr_batches ? p.tabA[blockIdx.y] : p.A);
+            const sis_u16* x = (const sis_u16*)(p.ptr_batches ? p.tabA[blockIdx.y] : p.A);
             float* cs_out = p.cs_part + (p.ptr_batches ? (long long)blockIdx.y * p.cs_slices * p.M : 0);
             float acc[4] = {0.f, 0.f, 0.f, 0.f};
             auto load4 = [&](int r, float* v) {
@@ -177,12 +171,12 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmParams p) 
     const int T = min(p.ksteps_per_split, ks_total - ks_begin);   // K steps of this workgroup (>= 1 by construction)
 
     const long long bidx = p.batch_k ? split : (long long)blockIdx.y;
-    const u16* Ab = p.ptr_batches ? (const u16*)p.tabA[blockIdx.y] : (const u16*)p.A + bidx * p.a_bstride;
-    const u16* Bb = p.ptr_batches ? (const u16*)p.tabB[blockIdx.y] : (const u16*)p.B + bidx * p.b_bstride;
+    const sis_u16* Ab = p.ptr_batches ? (const sis_u16*)p.tabA[blockIdx.y] : (const sis_u16*)p.A + bidx * p.a_bstride;
+    const sis_u16* Bb = p.ptr_batches ? (const sis_u16*)p.tabB[blockIdx.y] : (const sis_u16*)p.B + bidx * p.b_bstride;
     void* const Cb = p.ptr_batches ? p.tabC[blockIdx.y] : p.C;
     const long long c_batch = (p.batch_k || p.ptr_batches) ? 0 : (long long)blockIdx.y * p.c_bstride;
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(Ab), 0, p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(Bb), 0, p.b_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsA = sis_buffer_rsrc(Ab, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t rsB = sis_buffer_rsrc(Bb, p.b_bytes);
 
     // ---- DMA source offsets of this lane (bytes from the operand base, K step 0), fixed over the loop
     int a_src[C::PA], b_src[C::PB];
@@ -225,10 +219,10 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmParams p) 
         const int sa = ks * a_step, sb = ks * b_step;
 #pragma unroll
         for (int i = 0; i < C::PA; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_void*)(dst + (wave + i * C::WAVES) * 1024), 16, a_src[i], sa, 0, 0);
+            sis_buffer_load_lds16(rsA, dst + (wave + i * C::WAVES) * 1024, a_src[i], sa);
 #pragma unroll
         for (int i = 0; i < C::PB; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_void*)(dst + C::A_BYTES + (wave + i * C::WAVES) * 1024), 16, b_src[i], sb, 0, 0);
+            sis_buffer_load_lds16(rsB, dst + C::A_BYTES + (wave + i * C::WAVES) * 1024, b_src[i], sb);
     };
 
     // ---- fragment read offsets (bytes inside a stage)
@@ -266,20 +260,20 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmParams p) 
             }
     }
 
-    f32x4 acc[C::NBK][4];   // [n block][m block]
+    sis_f32x4 acc[C::NBK][4];   // [n block][m block]
 #pragma unroll
     for (int a = 0; a < C::NBK; ++a)
 #pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < 4; ++b) acc[a][b] = sis_f32x4{0.f, 0.f, 0.f, 0.f};
 
-    auto frag = [&](const unsigned char* st, auto kmajor, const int* off, int rb_bytes, int b, int ks) -> bf16x8 {
+    auto frag = [&](const unsigned char* st, auto kmajor, const int* off, int rb_bytes, int b, int ks) -> sis_bf16x8 {
         if constexpr (!decltype(kmajor)::value) {
-            return *reinterpret_cast<const bf16x8*>(st + off[ks] + b * (16 * C::RROW));
+            return *reinterpret_cast<const sis_bf16x8*>(st + off[ks] + b * (16 * C::RROW));
         } else {
-            const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                (__attribute__((address_space(3))) bf16x4*)(st + off[b * 2] + ks * 32 * rb_bytes));
-            const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                (__attribute__((address_space(3))) bf16x4*)(st + off[b * 2 + 1] + ks * 32 * rb_bytes));
+            const sis_bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+                (__attribute__((address_space(3))) sis_bf16x4*)(st + off[b * 2] + ks * 32 * rb_bytes));
+            const sis_bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+                (__attribute__((address_space(3))) sis_bf16x4*)(st + off[b * 2 + 1] + ks * 32 * rb_bytes));
             return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
         }
     };
@@ -297,7 +291,7 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmParams p) 
     // LDS-DMA holds the wave's issue for tens of cycles -- fall under matrix work instead of in front of it.
     auto step = [&](auto with_dma, int t) {
         const unsigned char* st = lds + stage * C::STAGE;
-        bf16x8 a[C::KSUB][4], b[C::KSUB][C::NBK];
+        sis_bf16x8 a[C::KSUB][4], b[C::KSUB][C::NBK];
 #pragma unroll
         for (int ks = 0; ks < C::KSUB; ++ks) {
 #pragma unroll
@@ -394,7 +388,7 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmParams p) 
                     if (p.drop_thr) sis_drop_quad(key, ((unsigned)m * (unsigned)p.N + (unsigned)n) >> 2, p.drop_thr, p.drop_scale, keep);
                 float v[4] = {acc[tn][tm][0] + bq[tn].x, acc[tn][tm][1] + bq[tn].y, acc[tn][tm][2] + bq[tn].z, acc[tn][tm][3] + bq[tn].w};
                 if constexpr (EPI == SIS_GEMM_EPI_NONE || EPI == SIS_GEMM_EPI_BIAS) {
-                    if (ok) *reinterpret_cast<uint2*>((u16*)Cb + at) = make_uint2(sis_pack_bf16x2(v[0], v[1]), sis_pack_bf16x2(v[2], v[3]));
+                    if (ok) *reinterpret_cast<uint2*>((sis_u16*)Cb + at) = make_uint2(sis_pack_bf16x2(v[0], v[1]), sis_pack_bf16x2(v[2], v[3]));
                 } else if constexpr (EPI == SIS_GEMM_EPI_BIAS_GELU_DROP) {
                     // dropout(gelu(pre)) and, for the backward, d/d pre of it: gelu'(pre) * the same dropout factor (bf16) -- both from
                     // ONE evaluation of the normal cdf / pdf here, so that the data-gradient GEMM's epilogue is a multiplication
@@ -409,8 +403,8 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmParams p) 
                     }
                     const uint2 hp = make_uint2(sis_pack_bf16x2(dd[0], dd[1]), sis_pack_bf16x2(dd[2], dd[3]));
                     if (ok) {
-                        *reinterpret_cast<uint2*>((u16*)p.C2 + at) = hp;
-                        *reinterpret_cast<uint2*>((u16*)Cb + at) = make_uint2(sis_pack_bf16x2(y[0], y[1]), sis_pack_bf16x2(y[2], y[3]));
+                        *reinterpret_cast<uint2*>((sis_u16*)p.C2 + at) = hp;
+                        *reinterpret_cast<uint2*>((sis_u16*)Cb + at) = make_uint2(sis_pack_bf16x2(y[0], y[1]), sis_pack_bf16x2(y[2], y[3]));
                     }
                 } else if constexpr (EPI == SIS_GEMM_EPI_BIAS_DROP_RESID) {
 #pragma unroll
@@ -421,7 +415,7 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_bf16_kernel(GemmParams p) 
                     const float d[4] = {sis_bf16_lo(h[tm].x), sis_bf16_hi(h[tm].x), sis_bf16_lo(h[tm].y), sis_bf16_hi(h[tm].y)};
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] *= d[e];
-                    if (ok) *reinterpret_cast<uint2*>((u16*)Cb + at) = make_uint2(sis_pack_bf16x2(v[0], v[1]), sis_pack_bf16x2(v[2], v[3]));
+                    if (ok) *reinterpret_cast<uint2*>((sis_u16*)Cb + at) = make_uint2(sis_pack_bf16x2(v[0], v[1]), sis_pack_bf16x2(v[2], v[3]));
                 } else {  // SIS_GEMM_EPI_F32: fp32 result or partial slab of a split-K run
                     if (ok) *reinterpret_cast<float4*>((float*)Cb + (long long)split * p.slab_stride + at) = make_float4(v[0], v[1], v[2], v[3]);
                 }
@@ -576,7 +570,7 @@ static int gemm_impl(void* c, void* c2, const void* a, const void* b, int layout
     SIS_REQUIRE(ae * 2 < (1LL << 31) && be * 2 < (1LL << 31), "sis_gemm_bf16: operands above 2 GiB");
     p.a_bytes = (unsigned)(ae * 2); p.b_bytes = (unsigned)(be * 2);
     SIS_REQUIRE(bias_seg == 0 || (bias_seg % 4 == 0 && bias1 && bias2 && n == 3 * bias_seg), "sis_gemm_bf16: three bias segments of n / 3 columns each");
-    p.C = c; p.C2 = c2; p.ldc = ldc; p.bias = bias; p.bias1 = bias1; p.bias2 = bias2; p.bias_seg = bias_seg; p.resid = resid; p.pre = (const u16*)pre;
+    p.C = c; p.C2 = c2; p.ldc = ldc; p.bias = bias; p.bias1 = bias1; p.bias2 = bias2; p.bias_seg = bias_seg; p.resid = resid; p.pre = (const sis_u16*)pre;
     p.seed = (const unsigned long long*)seed; p.site = (unsigned)site;
     p.drop_thr = sis_drop_thr16(drop_p);
     p.drop_scale = sis_drop_scale(p.drop_thr);
@@ -589,7 +583,7 @@ static int gemm_impl(void* c, void* c2, const void* a, const void* b, int layout
         G256Params g;
         g.A = a; g.B = b; g.lda = lda; g.ldb = ldb; g.a_bytes = p.a_bytes; g.b_bytes = p.b_bytes; g.M = m; g.N = n; g.K = k;
         g.C = c; g.C2 = c2; g.ldc = ldc; g.bias = bias; g.bias1 = bias1; g.bias2 = bias2; g.bias_seg = bias_seg; g.resid = resid;
-        g.pre = (const u16*)pre; g.seed = p.seed; g.site = p.site; g.drop_thr = p.drop_thr; g.drop_scale = p.drop_scale;
+        g.pre = (const sis_u16*)pre; g.seed = p.seed; g.site = p.site; g.drop_thr = p.drop_thr; g.drop_scale = p.drop_scale;
         g.m_tiles = g.n_tiles = 0;
         return sis_gemm256_dispatch(g, tile - SIS_GEMM_TILE_256X96 + 1, epilogue, (hipStream_t)stream);
     }

@@ -2,15 +2,9 @@
 // coefficients and the ToRGB / skip accumulation.  None of these is on the MFMA roofline; they
 // are latency- or HBM-bound and written so that each reads its operands exactly once.
 #include <type_traits>
-#include "sis_common.h"
+#include "sis_device.h"
 
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // PixelNorm (model.py:19-20): one wave per row.
 __global__ __launch_bounds__(256) void pixel_norm_kernel(float* __restrict__ out, const float* __restrict__ x,
@@ -21,7 +15,7 @@ __global__ __launch_bounds__(256) void pixel_norm_kernel(float* __restrict__ out
     const float* xr = x + (int64_t)row * dim;
     float ss = 0.f;
     for (int i = lane; i < dim; i += 64) { const float v = xr[i]; ss += v * v; }
-    ss = wave_sum(ss);
+    ss = sis_wave_sum(ss);
     const float r = rsqrtf(ss / (float)dim + 1e-8f);
     for (int i = lane; i < dim; i += 64) out[(int64_t)row * dim + i] = xr[i] * r;
 }
@@ -60,7 +54,7 @@ __global__ __launch_bounds__(256) void equal_linear_kernel(float* __restrict__ o
         }
     }
 #pragma unroll
-    for (int rr = 0; rr < EL_ROWS; ++rr) acc[rr] = wave_sum(acc[rr]);
+    for (int rr = 0; rr < EL_ROWS; ++rr) acc[rr] = sis_wave_sum(acc[rr]);
     if (lane == 0) {
 #pragma unroll
         for (int rr = 0; rr < EL_ROWS; ++rr) {
@@ -104,7 +98,7 @@ __global__ __launch_bounds__(256) void equal_linear_full_kernel(float* __restric
         for (int j = 0; j < NJ; ++j) acc[rr] += xv[rr][j] * wr[j];  // (same order as the general kernel: j ascending)
     }
 #pragma unroll
-    for (int rr = 0; rr < EL_ROWS; ++rr) acc[rr] = wave_sum(acc[rr]);
+    for (int rr = 0; rr < EL_ROWS; ++rr) acc[rr] = sis_wave_sum(acc[rr]);
     if (lane == 0) {
 #pragma unroll
         for (int rr = 0; rr < EL_ROWS; ++rr) {
@@ -127,7 +121,6 @@ __global__ __launch_bounds__(256) void equal_linear_full_kernel(float* __restric
 // (The 8 mapping layers stay on equal_linear_kernel: 32 x 512 x 512 gives this tile shape 4 workgroups and a serial chain
 // of 8 load latencies -- 24 us against 14.)
 constexpr int HG_ROWS = 32, HG_COLS = 128, HG_KC = 64, HG_LD = 66;
-typedef __attribute__((ext_vector_type(16))) float hg_f32x16;
 
 struct HeadArgs {
     // MODE 0 (EqualLinear): a/w/bias/out direct.  MODE 1 (modulation) / 2 (demodulation): table rows, see the launchers.
@@ -174,7 +167,7 @@ __global__ __launch_bounds__(256) void head_gemm_kernel(const HeadArgs h) {
         }
         return;
     }
-    hg_f32x16 acc;
+    sis_f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     const int srow = tid >> 3, sk = (tid & 7) * 8;  // staging: 8 consecutive k of one row per thread and pass
@@ -308,7 +301,7 @@ __global__ __launch_bounds__(256) void demod_kernel(float* __restrict__ dscale, 
     const float* wr = wsq + (int64_t)co * cin;
     float acc = 0.f;
     for (int i = lane; i < cin; i += 64) { const float sv = sr[i] * scale; acc += sv * sv * wr[i]; }
-    acc = wave_sum(acc);
+    acc = sis_wave_sum(acc);
     if (lane == 0) dscale[idx] = scale * rsqrtf(acc + 1e-8f);
 }
 

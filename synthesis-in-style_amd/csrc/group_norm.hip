@@ -12,53 +12,21 @@
 // workgroup adds the plane sums over the batch in fixed order: d(gamma) / d(beta).  (Batch-norm mode and callers without a
 // counter buffer keep the merge as a launch of its own.)
 #include <cstdlib>
-#include "sis_common.h"
+#include "sis_device.h"
 #include "sis_xwg.h"
 
 namespace {
 
-__device__ __forceinline__ float gn_block_sum(float v, float* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// VEC consecutive elements as floats: one 16-byte (f32) or 8-byte (f16 / bf16) load when VEC == 4
+// VEC (4 or 1) consecutive elements as floats
 template <int VEC, typename T>
 __device__ __forceinline__ void gn_load(const T* p, float* v) {
-    if constexpr (VEC == 4 && sizeof(T) == 4) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else if constexpr (VEC == 4 && sizeof(T) == 2) {
-        const uint2 q = *reinterpret_cast<const uint2*>(p);
-        T t[4];
-        __builtin_memcpy(t, &q, 8);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = sis_ld(t, e);
-    } else {
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) v[e] = sis_ld(p, e);
-    }
+    if constexpr (VEC == 4) sis_load4(p, v);
+    else v[0] = sis_ld(p, 0);
 }
-
 template <int VEC, typename T>
 __device__ __forceinline__ void gn_store(T* p, const float* v) {
-    if constexpr (VEC == 4 && sizeof(T) == 4) {
-        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    } else if constexpr (VEC == 4 && sizeof(T) == 2) {
-        T t[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) sis_st(t, e, v[e]);
-        uint2 q;
-        __builtin_memcpy(&q, t, 8);
-        *reinterpret_cast<uint2*>(p) = q;
-    } else {
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) sis_st(p, e, v[e]);
-    }
+    if constexpr (VEC == 4) sis_store4(p, v);
+    else sis_st(p, 0, v[0]);
 }
 
 // Elements [lo, hi) of a plane whose first element sits at flat offset `base` of a vector-aligned tensor: scalar head up
@@ -114,7 +82,7 @@ __global__ __launch_bounds__(256) void gn_plane_stats_kernel(float* __restrict__
         for (int e = 0; e < VEC; ++e) s += v[e];
     });
     const float cnt = (float)(hi - lo);
-    const float mean = gn_block_sum(s, red) / cnt;
+    const float mean = sis_block_sum4(s, red) / cnt;
     float m2 = 0.f;
     gn_span<VEC>(base, lo, hi, [&](int i) { const float d = sis_ld(pl, i) - mean; m2 += d * d; }, [&](int i) {
         float v[VEC];
@@ -122,7 +90,7 @@ __global__ __launch_bounds__(256) void gn_plane_stats_kernel(float* __restrict__
 #pragma unroll
         for (int e = 0; e < VEC; ++e) { const float d = v[e] - mean; m2 += d * d; }
     });
-    m2 = gn_block_sum(m2, red);
+    m2 = sis_block_sum4(m2, red);
     if (threadIdx.x == 0) {
         float* o = part + 3 * ((int64_t)blockIdx.x * gridDim.y + blockIdx.y);
         xwg_publish(o, cnt); xwg_publish(o + 1, mean); xwg_publish(o + 2, m2);
@@ -341,8 +309,8 @@ __global__ __launch_bounds__(256) void gn_bwd_plane_kernel(float* __restrict__ p
 #pragma unroll
         for (int e = 0; e < VEC; ++e) one(xv[e], gv[e] + (pg2 ? g2[e] : 0.f), gated ? mv[e] : 1.f);
     });
-    sg = gn_block_sum(sg, red);
-    sgx = gn_block_sum(sgx, red);
+    sg = sis_block_sum4(sg, red);
+    sgx = sis_block_sum4(sgx, red);
     if (threadIdx.x == 0) {
         float* o = part + 2 * (plane * gridDim.y + blockIdx.y);
         xwg_publish(o, sg); xwg_publish(o + 1, sgx);
@@ -527,44 +495,6 @@ struct GnGroupArgs {
     int hw, cpg, groups, relu; float eps;
 };
 
-template <typename TI>
-__device__ __forceinline__ void gn_load8(const TI* p, float* v) {   // 8 consecutive 16-bit elements: one 16-byte load
-    const uint4 q = *reinterpret_cast<const uint4*>(p);
-    TI t[8];
-    __builtin_memcpy(t, &q, 16);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = sis_ld(t, e);
-}
-template <typename TI>
-__device__ __forceinline__ void gn_store8(TI* p, const float* v) {
-    TI t[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) sis_st(t, e, v[e]);
-    uint4 q;
-    __builtin_memcpy(&q, t, 16);
-    *reinterpret_cast<uint4*>(p) = q;
-}
-__device__ __forceinline__ void gn_load8(const float* p, float* v) {
-    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-__device__ __forceinline__ void gn_store8(float* p, const float* v) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
-}
-
-// sum over the workgroup (<= 16 waves), the same value in every thread
-__device__ __forceinline__ float gn_group_sum(float v, float* red, int nw) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = 0.f;
-    for (int w = 0; w < nw; ++w) s += red[w];
-    return s;
-}
-
 template <typename TI, typename TO, int NIT>
 __global__ __launch_bounds__(1024) void gn_group_fwd_kernel(TO* __restrict__ y, TI* __restrict__ y_lp, float* __restrict__ mean_out,
                                                             float* __restrict__ rstd_out, const TI* __restrict__ x,
@@ -579,18 +509,18 @@ __global__ __launch_bounds__(1024) void gn_group_fwd_kernel(TO* __restrict__ y, 
     float s = 0.f;
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
-        gn_load8(x + base + 8 * (int64_t)(v0 + it * 64), xv[it]);
+        sis_load8(x + base + 8 * (int64_t)(v0 + it * 64), xv[it]);
 #pragma unroll
         for (int e = 0; e < 8; ++e) s += xv[it][e];
     }
     const float n = (float)a.cpg * (float)a.hw;
-    const float mean = gn_group_sum(s, red, nw) / n;
+    const float mean = sis_block_sum_waves(s, red, nw) / n;
     float m2 = 0.f;
 #pragma unroll
     for (int it = 0; it < NIT; ++it)
 #pragma unroll
         for (int e = 0; e < 8; ++e) { const float d = xv[it][e] - mean; m2 += d * d; }
-    const float rstd = rsqrtf(gn_group_sum(m2, red, nw) / n + a.eps);
+    const float rstd = rsqrtf(sis_block_sum_waves(m2, red, nw) / n + a.eps);
     if (threadIdx.x == 0) { mean_out[row] = mean; rstd_out[row] = rstd; }
     const int c0 = (row % a.groups) * a.cpg;
 #pragma unroll
@@ -599,7 +529,7 @@ __global__ __launch_bounds__(1024) void gn_group_fwd_kernel(TO* __restrict__ y, 
         const int c = c0 + (int)(off / a.hw);
         const float ga = rstd * gamma[c], gb = beta[c] - mean * ga;
         float rv[8], out[8];
-        if (res) gn_load8(res + base + off, rv);
+        if (res) sis_load8(res + base + off, rv);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             float v = xv[it][e] * ga + gb;
@@ -607,8 +537,8 @@ __global__ __launch_bounds__(1024) void gn_group_fwd_kernel(TO* __restrict__ y, 
             if (a.relu) v = fmaxf(v, 0.f);
             out[e] = v;
         }
-        gn_store8(y + base + off, out);
-        if (y_lp) gn_store8(y_lp + base + off, out);
+        sis_store8(y + base + off, out);
+        if (y_lp) sis_store8(y_lp + base + off, out);
         if (bits) {   // this lane's 8 elements are one byte of the gate bits
             unsigned byte = 0;
 #pragma unroll
@@ -642,16 +572,16 @@ __global__ __launch_bounds__(1024) void gn_group_bwd_kernel(TI* __restrict__ dx,
         const int64_t off = 8 * (int64_t)(v0 + it * 64);
         const int c = c0 + (int)(off / a.hw);
         float xv[8], g2[8], mv[8];
-        gn_load8(x + base + off, xv);
-        gn_load8(g + base + off, gi[it]);
-        if (HAS_LP) gn_load8(g_lp + base + off, g2);
+        sis_load8(x + base + off, xv);
+        sis_load8(g + base + off, gi[it]);
+        if (HAS_LP) sis_load8(g_lp + base + off, g2);
         if (HAS_MASK) {
             if (bits) {
                 const unsigned byte = bits[(base + off) >> 3];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) mv[e] = (float)((byte >> e) & 1u);
             } else {
-                gn_load8(ymask + base + off, mv);
+                sis_load8(ymask + base + off, mv);
             }
         }
         const float gm = gamma[c], bt = beta[c];
@@ -691,8 +621,8 @@ __global__ __launch_bounds__(1024) void gn_group_bwd_kernel(TI* __restrict__ dx,
         float out[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) out[e] = k1 * gi[it][e] - k2 - k3 * xh[it][e];
-        gn_store8(dx + base + off, out);
-        if (HAS_MASK && dres) gn_store8(dres + base + off, gi[it]);
+        sis_store8(dx + base + off, out);
+        if (HAS_MASK && dres) sis_store8(dres + base + off, gi[it]);
     }
     // d gamma / d beta: the last workgroup of the launch adds the plane sums over the batch (counter == nullptr: launches of
     // thousands of workgroups leave that to gn_param_reduce_kernel -- see gn_bwd_run)

@@ -11,38 +11,6 @@
 
 namespace {
 
-template <typename T>
-__device__ __forceinline__ void ln_load4(const T* p, float* v) {
-    if constexpr (sizeof(T) == 4) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-        const uint2 q = *reinterpret_cast<const uint2*>(p);
-        T t[4];
-        __builtin_memcpy(t, &q, 8);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = sis_ld(t, e);
-    }
-}
-template <typename T>
-__device__ __forceinline__ void ln_store4(T* p, const float* v) {
-    if constexpr (sizeof(T) == 4) {
-        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-        T t[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) sis_st(t, e, v[e]);
-        uint2 q;
-        __builtin_memcpy(&q, t, 8);
-        *reinterpret_cast<uint2*>(p) = q;
-    }
-}
-__device__ __forceinline__ float ln_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 template <typename TI, typename TO, int NJ>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(TO* __restrict__ y, float* __restrict__ mean_out,
                                                      float* __restrict__ rstd_out, const TI* __restrict__ x,
@@ -57,16 +25,16 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(TO* __restrict__ y, float* 
     float s = 0.f;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-        ln_load4(xr + 4 * (lane + 64 * j), v[j]);
+        sis_load4(xr + 4 * (lane + 64 * j), v[j]);
         s += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
     }
-    const float mean = ln_wave_sum(s) / (float)N;
+    const float mean = sis_wave_sum(s) / (float)N;
     float m2 = 0.f;
 #pragma unroll
     for (int j = 0; j < NJ; ++j)
 #pragma unroll
         for (int e = 0; e < 4; ++e) { const float d = v[j][e] - mean; m2 += d * d; }
-    const float rstd = rsqrtf(ln_wave_sum(m2) / (float)N + eps);
+    const float rstd = rsqrtf(sis_wave_sum(m2) / (float)N + eps);
     if (lane == 0) { mean_out[row] = mean; rstd_out[row] = rstd; }
     TO* yr = y + (int64_t)row * N;
 #pragma unroll
@@ -75,7 +43,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(TO* __restrict__ y, float* 
         const float4 g = *reinterpret_cast<const float4*>(gamma + c), b = *reinterpret_cast<const float4*>(beta + c);
         float o[4] = {(v[j][0] - mean) * rstd * g.x + b.x, (v[j][1] - mean) * rstd * g.y + b.y,
                       (v[j][2] - mean) * rstd * g.z + b.z, (v[j][3] - mean) * rstd * g.w + b.w};
-        ln_store4(yr + c, o);
+        sis_store4(yr + c, o);
     }
 }
 
@@ -111,8 +79,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(TI* __restrict__ dx, float*
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
-            ln_load4(xr + 4 * (lane + 64 * j), xh[j]);
-            ln_load4(gr + 4 * (lane + 64 * j), gv[j]);
+            sis_load4(xr + 4 * (lane + 64 * j), xh[j]);
+            sis_load4(gr + 4 * (lane + 64 * j), gv[j]);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 xh[j][e] = (xh[j][e] - mean) * rstd;
@@ -122,7 +90,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(TI* __restrict__ dx, float*
                 s1 += gv[j][e]; s2 += gv[j][e] * xh[j][e];
             }
         }
-        const float m1 = ln_wave_sum(s1) / (float)N, m2 = ln_wave_sum(s2) / (float)N;
+        const float m1 = sis_wave_sum(s1) / (float)N, m2 = sis_wave_sum(s2) / (float)N;
         TI* dr = dx + (int64_t)row * N;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
@@ -134,7 +102,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(TI* __restrict__ dx, float*
                 const float4 r = *reinterpret_cast<const float4*>(ex.radd + (int64_t)row * N + col);
                 o[0] += r.x; o[1] += r.y; o[2] += r.z; o[3] += r.w;
             }
-            ln_store4(dr + col, o);
+            sis_store4(dr + col, o);
             if (ex.cast_out) {
                 float f[4] = {o[0], o[1], o[2], o[3]};
                 if (ex.thr) {

@@ -13,7 +13,7 @@
 //     a_c = -2 / (C (D_c + s)),  b_c = 2 (2 I_c + s) / (C (D_c + s)^2),  I = sum p t, D = sum p^2 + sum t.
 // Labels outside [0, C) count as "ignore" for the cross entropy (nn.CrossEntropyLoss's ignore_index) and as an all-zero
 // one-hot row for the Dice term (what the reference's comparison against the class ids produces).
-#include "sis_common.h"
+#include "sis_device.h"
 
 namespace {
 
@@ -21,6 +21,8 @@ constexpr int LOSS_MAXC = 8;
 constexpr int LOSS_BLOCKS = 512;
 constexpr float DICE_SMOOTH = 1e-5f;
 
+// The 16-bit element type of these kernels is unsigned short holding bf16 BITS (it is in the kernels' names), so the quads
+// are converted by bit operations here, not by sis_load4 / sis_store4, which go by the element's C++ type.
 template <typename T>
 __device__ __forceinline__ void load_quad(const T* p, float* v) {
     if constexpr (sizeof(T) == 4) {
@@ -37,8 +39,7 @@ __device__ __forceinline__ void store_quad(T* p, const float* v) {
     if constexpr (sizeof(T) == 4) {
         *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
     } else {
-        typedef __attribute__((ext_vector_type(2))) __bf16 b2;
-        const b2 lo = {(__bf16)v[0], (__bf16)v[1]}, hi = {(__bf16)v[2], (__bf16)v[3]};
+        const sis_bf16x2 lo = {(__bf16)v[0], (__bf16)v[1]}, hi = {(__bf16)v[2], (__bf16)v[3]};
         *reinterpret_cast<uint2*>(p) = make_uint2(__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi));
     }
 }
@@ -94,7 +95,7 @@ __global__ __launch_bounds__(256) void ce_dice_fwd_kernel(float* __restrict__ pa
     for (int i = 0; i < NV; ++i) {
         float v = acc[i];
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);   // written out: a call of sis_wave_sum here changes the generated code
         if (lane == 0) red[wave][i] = v;
     }
     __syncthreads();

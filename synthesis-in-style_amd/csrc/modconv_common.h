@@ -1,9 +1,7 @@
 // Shared between the two modulated-convolution kernels (modconv_mfma.hip: register-staged, any shape;
 // modconv_mfma2.hip: LDS-DMA double-buffered fast path).
 #pragma once
-#include "sis_common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "sis_device.h"
 
 constexpr int MC_MAX_CLS = 4;
 constexpr int MC_XI = 3;  // staged x elements per lane per channel (covers xt <= 768)

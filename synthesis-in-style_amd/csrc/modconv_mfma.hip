@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256, 2) void modconv_mfma_kernel(const ConvParams p
     }
     const int aoff = half * C::NTAPS * C::MBLK + wm * 64 + l31;
 
-    f32x16 acc[C::MT][C::NACC];
+    sis_f32x16 acc[C::MT][C::NACC];
 #pragma unroll
     for (int m = 0; m < C::MT; ++m)
 #pragma unroll

@@ -46,19 +46,9 @@ struct V2Cfg {
     static constexpr int XI = (512 + THREADS - 1) / THREADS;  // float4 chunks per lane per channel (xt <= 2048)
 };
 
-__device__ __forceinline__ void glds16(const float* g, float* l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
 // LDS-DMA through a buffer descriptor (see modconv_wino.hip): per-lane byte offset in a VGPR, wave-uniform offset in an
 // SGPR -- the per-chunk address arithmetic is scalar -- and out-of-range lanes get zeros written to their LDS slot.
 constexpr unsigned BUF_OOB = 0x80000000u;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t dma_rsrc(const float* base) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0x7FFFFFFF, 0x00020000);
-}
-__device__ __forceinline__ void bufld16(__amdgpu_buffer_rsrc_t r, float* l, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)l, 16, voff, soff, 0, 0);
-}
 
 #ifdef SIS_V2_TRACE
 // Development build only (tools/v2_trace.py): cycle stamps of the chunk loop of 4 workgroups of the transposed kernel.
@@ -187,8 +177,8 @@ __global__ __launch_bounds__(C::THREADS, C::OCC) void modconv_v2_kernel(const Co
         const int b = b0 + n, h = h0 - C::PAD_LO + r, w = w0 - LP + 4 * c4;
         if (b < p.B && h >= 0 && h < p.H && w >= 0 && w < p.W) x_voff = (unsigned)(n * p.Cin * HW + h * p.W + w) * 4u;
     }
-    const __amdgpu_buffer_rsrc_t x_rsrc = dma_rsrc(p.x + (int64_t)b0 * p.Cin * HW);
-    const __amdgpu_buffer_rsrc_t w_rsrc = dma_rsrc(p.wpk + o0);
+    const __amdgpu_buffer_rsrc_t x_rsrc = sis_buffer_rsrc(p.x + (int64_t)b0 * p.Cin * HW);
+    const __amdgpu_buffer_rsrc_t w_rsrc = sis_buffer_rsrc(p.wpk + o0);
     constexpr int WROW4 = C::MBLK / 4;  // float4 per weight row
     static_assert(!BUF || ((C::CC * C::NTAPS * C::MBLK / 4) % 64 == 0 && NTHR % WROW4 == 0), "weight chunk must split into whole waves / rows");
     const unsigned w_voff = (o0 + (tid % WROW4) * 4 < p.Cout) ? (unsigned)((tid / WROW4) * p.Cout + (tid % WROW4) * 4) * 4u : BUF_OOB;
@@ -197,10 +187,10 @@ __global__ __launch_bounds__(C::THREADS, C::OCC) void modconv_v2_kernel(const Co
 #pragma unroll
         for (int it = 0; it < WIT; ++it)
             if (it * NTHR + wbase < WV4)  // wave-uniform (WV4 % 64 == 0)
-                bufld16(w_rsrc, wdst + it * NTHR * 4, w_voff, (unsigned)((ci0 * C::NTAPS + it * (NTHR / WROW4)) * p.Cout) * 4u);
+                sis_buffer_load_lds16(w_rsrc, wdst + it * NTHR * 4, w_voff, (unsigned)((ci0 * C::NTAPS + it * (NTHR / WROW4)) * p.Cout) * 4u);
         float* xdst = Xl + buf * CC * xt + x_part * 256;
         if (x_lane) {
-            for (int j = x_ch0; j < CC; j += x_chstep) bufld16(x_rsrc, xdst + j * xt, x_voff, (unsigned)((ci0 + j) * HW) * 4u);
+            for (int j = x_ch0; j < CC; j += x_chstep) sis_buffer_load_lds16(x_rsrc, xdst + j * xt, x_voff, (unsigned)((ci0 + j) * HW) * 4u);
         }
     };
     auto stage = [&](int ci0, int buf) {
@@ -209,14 +199,14 @@ __global__ __launch_bounds__(C::THREADS, C::OCC) void modconv_v2_kernel(const Co
         float* wdst = Wl + buf * WF + wbase * 4;
 #pragma unroll
         for (int it = 0; it < WIT; ++it)
-            if (w_goff[it] >= 0) glds16(wsrc + w_goff[it], wdst + it * NTHR * 4);
+            if (w_goff[it] >= 0) sis_global_load_lds16(wsrc + w_goff[it], wdst + it * NTHR * 4);
         const float* xsrc = p.x + (int64_t)ci0 * HW;
         float* xdst = Xl + buf * CC * xt + wbase * 4;
 #pragma unroll
         for (int j = 0; j < CC; ++j)
 #pragma unroll
             for (int i = 0; i < XI; ++i)
-                if (st_goff[i] >= 0) glds16(xsrc + st_goff[i] + j * HW, xdst + j * xt + i * NTHR * 4);
+                if (st_goff[i] >= 0) sis_global_load_lds16(xsrc + st_goff[i] + j * HW, xdst + j * xt + i * NTHR * 4);
     };
 
     // ---- per-lane operand offsets
@@ -235,7 +225,7 @@ __global__ __launch_bounds__(C::THREADS, C::OCC) void modconv_v2_kernel(const Co
     // matrix pipe of its SIMD goes to the other workgroup on the CU (edge tiles are 5 % of the 64x64 layer, 27 % of 16x16).
     const bool wave_live = MODE == 0 || ((wn * 32) >> (thl + twl)) < tc.nb;
 
-    f32x16 acc[C::MT][C::NACC];
+    sis_f32x16 acc[C::MT][C::NACC];
 #pragma unroll
     for (int m = 0; m < C::MT; ++m)
 #pragma unroll

@@ -45,8 +45,6 @@
 
 namespace {
 
-typedef float uf_f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int UF_MBLK = 64;                           // output channels per workgroup
 // NW = waves per workgroup (8 or 4): NW input channels per chunk (one channel's DMA per wave) and 8 NW position blocks per
 // workgroup.  NW = 4 halves the tile and the chunk (46 - 52 KB of LDS): TWO workgroups share a CU, one wave of each per SIMD, and
@@ -66,10 +64,6 @@ struct UpFirParams {
     int rw4;                       // float4 per staged row = W / 4 + 2
     int xs;                        // floats per channel of the staged tile (multiple of 256)
 };
-
-__device__ __forceinline__ void uf_dma16(__amdgpu_buffer_rsrc_t r, float* l, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)l, 16, voff, soff, 0, 0);
-}
 
 // ABL: timing ablations for development builds (tools/bench_upfir.py, SIS_UPFIR_ABL): bit 0 no barrier in the chunk loop, bit 1 no
 // DMA in the loop, bit 2 no patch reads / transform in the loop, bit 3 no weight-fragment reads in the loop.  Any non-zero value
@@ -110,8 +104,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
 
     // ---- DMA plan.  Weights: wave w moves channel ci0 + w, piece q = planes 4 q .. 4 q + 3 (lane >> 4) x 64 channels.
     // Input: wave w moves channel ci0 + w, piece q = float4 q * 64 + lane of the [rows][rw4] tile.
-    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.u + 2 * o0), 0, 0x7FFFFFFF, 0x00020000);
-    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, 0x7FFFFFFF, 0x00020000);
+    const __amdgpu_buffer_rsrc_t w_rsrc = sis_buffer_rsrc(p.u + 2 * o0);
+    const __amdgpu_buffer_rsrc_t x_rsrc = sis_buffer_rsrc(p.x);
     // weight image of a channel: [plane pair 0..7][co][2 planes]; a 1 KiB piece = two pairs x 64 channels x 2
     const unsigned w_voff = (unsigned)(((lane >> 5) * p.Cout * 2 + (lane & 31) * 4) * 4);
     const int xpieces = p.xs >> 8;
@@ -129,21 +123,21 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
         float* wdst = Wl + (buf * UF_CC + wave) * UF_WROW;
         const unsigned wbase = (unsigned)((ci0 + wave) * UF_PLANES * p.Cout * 4);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) uf_dma16(w_rsrc, wdst + q * 256, w_voff, wbase + (unsigned)(q * 2 * p.Cout * 2 * 4));
+        for (int q = 0; q < 4; ++q) sis_buffer_load_lds16(w_rsrc, wdst + q * 256, w_voff, wbase + (unsigned)(q * 2 * p.Cout * 2 * 4));
         float* xdst = Xl + (buf * UF_CC + wave) * p.xs;
         const unsigned xbase = (unsigned)((ci0 + wave) * HW * 4);
 #pragma unroll
         for (int q = 0; q < UF_XP_MAX; ++q)
-            if (q < xpieces) uf_dma16(x_rsrc, xdst + q * 256, x_voff[q], xbase);   // (wave-uniform)
+            if (q < xpieces) sis_buffer_load_lds16(x_rsrc, xdst + q * 256, x_voff[q], xbase);   // (wave-uniform)
     };
 
-    uf_f32x4 acc[5][5][2];
+    sis_f32x4 acc[5][5][2];
 #pragma unroll
     for (int a = 0; a < 5; ++a)
 #pragma unroll
         for (int c = 0; c < 5; ++c)
 #pragma unroll
-            for (int t = 0; t < 2; ++t) acc[a][c][t] = uf_f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int t = 0; t < 2; ++t) acc[a][c][t] = sis_f32x4{0.f, 0.f, 0.f, 0.f};
 
     __syncthreads();   // style rows
     stage(0, 0);
@@ -189,25 +183,24 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
         for (int r = 0; r < 3; ++r) tr_col(r, tA);
         tr_row(tA);
-        typedef float f2 __attribute__((ext_vector_type(2)));
         const int woff = kq * UF_WROW + (wm * 32 + l15) * 2;
         // ring of three fragment pairs, carried from chunk to chunk: pair 0 of chunk c + 1 takes pair 6's slot once that is used up
-        f2 ra[3][2];
-        ra[0][0] = *reinterpret_cast<const f2*>(Wl + woff); ra[0][1] = *reinterpret_cast<const f2*>(Wl + woff + 32);
+        sis_f32x2 ra[3][2];
+        ra[0][0] = *reinterpret_cast<const sis_f32x2*>(Wl + woff); ra[0][1] = *reinterpret_cast<const sis_f32x2*>(Wl + woff + 32);
         auto chunk = [&](auto parity, int c, const float (&t)[4][4], float (&tn)[4][4]) {
             constexpr int B = decltype(parity)::value;
             const float* wb = Wl + B * UF_CC * UF_WROW + woff;
             auto fetch = [&](int k) {
-                ra[k % 3][0] = *reinterpret_cast<const f2*>(wb + k * 2 * UF_MBLK);
-                ra[k % 3][1] = *reinterpret_cast<const f2*>(wb + k * 2 * UF_MBLK + 32);
+                ra[k % 3][0] = *reinterpret_cast<const sis_f32x2*>(wb + k * 2 * UF_MBLK);
+                ra[k % 3][1] = *reinterpret_cast<const sis_f32x2*>(wb + k * 2 * UF_MBLK + 32);
             };
             fetch(1);
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 if (k + 2 < 8) fetch(k + 2);
                 if (k == 7) {   // (behind the barrier: chunk c + 1 has landed)
-                    ra[0][0] = *reinterpret_cast<const f2*>(Wl + (B ^ 1) * UF_CC * UF_WROW + woff);
-                    ra[0][1] = *reinterpret_cast<const f2*>(Wl + (B ^ 1) * UF_CC * UF_WROW + woff + 32);
+                    ra[0][0] = *reinterpret_cast<const sis_f32x2*>(Wl + (B ^ 1) * UF_CC * UF_WROW + woff);
+                    ra[0][1] = *reinterpret_cast<const sis_f32x2*>(Wl + (B ^ 1) * UF_CC * UF_WROW + woff + 32);
                 }
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
@@ -287,15 +280,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
         // itself the compiler reads each pair right in front of its MFMAs and waits for it -- 32 exposed LDS latencies per chunk).
         auto multiply = [&](int ks, const float (&t)[4][4]) {
             // A fragments: one ds_read2_b64 per PAIR of planes (u, 2 h) / (u, 2 h + 1) delivers both planes for both channel tiles
-            typedef float f2 __attribute__((ext_vector_type(2)));
             const float* wb = Wb + (4 * ks + kq) * UF_WROW + (wm * 32 + l15) * 2;
-            f2 ra[3][2];   // ring of three pairs x two channel tiles
+            sis_f32x2 ra[3][2];   // ring of three pairs x two channel tiles
             auto fetch = [&](int k) {
                 if constexpr (ABL & 8) {
-                    ra[k % 3][0] = f2{(float)(k + lane), (float)(k - lane)}; ra[k % 3][1] = f2{(float)lane, (float)k};
+                    ra[k % 3][0] = sis_f32x2{(float)(k + lane), (float)(k - lane)}; ra[k % 3][1] = sis_f32x2{(float)lane, (float)k};
                 } else {
-                    ra[k % 3][0] = *reinterpret_cast<const f2*>(wb + k * 2 * UF_MBLK);
-                    ra[k % 3][1] = *reinterpret_cast<const f2*>(wb + k * 2 * UF_MBLK + 32);
+                    ra[k % 3][0] = *reinterpret_cast<const sis_f32x2*>(wb + k * 2 * UF_MBLK);
+                    ra[k % 3][1] = *reinterpret_cast<const sis_f32x2*>(wb + k * 2 * UF_MBLK + 32);
                 }
             };
             if constexpr (PIPE >= 1) { fetch(0); fetch(1); }
@@ -405,7 +397,6 @@ constexpr int UE_KC = 64;                             // channels per chunk of t
 template <bool ROWK, int NWV>
 __device__ __forceinline__ void upfir_edge_tile(const UpFirParams& p, int tile, int cgb, float4* Dl) {
     constexpr int CSTEP = 4 * NWV, NR = UE_KC / CSTEP;  // staging: thread = (block tid & 15, channel (tid >> 4) + k CSTEP), k < NR
-    typedef float f2 __attribute__((ext_vector_type(2)));
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, kq = lane >> 4, sc = tid >> 4;
     const int co0 = (cgb * NWV + wave) * 16;
@@ -449,7 +440,7 @@ __device__ __forceinline__ void upfir_edge_tile(const UpFirParams& p, int tile, 
         for (int k = 0; k < 16; ++k) {
             const float* uc = p.u + (int64_t)min(c0 + 4 * k, p.Cin - 4) * UF_PLANES * p.Cout;   // (wave-uniform)
             if constexpr (ROWK) {     // planes (0, 0 .. 3): pairs 0 and 1
-                const f2 w0 = *reinterpret_cast<const f2*>(uc + uo), w1 = *reinterpret_cast<const f2*>(uc + 2 * p.Cout + uo);
+                const sis_f32x2 w0 = *reinterpret_cast<const sis_f32x2*>(uc + uo), w1 = *reinterpret_cast<const sis_f32x2*>(uc + 2 * p.Cout + uo);
                 w[k][0] = w0[0]; w[k][1] = w0[1]; w[k][2] = w1[0]; w[k][3] = w1[1];
             } else {                  // planes (0 .. 3, 0): first plane of pairs 0, 2, 4, 6
 #pragma unroll
@@ -458,9 +449,9 @@ __device__ __forceinline__ void upfir_edge_tile(const UpFirParams& p, int tile, 
         }
     };
 
-    uf_f32x4 acc[5];
+    sis_f32x4 acc[5];
 #pragma unroll
-    for (int a = 0; a < 5; ++a) acc[a] = uf_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int a = 0; a < 5; ++a) acc[a] = sis_f32x4{0.f, 0.f, 0.f, 0.f};
     float wc[16][4], wn[16][4];
     load_patch(0);
     load_w(0, wc);

@@ -41,20 +41,14 @@ constexpr int S_BAR = SIS_WINO_BAR_SLOT;  // MFMA slot of a chunk behind which i
 constexpr int WMBLK = 64;   // output channels per workgroup
 constexpr int WTILES = 64;  // 2x2 output tiles per workgroup (256 pixels)
 
-__device__ __forceinline__ void glds16(const float* g, float* l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
 // 8-byte LDS read of two adjacent floats, typed as double on purpose: the compiler's wait-count pass puts
 // s_waitcnt vmcnt(0) in front of every LDS read it thinks may alias an in-flight LDS-DMA write, and type-based alias
 // info is what tells it otherwise -- float2 (a struct) aliases everything, which stalled every chunk on the DMA it
 // had just issued; float and double reads do not.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 lds_ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }  // ds_read_b128, typed like lds_ld2
-__device__ __forceinline__ void lds_st4(float* p, f32x2 a, f32x2 b) { *reinterpret_cast<f32x4*>(p) = f32x4{a.x, a.y, b.x, b.y}; }
+__device__ __forceinline__ sis_f32x4 lds_ld4(const float* p) { return *reinterpret_cast<const sis_f32x4*>(p); }  // ds_read_b128, typed like lds_ld2
+__device__ __forceinline__ void lds_st4(float* p, sis_f32x2 a, sis_f32x2 b) { *reinterpret_cast<sis_f32x4*>(p) = sis_f32x4{a.x, a.y, b.x, b.y}; }
 __device__ __forceinline__ float2 lds_ld2(const float* p) {
-    const f32x2 d = *reinterpret_cast<const f32x2*>(p);
+    const sis_f32x2 d = *reinterpret_cast<const sis_f32x2*>(p);
     return make_float2(d.x, d.y);
 }
 // LDS-DMA through a buffer descriptor: address = descriptor base + per-lane byte offset (VGPR) + wave-uniform byte
@@ -62,47 +56,37 @@ __device__ __forceinline__ float2 lds_ld2(const float* p) {
 // throttles to one instruction per ~10 cycles), and a lane whose offset is >= num_records gets ZEROS written to its
 // LDS slot (tools/micro/buffer_lds_oob.hip): image halos and partial blocks need neither exec masks nor a zero fill.
 constexpr unsigned BUF_OOB = 0x80000000u;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t dma_rsrc(const float* base) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0x7FFFFFFF, 0x00020000);
-}
-__device__ __forceinline__ void bufld16(__amdgpu_buffer_rsrc_t r, float* l, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)l, 16, voff, soff, 0, 0);
-}
 // Packed fp32 VALU (two lanes of work per instruction), written as assembly because the compiler splits v2f32 arithmetic
 // back into scalar instructions.  np = (-1, 1).
-__device__ __forceinline__ f32x2 pk_lo_np_plus(f32x2 y, f32x2 np, f32x2 x) {  // (x.lo - y.lo, x.hi + y.lo)
-    f32x2 r;
+__device__ __forceinline__ sis_f32x2 pk_lo_np_plus(sis_f32x2 y, sis_f32x2 np, sis_f32x2 x) {  // (x.lo - y.lo, x.hi + y.lo)
+    sis_f32x2 r;
     asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1]" : "=v"(r) : "v"(y), "v"(np), "v"(x));
     return r;
 }
-__device__ __forceinline__ f32x2 pk_hi_np_cross(f32x2 x, f32x2 np, f32x2 y) {  // (y.lo - x.hi, x.hi - y.hi)
-    f32x2 r;
+__device__ __forceinline__ sis_f32x2 pk_hi_np_cross(sis_f32x2 x, sis_f32x2 np, sis_f32x2 y) {  // (y.lo - x.hi, x.hi - y.hi)
+    sis_f32x2 r;
     asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,1,1] neg_hi:[0,0,1]" : "=v"(r) : "v"(x), "v"(np), "v"(y));
     return r;
 }
-__device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {
-    f32x2 r;
+__device__ __forceinline__ sis_f32x2 pk_add(sis_f32x2 a, sis_f32x2 b) {
+    sis_f32x2 r;
     asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
-__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
-    f32x2 r;
+__device__ __forceinline__ sis_f32x2 pk_sub(sis_f32x2 a, sis_f32x2 b) {
+    sis_f32x2 r;
     asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
-__device__ __forceinline__ f32x2 pk_neg_sub(f32x2 a, f32x2 b) {  // -a - b
-    f32x2 r;
+__device__ __forceinline__ sis_f32x2 pk_neg_sub(sis_f32x2 a, sis_f32x2 b) {  // -a - b
+    sis_f32x2 r;
     asm("v_pk_add_f32 %0, %1, %2 neg_lo:[1,1] neg_hi:[1,1]" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
-__device__ __forceinline__ f32x2 pk_scale(f32x2 a, f32x2 s_lo) {  // a * s_lo.lo
-    f32x2 r;
+__device__ __forceinline__ sis_f32x2 pk_scale(sis_f32x2 a, sis_f32x2 s_lo) {  // a * s_lo.lo
+    sis_f32x2 r;
     asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(r) : "v"(a), "v"(s_lo));
     return r;
-}
-__device__ __forceinline__ void glds4(const float* g, float* l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)l, 4, 0, 0);
 }
 
 // u[ci][q][ih][co][il][jj] (xi = 4 (2 ih + il) + 2 q + jj) from w[co][ci][3][3]
@@ -293,12 +277,12 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino_kernel(const ConvParams
         float* udst = Ul + buf * WF + wbase * 4;
 #pragma unroll
         for (int it = 0; it < WIT; ++it)
-            if (w_goff[it] >= 0) glds16(usrc + w_goff[it], udst + it * WNTHR * 4);
+            if (w_goff[it] >= 0) sis_global_load_lds16(usrc + w_goff[it], udst + it * WNTHR * 4);
         const float* xsrc = p.x + (int64_t)ci0 * HW;
         float* xdst = Xl + buf * WCC * xt + wbase * 4;
         if (st_goff >= 0) {
 #pragma unroll
-            for (int j = 0; j < WCC; ++j) glds16(xsrc + st_goff + j * HW, xdst + j * xt);
+            for (int j = 0; j < WCC; ++j) sis_global_load_lds16(xsrc + st_goff + j * HW, xdst + j * xt);
         }
     };
 
@@ -310,7 +294,7 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino_kernel(const ConvParams
     const int so = min(tn, tc.nb - 1) * p.Cin + half;
     const int aoff = (half * 4 + q * 2) * (WMBLK * 4) + (wm * 32 + l31) * 4;  // + (8 cp + ih) * WMBLK * 4: float4 (il, jj)
 
-    f32x16 acc[4][2];  // [row i of M][column jj of this wave's pair]
+    sis_f32x16 acc[4][2];  // [row i of M][column jj of this wave's pair]
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -347,8 +331,8 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino_kernel(const ConvParams
                 tt[2][c] = d[2][c] - d[1][c];
                 tt[3][c] = d[1][c] - d[3][c];
             }
-            const f32x4 ua0 = lds_ld4(Ub + (8 * cp) * WMBLK * 4);      // rows i = 0, 1
-            const f32x4 ua1 = lds_ld4(Ub + (8 * cp + 1) * WMBLK * 4);  // rows i = 2, 3
+            const sis_f32x4 ua0 = lds_ld4(Ub + (8 * cp) * WMBLK * 4);      // rows i = 0, 1
+            const sis_f32x4 ua1 = lds_ld4(Ub + (8 * cp + 1) * WMBLK * 4);  // rows i = 2, 3
             const float ua[4][2] = {{ua0.x, ua0.y}, {ua0.z, ua0.w}, {ua1.x, ua1.y}, {ua1.z, ua1.w}};
             float v0[4], v1[4];
             if (q == 0) {  // wave-uniform: this wave's two columns of (B^T d) B, scaled by the style
@@ -535,7 +519,7 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino2_kernel(const ConvParam
         S.b0 = (pt / tc.nth) * tc.nb; S.h0 = thi << thl; S.w0 = twi << twl;
         const int b = S.b0 + xl_n, h = S.h0 - 1 + xl_r, w = S.w0 - 4 + 4 * xl_c4;
         S.x_voff = (b < p.B && h >= 0 && h < p.H && w >= 0 && w < p.W) ? (unsigned)(xl_n * p.Cin * HW + h * p.W + w) * 4u : BUF_OOB;
-        S.x_rsrc = dma_rsrc(p.x + (int64_t)S.b0 * p.Cin * HW);
+        S.x_rsrc = sis_buffer_rsrc(p.x + (int64_t)S.b0 * p.Cin * HW);
     };
     // Tile k of workgroup g is pixel tile g + k * (#workgroups per channel block): the workgroups running at the same
     // time cover NEIGHBOURING tiles, whose halos they share through L2 (consecutive tiles per workgroup measured 57 %
@@ -545,29 +529,29 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino2_kernel(const ConvParam
     // weights: chunk = 32 rows (ci, q, ih) of 64 co x 4 floats = one 1 KB DMA instruction per row, 4 rows per wave
     // (row = it * 8 + wave); every lane moves the float4 of output channel o0 + lane
     constexpr int WIT = WF / 4 / WNTHR;
-    const __amdgpu_buffer_rsrc_t u_rsrc = dma_rsrc(p.wpk + (int64_t)o0 * 4);
+    const __amdgpu_buffer_rsrc_t u_rsrc = sis_buffer_rsrc(p.wpk + (int64_t)o0 * 4);
     const unsigned u_voff = (o0 + lane < p.Cout) ? (unsigned)lane * 16u : BUF_OOB;
     const unsigned u_row_bytes = (unsigned)p.Cout * 16u;
     auto stage_u = [&](int ci0, int buf) {
         float* udst = Ul + buf * WF + wave * 256;
         const unsigned s0 = (unsigned)(ci0 * 4 + wave) * u_row_bytes;
 #pragma unroll
-        for (int it = 0; it < WIT; ++it) bufld16(u_rsrc, udst + it * 8 * 256, u_voff, s0 + (unsigned)(it * 8) * u_row_bytes);
+        for (int it = 0; it < WIT; ++it) sis_buffer_load_lds16(u_rsrc, udst + it * 8 * 256, u_voff, s0 + (unsigned)(it * 8) * u_row_bytes);
     };
     auto stage_x = [&](int ci0, int buf, const TileState& S) {
         float* xdst = Xl + buf * WCC * xt + x_base;
 #pragma unroll
         for (int k = 0; k < XI; ++k) {
             const int j = x_ch0 + k * x_chstep;
-            bufld16(S.x_rsrc, xdst + j * xt, S.x_voff, (unsigned)((ci0 + j) * HW) * 4u);
+            sis_buffer_load_lds16(S.x_rsrc, xdst + j * xt, S.x_voff, (unsigned)((ci0 + j) * HW) * 4u);
         }
     };
     auto stage_u_piece = [&](int ci0, int buf, int it) {  // one 1 KB DMA instruction of stage_u
-        bufld16(u_rsrc, Ul + buf * WF + wave * 256 + it * 8 * 256, u_voff, (unsigned)(ci0 * 4 + wave + it * 8) * u_row_bytes);
+        sis_buffer_load_lds16(u_rsrc, Ul + buf * WF + wave * 256 + it * 8 * 256, u_voff, (unsigned)(ci0 * 4 + wave + it * 8) * u_row_bytes);
     };
     auto stage_x_piece = [&](int ci0, int buf, int k, __amdgpu_buffer_rsrc_t rsrc, unsigned voff) {  // one DMA instruction of stage_x
         const int j = x_ch0 + k * x_chstep;
-        bufld16(rsrc, Xl + buf * WCC * xt + x_base + j * xt, voff, (unsigned)((ci0 + j) * HW) * 4u);
+        sis_buffer_load_lds16(rsrc, Xl + buf * WCC * xt + x_base + j * xt, voff, (unsigned)((ci0 + j) * HW) * 4u);
     };
     // Input transform, ONE patch per lane per chunk: lane = tile (0..63), wave = channel of the chunk.  V = B^T d B
     // scaled by the style of the tile's sample, written as [channel][q][ih][tile][il][jj] (xi = 4 (2 ih + il) + 2 q + jj):
@@ -578,23 +562,23 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino2_kernel(const ConvParam
     const int txo = min(ttn, tc.nb - 1) * eh * ew + 2 * tty * ew + 2 * ttx + 2 + tch * xt;
     const int tso = min(ttn, tc.nb - 1) * p.Cin + tch;
     const int tvo = tch * (16 * WTILES) + ttile * 4;  // + (2 q + ih) * WTILES * 4
-    const f32x2 negpos = {-1.f, 1.f};
+    const sis_f32x2 negpos = {-1.f, 1.f};
     auto transform = [&](int ci0, int xbuf, int vbuf) {
-        f32x2 sv2 = {1.f, 1.f};
+        sis_f32x2 sv2 = {1.f, 1.f};
         if (STYLED) sv2.x = Sl[tso + ci0];
         const float* xb = Xl + xbuf * WCC * xt + txo + 1;
-        f32x2 t01[4], t23[4];
+        sis_f32x2 t01[4], t23[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const f32x2 px = {xb[r * ew], xb[r * ew + 1]}, py = {xb[r * ew + 2], xb[r * ew + 3]};
+            const sis_f32x2 px = {xb[r * ew], xb[r * ew + 1]}, py = {xb[r * ew + 2], xb[r * ew + 3]};
             t01[r] = pk_lo_np_plus(py, negpos, px);
             t23[r] = pk_hi_np_cross(px, negpos, py);
         }
         float* vb = Vl + vbuf * VF + tvo;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {  // column pair (2h, 2h+1) = q
-            const f32x2* tq = h == 0 ? t01 : t23;
-            const f32x2 a0_ = pk_sub(tq[0], tq[2]), a1_ = pk_add(tq[1], tq[2]), a2_ = pk_sub(tq[2], tq[1]), a3_ = pk_sub(tq[1], tq[3]);
+            const sis_f32x2* tq = h == 0 ? t01 : t23;
+            const sis_f32x2 a0_ = pk_sub(tq[0], tq[2]), a1_ = pk_add(tq[1], tq[2]), a2_ = pk_sub(tq[2], tq[1]), a3_ = pk_sub(tq[1], tq[3]);
             lds_st4(vb + (2 * h) * WTILES * 4, pk_scale(a0_, sv2), pk_scale(a1_, sv2));      // rows i = 0, 1
             lds_st4(vb + (2 * h + 1) * WTILES * 4, pk_scale(a2_, sv2), pk_scale(a3_, sv2));  // rows i = 2, 3
         }
@@ -608,7 +592,7 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino2_kernel(const ConvParam
     const int aoff = (half * 4 + q * 2) * (WMBLK * 4) + (wm * 32 + l31) * 4;    // + (8 cp + ih) * WMBLK * 4
     const int voff = (half * 4 + q * 2) * (WTILES * 4) + (wn * 32 + l31) * 4;   // + (8 cp + ih) * WTILES * 4
 
-    f32x16 acc[4][2];  // [row i of M][column jj of this wave's pair]
+    sis_f32x16 acc[4][2];  // [row i of M][column jj of this wave's pair]
     const bool partial = p.ksplit > 1;
 
     // First DMA of a tile: every global access of the start-up is in flight before the first wait (one memory
@@ -715,7 +699,7 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino2_kernel(const ConvParam
         // One slot after each of the 32 MFMAs.  Issue costs add up inside an MFMA gap and only ~48 cycles of them hide under a
         // 64-cycle MFMA (MI355X_MICROARCH.md, constants: an LDS-DMA piece costs 60-185 cycles to issue, a packed-f32 VALU
         // instruction ~3x a scalar one), so the side work is spread one expensive item per slot.
-        f32x4 ou[3], ov[3];
+        sis_f32x4 ou[3], ov[3];
         auto chunk_barrier = [&]() {
 #ifdef SIS_WINO_NOBARRIER  // timing experiment only (results are garbage): what does the per-chunk barrier cost?
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -806,8 +790,8 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino2_kernel(const ConvParam
                         for (int ii = 0; ii < 4; ++ii) o[ii][j] *= sv;
                         if (j & 1) {  // column pair q = j / 2 complete: rows (0,1) and (2,3) as two 16-byte writes
                             const int qq = j >> 1;
-                            *reinterpret_cast<f32x4*>(vw + (2 * qq) * WTILES * 4) = f32x4{o[0][j - 1], o[0][j], o[1][j - 1], o[1][j]};
-                            *reinterpret_cast<f32x4*>(vw + (2 * qq + 1) * WTILES * 4) = f32x4{o[2][j - 1], o[2][j], o[3][j - 1], o[3][j]};
+                            *reinterpret_cast<sis_f32x4*>(vw + (2 * qq) * WTILES * 4) = sis_f32x4{o[0][j - 1], o[0][j], o[1][j - 1], o[1][j]};
+                            *reinterpret_cast<sis_f32x4*>(vw + (2 * qq + 1) * WTILES * 4) = sis_f32x4{o[2][j - 1], o[2][j], o[3][j - 1], o[3][j]};
                         }
                     }
                 }
@@ -860,17 +844,17 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino2_kernel(const ConvParam
             constexpr int Q = decltype(qc)::value;
 #pragma unroll
             for (int j = 0; j < 16; j += 2) {
-                f32x2 m[2][2];
+                sis_f32x2 m[2][2];
 #pragma unroll
                 for (int jj = 0; jj < 2; ++jj) {
-                    const f32x2 a0 = {acc[0][jj][j], acc[0][jj][j + 1]};
-                    const f32x2 a1 = {acc[1][jj][j], acc[1][jj][j + 1]};
-                    const f32x2 a2 = {acc[2][jj][j], acc[2][jj][j + 1]};
-                    const f32x2 a3 = {acc[3][jj][j], acc[3][jj][j + 1]};
+                    const sis_f32x2 a0 = {acc[0][jj][j], acc[0][jj][j + 1]};
+                    const sis_f32x2 a1 = {acc[1][jj][j], acc[1][jj][j + 1]};
+                    const sis_f32x2 a2 = {acc[2][jj][j], acc[2][jj][j + 1]};
+                    const sis_f32x2 a3 = {acc[3][jj][j], acc[3][jj][j + 1]};
                     m[0][jj] = pk_add(pk_add(a0, a1), a2);
                     m[1][jj] = pk_sub(pk_sub(a1, a2), a3);
                 }
-                f32x2 pr[4];
+                sis_f32x2 pr[4];
 #pragma unroll
                 for (int r = 0; r < 2; ++r) {
                     pr[2 * r] = Q == 0 ? pk_add(m[r][0], m[r][1]) : m[r][0];

@@ -21,12 +21,9 @@
 // product W . X takes register i of every lane as its B operand for k = {row_i, row_i + 4} -- no LDS round trip.
 // Every output element is computed by the same instruction sequence whatever the batch size or tile position: the labels of
 // an image do not depend on the batch it is labelled in.
-#include "sis_common.h"
+#include "sis_device.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;   // (HIP's f32x4 is a union class: arrays of it end up in scratch)
 
 constexpr int PE_MAX_GROUPS = 8;   // resolutions below the output size (a 2^8 : 1 range)
 constexpr int PE_KC = 32;          // K chunk: one chunk never straddles two layers (channel counts % 32 == 0)
@@ -84,7 +81,7 @@ __global__ __launch_bounds__(256, 2) void pe_project_kernel(PeProjParams p) {
     const int q0 = (local / mtiles) * PJ_TQ, m0 = (local % mtiles) * PJ_TM;
     const int nch = (G.L.c0 + G.L.c1) / PE_KC;
 
-    f32x4 ra[4], rw[4];
+    sis_f32x4 ra[4], rw[4];
     auto load = [&](int c) {
         const int k0 = c * PE_KC;
 #pragma unroll
@@ -93,26 +90,26 @@ __global__ __launch_bounds__(256, 2) void pe_project_kernel(PeProjParams p) {
             const int q = q0 + 4 * v;
             if (q < Q) {   // hw % 4 == 0: the four pixels belong to one sample
                 const int b = q / hw, px = q - b * hw;
-                ra[i] = *reinterpret_cast<const f32x4*>(chunk_base(G.L, k0, b, hw) + (int64_t)k * hw + px);
+                ra[i] = *reinterpret_cast<const sis_f32x4*>(chunk_base(G.L, k0, b, hw) + (int64_t)k * hw + px);
             } else {
-                ra[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+                ra[i] = sis_f32x4{0.f, 0.f, 0.f, 0.f};
             }
-            rw[i] = *reinterpret_cast<const f32x4*>(G.wt + (int64_t)(k0 + k) * M + m0 + 4 * v);
+            rw[i] = *reinterpret_cast<const sis_f32x4*>(G.wt + (int64_t)(k0 + k) * M + m0 + 4 * v);
         }
     };
     auto store = [&]() {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int e = tid + 256 * i, k = e >> 5, v = e & 31;
-            *reinterpret_cast<f32x4*>(&sa[k][4 * v]) = ra[i];
-            *reinterpret_cast<f32x4*>(&sw[k][4 * v]) = rw[i];
+            *reinterpret_cast<sis_f32x4*>(&sa[k][4 * v]) = ra[i];
+            *reinterpret_cast<sis_f32x4*>(&sw[k][4 * v]) = rw[i];
         }
     };
 
     // wave tile: 64 pixels x 64 outputs; A = activations (rows = pixels), B = weights (columns = outputs), so the result's
     // column (the lane) runs along m and a row store is 128 contiguous bytes of the pixel-major output
     const int wq = wave & 1, wm = wave >> 1, r = lane & 31, h = lane >> 5;
-    f32x16 acc[2][2];
+    sis_f32x16 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -183,7 +180,7 @@ __global__ __launch_bounds__(256) void pe_head_kernel(PeHeadParams p) {
     __shared__ __attribute__((aligned(16))) float sw[PE_KC][H1 + PE_PAD];      // first-layer weights [k][h]
     __shared__ unsigned char votes[10][HD_TP];
     constexpr int HB = H1 / 32, OB = H2 / 32, CB = CP / 32;
-    constexpr int WV = PE_KC * H1 / 4 / 256;   // f32x4 weight loads per thread per chunk
+    constexpr int WV = PE_KC * H1 / 4 / 256;   // sis_f32x4 weight loads per thread per chunk
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int SS = p.S * p.S, tiles = SS / HD_TP;
     const int b = blockIdx.x / tiles, p0 = (blockIdx.x - b * tiles) * HD_TP;
@@ -191,7 +188,7 @@ __global__ __launch_bounds__(256) void pe_head_kernel(PeHeadParams p) {
     const int nch = p.Kf / PE_KC;
 
     for (int n = 0; n < p.N; ++n) {
-        f32x16 acc[HB];
+        sis_f32x16 acc[HB];
 #pragma unroll
         for (int hb = 0; hb < HB; ++hb)
 #pragma unroll
@@ -199,31 +196,31 @@ __global__ __launch_bounds__(256) void pe_head_kernel(PeHeadParams p) {
 
         // ---- full-resolution layers: acc[h][pixel] = W1[n][h][k] . act[k][pixel]
         if (nch > 0) {
-            f32x4 ra[4], rw[WV];
+            sis_f32x4 ra[4], rw[WV];
             auto load = [&](int c) {
                 const int k0 = c * PE_KC;
                 const float* base = chunk_base(p.full, k0, b, SS) + p0;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int e = tid + 256 * i, k = e >> 5, v = e & 31;
-                    ra[i] = *reinterpret_cast<const f32x4*>(base + (int64_t)k * SS + 4 * v);
+                    ra[i] = *reinterpret_cast<const sis_f32x4*>(base + (int64_t)k * SS + 4 * v);
                 }
 #pragma unroll
                 for (int i = 0; i < WV; ++i) {
                     const int e = tid + 256 * i, k = e / (H1 / 4), v = e % (H1 / 4);
-                    rw[i] = *reinterpret_cast<const f32x4*>(p.w1f + (int64_t)(k0 + k) * p.M + n * H1 + 4 * v);
+                    rw[i] = *reinterpret_cast<const sis_f32x4*>(p.w1f + (int64_t)(k0 + k) * p.M + n * H1 + 4 * v);
                 }
             };
             auto store = [&]() {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int e = tid + 256 * i, k = e >> 5, v = e & 31;
-                    *reinterpret_cast<f32x4*>(&sa[k][4 * v]) = ra[i];
+                    *reinterpret_cast<sis_f32x4*>(&sa[k][4 * v]) = ra[i];
                 }
 #pragma unroll
                 for (int i = 0; i < WV; ++i) {
                     const int e = tid + 256 * i, k = e / (H1 / 4), v = e % (H1 / 4);
-                    *reinterpret_cast<f32x4*>(&sw[k][4 * v]) = rw[i];
+                    *reinterpret_cast<sis_f32x4*>(&sw[k][4 * v]) = rw[i];
                 }
             };
             load(0);
@@ -268,8 +265,8 @@ __global__ __launch_bounds__(256) void pe_head_kernel(PeHeadParams p) {
 #pragma unroll
                 for (int gq = 0; gq < 4; ++gq) {
                     const int o = hb * 32 + 8 * gq;
-                    const f32x4 a00 = *reinterpret_cast<const f32x4*>(r00 + o), a01 = *reinterpret_cast<const f32x4*>(r01 + o);
-                    const f32x4 a10 = *reinterpret_cast<const f32x4*>(r10 + o), a11 = *reinterpret_cast<const f32x4*>(r11 + o);
+                    const sis_f32x4 a00 = *reinterpret_cast<const sis_f32x4*>(r00 + o), a01 = *reinterpret_cast<const sis_f32x4*>(r01 + o);
+                    const sis_f32x4 a10 = *reinterpret_cast<const sis_f32x4*>(r10 + o), a11 = *reinterpret_cast<const sis_f32x4*>(r11 + o);
                     acc[hb][4 * gq + 0] += ly0 * (lx0 * a00.x + lx1 * a01.x) + ly1 * (lx0 * a10.x + lx1 * a11.x);
                     acc[hb][4 * gq + 1] += ly0 * (lx0 * a00.y + lx1 * a01.y) + ly1 * (lx0 * a10.y + lx1 * a11.y);
                     acc[hb][4 * gq + 2] += ly0 * (lx0 * a00.z + lx1 * a01.z) + ly1 * (lx0 * a10.z + lx1 * a11.z);
@@ -283,7 +280,7 @@ __global__ __launch_bounds__(256) void pe_head_kernel(PeHeadParams p) {
         for (int hb = 0; hb < HB; ++hb)
 #pragma unroll
             for (int gq = 0; gq < 4; ++gq) {
-                const f32x4 bb = *reinterpret_cast<const f32x4*>(p.b1 + n * H1 + hb * 32 + 8 * gq + 4 * h);
+                const sis_f32x4 bb = *reinterpret_cast<const sis_f32x4*>(p.b1 + n * H1 + hb * 32 + 8 * gq + 4 * h);
                 acc[hb][4 * gq + 0] = fmaxf(acc[hb][4 * gq + 0] + bb.x, 0.f);
                 acc[hb][4 * gq + 1] = fmaxf(acc[hb][4 * gq + 1] + bb.y, 0.f);
                 acc[hb][4 * gq + 2] = fmaxf(acc[hb][4 * gq + 2] + bb.z, 0.f);
@@ -292,7 +289,7 @@ __global__ __launch_bounds__(256) void pe_head_kernel(PeHeadParams p) {
 
         // ---- H1 -> H2 (BatchNorm 1 folded), + b2, ReLU
         const float* w2 = p.w2t + (int64_t)n * H1 * H2;
-        f32x16 acc2[OB];
+        sis_f32x16 acc2[OB];
 #pragma unroll
         for (int ob = 0; ob < OB; ++ob) {
 #pragma unroll
@@ -310,7 +307,7 @@ __global__ __launch_bounds__(256) void pe_head_kernel(PeHeadParams p) {
         for (int ob = 0; ob < OB; ++ob)
 #pragma unroll
             for (int gq = 0; gq < 4; ++gq) {
-                const f32x4 bb = *reinterpret_cast<const f32x4*>(p.b2 + n * H2 + ob * 32 + 8 * gq + 4 * h);
+                const sis_f32x4 bb = *reinterpret_cast<const sis_f32x4*>(p.b2 + n * H2 + ob * 32 + 8 * gq + 4 * h);
                 acc2[ob][4 * gq + 0] = fmaxf(acc2[ob][4 * gq + 0] + bb.x, 0.f);
                 acc2[ob][4 * gq + 1] = fmaxf(acc2[ob][4 * gq + 1] + bb.y, 0.f);
                 acc2[ob][4 * gq + 2] = fmaxf(acc2[ob][4 * gq + 2] + bb.z, 0.f);
@@ -319,7 +316,7 @@ __global__ __launch_bounds__(256) void pe_head_kernel(PeHeadParams p) {
 
         // ---- H2 -> C (BatchNorm 2 folded), + b3
         const float* w3 = p.w3t + (int64_t)n * H2 * CP;
-        f32x16 acc3[CB];
+        sis_f32x16 acc3[CB];
 #pragma unroll
         for (int cb = 0; cb < CB; ++cb) {
 #pragma unroll

@@ -9,7 +9,7 @@
 //                             in ONE launch (training_builder/ema_net_train_builder.py:27-48: three groups with
 //                             their own lr / weight decay), driven by a device-resident chunk table.
 //  * sis_ema_update           emau.mu <- m*mu + (1-m)*mean_b(mu_b)  (updater/segmentation_updater.py:56-66).
-#include "sis_common.h"
+#include "sis_device.h"
 
 namespace {
 
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(float* __restrict__ partial
         acc += (m + logf(s)) - v[(int)lab];
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);   // written out: a call of sis_wave_sum here changes the generated code
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) partial[(int64_t)b * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(64) void ce_finish_kernel(float* __restrict__ loss,
     float acc = 0.f;
     for (int i = threadIdx.x; i < nblk; i += 64) acc += partial[(int64_t)b * nblk + i];
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);   // written out: a call of sis_wave_sum here changes the generated code
     if (threadIdx.x == 0) loss[b] = acc * inv_npix;
 }
 

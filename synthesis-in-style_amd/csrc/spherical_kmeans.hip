@@ -6,12 +6,9 @@
 //  * skm_label_kernel     labels, inertia and per-centre pixel counts over all pixels in one read of the activation
 //  * skm_label_finish_kernel   adds the per-workgroup partials in a fixed order
 // Everything is deterministic: no floating-point atomics, partial sums are added in a fixed order that depends on the shape only.
-#include "sis_common.h"
+#include "sis_device.h"
 
 #include <type_traits>
-
-typedef float skm_f32x16 __attribute__((ext_vector_type(16)));
-typedef float skm_f32x4 __attribute__((ext_vector_type(4)));
 
 #define SKM_KMAX 32
 #define SKM_CMAX 512
@@ -41,8 +38,7 @@ __global__ __launch_bounds__(256) void skm_gather_kernel(float* __restrict__ out
         v[i] = c < C ? xp[(int64_t)c * HW] : 0.f;
         s += (double)v[i] * (double)v[i];
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    s = sis_wave_sum(s);
     const double inv = s > 0.0 ? 1.0 / sqrt(s) : 0.0;
 #pragma unroll
     for (int i = 0; i < SKM_CMAX / 64; ++i) {
@@ -137,7 +133,7 @@ __global__ __launch_bounds__(256) void skm_loop_kernel(double* __restrict__ stat
         }
         // ---- distances on the matrix cores: S[centre][row] = sum_c cen[c][centre] x[row][c]; a lane's 16-byte load of channels
         // c0 + 4 half .. + 3 of its row feeds four MFMAs (channel pair (c0 + e, c0 + 4 + e) in step e: A is read to match)
-        skm_f32x16 acc[2];
+        sis_f32x16 acc[2];
         float xx[2] = {0.f, 0.f};
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -148,16 +144,16 @@ __global__ __launch_bounds__(256) void skm_loop_kernel(double* __restrict__ stat
                 const int row = tile * 32 + l31;
                 const float* xr = xb + (int64_t)(row < batch ? row : batch - 1) * C + 4 * half;
                 const float* ar = cen + (4 * half) * SKM_CS + l31;
-                skm_f32x4 ring[4];   // four loads in flight (the rows come from L2)
+                sis_f32x4 ring[4];   // four loads in flight (the rows come from L2)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) ring[q] = *reinterpret_cast<const skm_f32x4*>(xr + (8 * q < C ? 8 * q : C - 8));
+                for (int q = 0; q < 4; ++q) ring[q] = *reinterpret_cast<const sis_f32x4*>(xr + (8 * q < C ? 8 * q : C - 8));
                 for (int c0 = 0; c0 < C; c0 += 32) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const int c = c0 + 8 * q;
                         if (c < C) {   // (uniform)
-                            const skm_f32x4 v = ring[q];
-                            ring[q] = *reinterpret_cast<const skm_f32x4*>(xr + (c + 32 < C ? c + 32 : C - 8));
+                            const sis_f32x4 v = ring[q];
+                            ring[q] = *reinterpret_cast<const sis_f32x4*>(xr + (c + 32 < C ? c + 32 : C - 8));
                             acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(ar[(c + 0) * SKM_CS], v.x, acc[u], 0, 0, 0);
                             acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(ar[(c + 1) * SKM_CS], v.y, acc[u], 0, 0, 0);
                             acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(ar[(c + 2) * SKM_CS], v.z, acc[u], 0, 0, 0);
@@ -205,8 +201,7 @@ __global__ __launch_bounds__(256) void skm_loop_kernel(double* __restrict__ stat
             if (wave == 1) {   // rows lane, lane + 64, ... in order, then a butterfly
                 double e = 0.0;
                 for (int i = lane; i < batch; i += 64) e += dmin[i];
-#pragma unroll
-                for (int off = 32; off >= 1; off >>= 1) e += __shfl_xor(e, off, 64);
+                e = sis_wave_sum(e);
                 if (lane == 0) red[0] = e;
             }
         }
@@ -356,20 +351,20 @@ __global__ __launch_bounds__(256) void skm_label_kernel(int64_t* __restrict__ la
             const int64_t b = nn / HW, p = nn - b * HW;
             xp[j] = x + (b * C + half) * HW + p;
         }
-        skm_f32x16 acc[4];
+        sis_f32x16 acc[4];
         float xx[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
-        skm_f32x4 xs[2][U];
+        sis_f32x4 xs[2][U];
         auto request = [&](auto setc, int c0) {
             constexpr int S = decltype(setc)::value;
 #pragma unroll
             for (int s = 0; s < U; ++s) {
                 const int64_t off = (int64_t)(c0 + 2 * s) * HW;
-                if (VEC == 4) xs[S][s] = *reinterpret_cast<const skm_f32x4*>(xp[0] + off);
-                else xs[S][s] = skm_f32x4{xp[0][off], xp[1][off], xp[2][off], xp[3][off]};
+                if (VEC == 4) xs[S][s] = *reinterpret_cast<const sis_f32x4*>(xp[0] + off);
+                else xs[S][s] = sis_f32x4{xp[0][off], xp[1][off], xp[2][off], xp[3][off]};
             }
         };
         auto block = [&](auto setc, int c0) {
@@ -378,7 +373,7 @@ __global__ __launch_bounds__(256) void skm_label_kernel(int64_t* __restrict__ la
 #pragma unroll
             for (int s = 0; s < U; ++s) {
                 const float a = ab[(c0 + 2 * s) * 32];
-                const skm_f32x4 v = xs[S][s];
+                const sis_f32x4 v = xs[S][s];
                 acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, v.x, acc[0], 0, 0, 0);
                 acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, v.y, acc[1], 0, 0, 0);
                 acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, v.z, acc[2], 0, 0, 0);
@@ -419,9 +414,8 @@ __global__ __launch_bounds__(256) void skm_label_kernel(int64_t* __restrict__ la
         if (half == 0) {
             if (VEC == 4) {
                 if (valid[0]) {   // N % 4 == 0: the four are valid together
-                    typedef long long skm_i64x2 __attribute__((ext_vector_type(2)));
-                    *reinterpret_cast<skm_i64x2*>(labels + n[0]) = skm_i64x2{lab[0], lab[1]};
-                    *reinterpret_cast<skm_i64x2*>(labels + n[0] + 2) = skm_i64x2{lab[2], lab[3]};
+                    *reinterpret_cast<sis_i64x2*>(labels + n[0]) = sis_i64x2{lab[0], lab[1]};
+                    *reinterpret_cast<sis_i64x2*>(labels + n[0] + 2) = sis_i64x2{lab[2], lab[3]};
                 }
             } else {
 #pragma unroll
@@ -431,7 +425,7 @@ __global__ __launch_bounds__(256) void skm_label_kernel(int64_t* __restrict__ la
         }
     }
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) inertia += __shfl_xor(inertia, off, 64);
+    for (int off = 32; off >= 1; off >>= 1) inertia += __shfl_xor(inertia, off, 64);   // written out: a call of sis_wave_sum here changes the generated code
     if (lane == 0) lred[wave] = inertia;
     __syncthreads();
     double* out = ws + (int64_t)blockIdx.x * 33;
@@ -446,7 +440,7 @@ __global__ __launch_bounds__(64) void skm_label_finish_kernel(double* __restrict
     double s = 0.0;
     for (int b = lane; b < blocks; b += 64) s += ws[(int64_t)b * 33 + i];
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);   // written out: a call of sis_wave_sum here changes the generated code
     if (lane == 0) result[i] = s;
 }
 

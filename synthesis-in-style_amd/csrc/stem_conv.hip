@@ -13,29 +13,25 @@
 //             B = for column K = (g, kx) the 8 input pixels 2 (ox0 + j) - 3 + kx, j = 0..7: every second element of a 16-element
 //             run -- eight dwords, their low or high halves picked by v_perm_b32 according to the parity of kx.
 // The image may be float32 (converted while it is staged: no cast launch, no bf16 copy kept for the backward) or bfloat16.
-#include "sis_common.h"
+#include "sis_device.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 st_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float st_f32x16;
-typedef unsigned short u16;
 
 constexpr int ST_CO = 64, ST_G = 21, ST_STEPS = 11, ST_ROWS = 13, ST_N = 168;   // channels out, (ci, ky) groups, K-steps, staged rows per 4 output rows, dW columns
 constexpr int ST_FW = 72;                                                       // staged columns of the forward's 32-pixel tile (2 * 32 + 8)
 
-__device__ __forceinline__ u16 st_bf16(float v) { __hip_bfloat16 b = __float2bfloat16(v); return *reinterpret_cast<u16*>(&b); }
-__device__ __forceinline__ u16 st_load(const float* p) { return st_bf16(*p); }
-__device__ __forceinline__ u16 st_load(const u16* p) { return *p; }
+__device__ __forceinline__ sis_u16 st_bf16(float v) { __hip_bfloat16 b = __float2bfloat16(v); return *reinterpret_cast<sis_u16*>(&b); }
+__device__ __forceinline__ sis_u16 st_load(const float* p) { return st_bf16(*p); }
+__device__ __forceinline__ sis_u16 st_load(const sis_u16* p) { return *p; }
 
 // rows 2 oy0 - 3 .. 2 oy0 + 9, columns c0 .. c0 + tw - 1 of the three image planes of sample b -> tile[ci][row][tw] (bf16; zeros outside)
 template <typename TX>
-__device__ __forceinline__ void st_stage(u16* tile, const TX* x, int b, int H, int W, int oy0, int c0, int tw, int threads) {
+__device__ __forceinline__ void st_stage(sis_u16* tile, const TX* x, int b, int H, int W, int oy0, int c0, int tw, int threads) {
     const int total = 3 * ST_ROWS * tw;
     for (int e = threadIdx.x; e < total; e += threads) {
         const int c = e % tw, rr = e / tw, r = rr % ST_ROWS, ci = rr / ST_ROWS;
         const int iy = 2 * oy0 - 3 + r, ix = c0 + c;
-        u16 v = 0;
+        sis_u16 v = 0;
         if (iy >= 0 && iy < H && ix >= 0 && ix < W) v = st_load(x + (((int64_t)b * 3 + ci) * H + iy) * W + ix);
         tile[e] = v;
     }
@@ -43,27 +39,27 @@ __device__ __forceinline__ void st_stage(u16* tile, const TX* x, int b, int H, i
 
 // wpk[step][half][co][8]: taps kx = 0..6 (7: zero) of group g = 2 step + half (g = 21: zero) of output channel co
 template <typename TW>
-__global__ __launch_bounds__(256) void stem7_pack_kernel(u16* __restrict__ wpk, const TW* __restrict__ w) {
+__global__ __launch_bounds__(256) void stem7_pack_kernel(sis_u16* __restrict__ wpk, const TW* __restrict__ w) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= ST_STEPS * 2 * ST_CO * 8) return;
     const int kx = i & 7, co = (i >> 3) & 63, g = i >> 9;
-    u16 v = 0;
+    sis_u16 v = 0;
     if (g < ST_G && kx < 7) v = st_load(w + ((int64_t)co * ST_G + g) * 7 + kx);   // w [co][ci][ky][kx], g = 7 ci + ky
     wpk[i] = v;
 }
 
 // workgroup = 4 output rows x 32 output pixels x 64 channels; wave w = row oy0 + w
 template <typename TX>
-__global__ __launch_bounds__(256) void stem7_fwd_kernel(u16* __restrict__ y, const TX* __restrict__ x, const u16* __restrict__ wpk, int H, int W,
+__global__ __launch_bounds__(256) void stem7_fwd_kernel(sis_u16* __restrict__ y, const TX* __restrict__ x, const sis_u16* __restrict__ wpk, int H, int W,
                                                         int Ho, int Wo) {
-    __shared__ __attribute__((aligned(16))) u16 tile[3 * ST_ROWS * ST_FW];
+    __shared__ __attribute__((aligned(16))) sis_u16 tile[3 * ST_ROWS * ST_FW];
     const int b = blockIdx.z, oy0 = blockIdx.y * 4, ox0 = blockIdx.x * 32;
     st_stage(tile, x, b, H, W, oy0, 2 * ox0 - 4, ST_FW, 256);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 31, kh = lane >> 5;
     const int oy = oy0 + wave;
     if (oy >= Ho) return;
-    st_f32x16 acc[2];
+    sis_f32x16 acc[2];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -80,17 +76,17 @@ __global__ __launch_bounds__(256) void stem7_fwd_kernel(u16* __restrict__ y, con
             frag = make_uint4(__builtin_amdgcn_alignbit(d1, d0, 16), __builtin_amdgcn_alignbit(d2, d1, 16), __builtin_amdgcn_alignbit(d3, d2, 16),
                               __builtin_amdgcn_alignbit(d4, d3, 16) & 0x0000FFFFu);   // (the 8th tap has a zero weight: its pixel must not reach the product as inf / NaN)
         }
-        const st_bf16x8 bf = __builtin_bit_cast(st_bf16x8, frag);
+        const sis_bf16x8 bf = __builtin_bit_cast(sis_bf16x8, frag);
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
             const uint4 a = *reinterpret_cast<const uint4*>(wpk + ((int64_t)(2 * s + kh) * ST_CO + mt * 32 + n) * 8);
-            acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(st_bf16x8, a), bf, acc[mt], 0, 0, 0);
+            acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(sis_bf16x8, a), bf, acc[mt], 0, 0, 0);
         }
     }
     const int ox = ox0 + n;
     if (ox >= Wo) return;
     const int64_t plane = (int64_t)Ho * Wo;
-    u16* yb = y + (int64_t)b * ST_CO * plane + (int64_t)oy * Wo + ox;
+    sis_u16* yb = y + (int64_t)b * ST_CO * plane + (int64_t)oy * Wo + ox;
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -103,9 +99,9 @@ __global__ __launch_bounds__(256) void stem7_fwd_kernel(u16* __restrict__ y, con
 // workgroup = 4 output rows of one sample, all their pixels; wave w = M tile w & 1, N tiles (w >> 1) + {0, 2, 4}; partial dW
 // [co][168] of the workgroup -> slab[workgroup]
 template <typename TX>
-__global__ __launch_bounds__(256) void stem7_wgrad_kernel(float* __restrict__ slab, const TX* __restrict__ x, const u16* __restrict__ gy, int H, int W,
+__global__ __launch_bounds__(256) void stem7_wgrad_kernel(float* __restrict__ slab, const TX* __restrict__ x, const sis_u16* __restrict__ gy, int H, int W,
                                                           int Ho, int Wo, int tw) {
-    extern __shared__ __attribute__((aligned(16))) u16 wtile[];   // [3][13][tw]
+    extern __shared__ __attribute__((aligned(16))) sis_u16 wtile[];   // [3][13][tw]
     const int b = blockIdx.y, oy0 = blockIdx.x * 4;
     st_stage(wtile, x, b, H, W, oy0, -4, tw, 256);
     __syncthreads();
@@ -122,19 +118,19 @@ __global__ __launch_bounds__(256) void stem7_wgrad_kernel(float* __restrict__ sl
         odd[t] = ((1 + kx) & 1) != 0;          // tile column of tap kx for pixel ox: 2 ox + 1 + kx
         cbase[t] = (1 + kx) & ~1;
     }
-    st_f32x16 acc[3];
+    sis_f32x16 acc[3];
 #pragma unroll
     for (int t = 0; t < 3; ++t)
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
     const unsigned* t32 = reinterpret_cast<const unsigned*>(wtile);
     const int64_t plane = (int64_t)Ho * Wo;
-    const u16* gyc = gy + ((int64_t)b * ST_CO + mt * 32 + nn) * plane;
+    const sis_u16* gyc = gy + ((int64_t)b * ST_CO + mt * 32 + nn) * plane;
     const bool vec = (Wo & 7) == 0;
     for (int r = 0; r < 4; ++r) {
         const int oy = oy0 + r;
         if (oy >= Ho) break;
-        const u16* grow = gyc + (int64_t)oy * Wo;
+        const sis_u16* grow = gyc + (int64_t)oy * Wo;
         for (int ox0 = 0; ox0 < Wo; ox0 += 16) {
             const int px = ox0 + 8 * kh;
             uint4 a = make_uint4(0u, 0u, 0u, 0u);
@@ -146,7 +142,7 @@ __global__ __launch_bounds__(256) void stem7_wgrad_kernel(float* __restrict__ sl
                 for (int j = 0; j < 8; ++j) e[j] = px + j < Wo ? grow[px + j] : 0u;
                 a = make_uint4(e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16));
             }
-            const st_bf16x8 af = __builtin_bit_cast(st_bf16x8, a);
+            const sis_bf16x8 af = __builtin_bit_cast(sis_bf16x8, a);
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
                 uint4 frag = make_uint4(0u, 0u, 0u, 0u);
@@ -160,7 +156,7 @@ __global__ __launch_bounds__(256) void stem7_wgrad_kernel(float* __restrict__ sl
                     frag = make_uint4(__builtin_amdgcn_perm(d[1], d[0], sel), __builtin_amdgcn_perm(d[3], d[2], sel),
                                       __builtin_amdgcn_perm(d[5], d[4], sel), __builtin_amdgcn_perm(d[7], d[6], sel));
                 }
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, __builtin_bit_cast(st_bf16x8, frag), acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, __builtin_bit_cast(sis_bf16x8, frag), acc[t], 0, 0, 0);
             }
         }
     }
@@ -213,9 +209,9 @@ extern "C" int sis_stem_conv_pack(void* packed, const void* weight, int weight_d
     SIS_REQUIRE(weight_dtype == SIS_F32 || weight_dtype == SIS_BF16, "sis_stem_conv_pack: weight must be float32 or bfloat16");
     const int total = ST_STEPS * 2 * ST_CO * 8;
     if (weight_dtype == SIS_F32)
-        hipLaunchKernelGGL(stem7_pack_kernel<float>, dim3(sis_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, (u16*)packed, (const float*)weight);
+        hipLaunchKernelGGL(stem7_pack_kernel<float>, dim3(sis_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, (sis_u16*)packed, (const float*)weight);
     else
-        hipLaunchKernelGGL(stem7_pack_kernel<u16>, dim3(sis_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, (u16*)packed, (const u16*)weight);
+        hipLaunchKernelGGL(stem7_pack_kernel<sis_u16>, dim3(sis_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, (sis_u16*)packed, (const sis_u16*)weight);
     SIS_CHECK_LAUNCH("stem7_pack_kernel");
     return 0;
 }
@@ -230,9 +226,9 @@ extern "C" int sis_stem_conv_fwd(void* y, const void* x, int x_dtype, const void
     const int ho = (h + 6 - 7) / 2 + 1, wo = (w + 6 - 7) / 2 + 1;
     const dim3 grid(sis_cdiv(wo, 32), sis_cdiv(ho, 4), batch);
     if (x_dtype == SIS_F32)
-        hipLaunchKernelGGL(stem7_fwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (u16*)y, (const float*)x, (const u16*)packed, h, w, ho, wo);
+        hipLaunchKernelGGL(stem7_fwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (sis_u16*)y, (const float*)x, (const sis_u16*)packed, h, w, ho, wo);
     else
-        hipLaunchKernelGGL(stem7_fwd_kernel<u16>, grid, dim3(256), 0, (hipStream_t)stream, (u16*)y, (const u16*)x, (const u16*)packed, h, w, ho, wo);
+        hipLaunchKernelGGL(stem7_fwd_kernel<sis_u16>, grid, dim3(256), 0, (hipStream_t)stream, (sis_u16*)y, (const sis_u16*)x, (const sis_u16*)packed, h, w, ho, wo);
     SIS_CHECK_LAUNCH("stem7_fwd_kernel");
     sis_kernel_name = "stem7_fwd_kernel";
     return 0;
@@ -255,22 +251,22 @@ extern "C" int sis_stem_conv_wgrad(void* dw, int dw_dtype, const void* x, int x_
     SIS_REQUIRE(batch <= 65535, "sis_stem_conv_wgrad: more than 65 535 samples");
     const int ho = (h + 6 - 7) / 2 + 1, wo = (w + 6 - 7) / 2 + 1;
     const int tw = 2 * (sis_cdiv(wo, 16) * 16) + 8;                    // staged columns -4 .. 2 * ceil16(Wo) + 3 (even: rows stay dword aligned)
-    const size_t lds = (size_t)3 * ST_ROWS * tw * sizeof(u16);
+    const size_t lds = (size_t)3 * ST_ROWS * tw * sizeof(sis_u16);
     SIS_REQUIRE(lds <= 160 * 1024, "sis_stem_conv_wgrad: image too wide");
     hipStream_t st = (hipStream_t)stream;
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&stem7_wgrad_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&stem7_wgrad_kernel<u16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&stem7_wgrad_kernel<sis_u16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return sis_fail("sis_stem_conv_wgrad: cannot raise the LDS limit: %s", hipGetErrorString(e));
         attr_set = true;
     }
     const dim3 grid(sis_cdiv(ho, 4), batch);
     if (x_dtype == SIS_F32)
-        hipLaunchKernelGGL(stem7_wgrad_kernel<float>, grid, dim3(256), lds, st, (float*)workspace, (const float*)x, (const u16*)grad_y, h, w, ho, wo, tw);
+        hipLaunchKernelGGL(stem7_wgrad_kernel<float>, grid, dim3(256), lds, st, (float*)workspace, (const float*)x, (const sis_u16*)grad_y, h, w, ho, wo, tw);
     else
-        hipLaunchKernelGGL(stem7_wgrad_kernel<u16>, grid, dim3(256), lds, st, (float*)workspace, (const u16*)x, (const u16*)grad_y, h, w, ho, wo, tw);
+        hipLaunchKernelGGL(stem7_wgrad_kernel<sis_u16>, grid, dim3(256), lds, st, (float*)workspace, (const sis_u16*)x, (const sis_u16*)grad_y, h, w, ho, wo, tw);
     SIS_CHECK_LAUNCH("stem7_wgrad_kernel");
     const int parts = batch * sis_cdiv(ho, 4);
     if (dw_dtype == SIS_F32)

@@ -11,7 +11,7 @@
 //     output instead of 16).  FUSE adds NoiseInjection + FusedLeakyReLU (model.py:338-340) so the
 //     (2H+1)^2 intermediate is read exactly once and the activation written exactly once.
 // Both are HBM-bound: 4*(in + out) bytes per plane.
-#include "sis_common.h"
+#include "sis_device.h"
 
 namespace {
 
@@ -152,9 +152,6 @@ struct BlurRowParams {
 };
 constexpr int BR_ROWS = 8;
 
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
 // Round 2: every load of the lane's 8 + 3 input rows (and of its 8 noise rows) is in flight before the first one is used.
 // The first version waited after each row's float4 (the halo shuffles consume it at once, and the edge lanes' scalar loads sat
 // behind branches): one 16-byte load in flight per lane, 32 KB per CU -- by Little's law about the 4.8 TB/s it measured.  Loads go
@@ -183,38 +180,38 @@ __global__ __launch_bounds__(256) void blur_rows_kernel(float* __restrict__ out,
     // The wave's descriptor starts at the plane of its first lane (a wave of a narrow map spans a few planes: small offsets).
     const int plane0 = __builtin_amdgcn_readfirstlane(plane);
     const int64_t plane_elems = (int64_t)p.in_h * p.in_rs;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(in + plane0 * plane_elems), 0, 0x7FFFFFFF, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = sis_buffer_rsrc(in + plane0 * plane_elems);
     const unsigned base = (unsigned)(((int64_t)(plane - plane0) * plane_elems + 4 * xi) * 4);  // bytes: row 0, column 4 xi
     const int oy0 = rg * BR_ROWS;
     const bool left_edge = xi == 0, right_edge = xi == p.cols4 - 1;
     // pad_x0 == 1: the lane's aligned float4 covers window columns 1..4; column 0 is the left neighbour's .w, columns 5..6 the right
     // neighbour's .x / .y -- by shuffle, except at wave edges (from memory) and image edges (zero / from memory up to in_w).
     const bool mem_l = lane == 0 && !left_edge, mem_r = lane == 63 || right_edge;
-    f32x4_t ra[NR];
+    sis_f32x4 ra[NR];
     float rl[NR];
-    f32x2_t rr[NR];
+    sis_f32x2 rr[NR];
 #pragma unroll
     for (int t = 0; t < NR; ++t) {
         const int iy = oy0 - p.pad_y0 + t;
         const bool ok = iy >= 0 && iy < p.in_h;
         const unsigned ro = base + (unsigned)(iy * p.in_rs * 4);
-        ra[t] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? ro : OOB, 0, 0));
+        ra[t] = __builtin_bit_cast(sis_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? ro : OOB, 0, 0));
         rl[t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (ok && mem_l) ? ro - 4u : OOB, 0, 0));
-        rr[t] = __builtin_bit_cast(f32x2_t, __builtin_amdgcn_raw_buffer_load_b64(rs, (ok && mem_r) ? ro + 16u : OOB, 0, 0));
+        rr[t] = __builtin_bit_cast(sis_f32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, (ok && mem_r) ? ro + 16u : OOB, 0, 0));
     }
     float nw = 0.f, bb = 0.f;
-    f32x4_t nz[BR_ROWS];
+    sis_f32x4 nz[BR_ROWS];
     if (FUSE) {
         const bool has_noise = noise != nullptr;
         if (has_noise) nw = noise_w[0];
         if (bias) bb = bias[plane % p.channels];
         const int b0 = __builtin_amdgcn_readfirstlane(plane / p.channels);
-        const __amdgpu_buffer_rsrc_t ns = __builtin_amdgcn_make_buffer_rsrc((void*)(noise + (has_noise ? b0 * p.noise_bstride : 0)), 0, 0x7FFFFFFF, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ns = sis_buffer_rsrc(noise + (has_noise ? b0 * p.noise_bstride : 0));
         const unsigned nbase = (unsigned)(((int64_t)(plane / p.channels - b0) * p.noise_bstride + 4 * xi) * 4);
 #pragma unroll
         for (int j = 0; j < BR_ROWS; ++j) {
             const int oy = oy0 + j;
-            nz[j] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(ns, (has_noise && oy < p.out_h) ? nbase + (unsigned)(oy * p.out_w * 4) : OOB, 0, 0));
+            nz[j] = __builtin_bit_cast(sis_f32x4, __builtin_amdgcn_raw_buffer_load_b128(ns, (has_noise && oy < p.out_h) ? nbase + (unsigned)(oy * p.out_w * 4) : OOB, 0, 0));
         }
     }
     const bool r0_ok = 4 * xi + 4 < p.in_w, r1_ok = 4 * xi + 5 < p.in_w;  // (only the image's right edge can fail these)

@@ -1,12 +1,6 @@
 // Device helpers shared by the ViT-encoder kernels of TransUNet (gemm_bf16.hip, attention_bf16.hip, vit_elementwise.hip).
 #pragma once
-#include "sis_common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 sis_bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 sis_bf16x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 sis_bf16x2;
-typedef __attribute__((ext_vector_type(4))) float sis_f32x4;
-typedef __attribute__((ext_vector_type(16))) float sis_f32x16;
+#include "sis_device.h"
 
 // ---- dropout as a counter-based stream.  The elements of a dropout site are numbered row-major; every consumer handles
 // aligned QUADS (4 consecutive elements, index % 4 == 0: a lane's 4 accumulator columns / one float4).  Quad `quad` of site

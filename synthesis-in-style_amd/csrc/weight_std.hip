@@ -5,18 +5,9 @@
 // and the result can be written directly in the autocast dtype (bf16 / f16) so the convolution needs no cast kernel.
 //   forward   w_hat[r, i] = (w[r, i] - mean_r) / sqrt(var_r + eps);  invstd_r kept for the backward
 //   backward  dw[r, i] = invstd_r * (g[r, i] - mean_i(g) - w_hat[r, i] * mean_i(g * w_hat))
-#include "sis_common.h"
+#include "sis_device.h"
 
 namespace {
-
-__device__ __forceinline__ float ws_block_sum(float v, float* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 template <typename TO>
 __global__ __launch_bounds__(256) void weight_std_fwd_kernel(TO* __restrict__ what, float* __restrict__ invstd,
@@ -25,10 +16,10 @@ __global__ __launch_bounds__(256) void weight_std_fwd_kernel(TO* __restrict__ wh
     const float* row = w + (int64_t)blockIdx.x * n;
     float s = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) s += row[i];
-    const float mean = ws_block_sum(s, red) / (float)n;
+    const float mean = sis_block_sum4(s, red) / (float)n;
     float m2 = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) { const float d = row[i] - mean; m2 += d * d; }
-    const float var = ws_block_sum(m2, red) / (float)n;
+    const float var = sis_block_sum4(m2, red) / (float)n;
     const float sd = sqrtf(var + eps);
     if (threadIdx.x == 0) invstd[blockIdx.x] = 1.f / sd;
     TO* o = what + (int64_t)blockIdx.x * n;
@@ -45,15 +36,15 @@ __global__ __launch_bounds__(256) void weight_std_bwd_kernel(float* __restrict__
     // w_hat is recomputed from w (fp32) instead of being read back in a 16-bit type
     float s = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) s += row[i];
-    const float mean = ws_block_sum(s, red) / (float)n;
+    const float mean = sis_block_sum4(s, red) / (float)n;
     const float is = invstd[blockIdx.x];
     float sg = 0.f, sgw = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) {
         const float gi = sis_ld(grow, i), wh = (row[i] - mean) * is;
         sg += gi; sgw += gi * wh;
     }
-    const float mg = ws_block_sum(sg, red) / (float)n;
-    const float mgw = ws_block_sum(sgw, red) / (float)n;
+    const float mg = sis_block_sum4(sg, red) / (float)n;
+    const float mgw = sis_block_sum4(sgw, red) / (float)n;
     float* o = dw + (int64_t)blockIdx.x * n;
     for (int i = threadIdx.x; i < n; i += 256) {
         const float gi = sis_ld(grow, i), wh = (row[i] - mean) * is;
