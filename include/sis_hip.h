@@ -133,6 +133,20 @@ int sis_modconv2d(float* out, const float* x, const float* wpk, const float* s,
  * selects the direct kernel. */
 int sis_modconv_prepack_wino(float* u, const float* w, int cout, int cin, void* stream);
 
+/* The same layers in Winograd F(2x4,3x3) form (csrc/modconv_wino24.h): 24 multiplies per 2 x 4 output tile, 24/72 of the
+ * direct form.  sis_modconv_prepack_wino24 writes cin * 24 * cout floats, (G2 w[co,ci] G4^T)[xi] with F(2,3) on the row axis and
+ * F(4,3) (points 0, +-1, +-2, inf) on the column axis, in the kernel's private order [ci][q][g][co][4] (plane 3 i + jj = 4 g + k
+ * of column half q, xi = 6 i + 3 q + jj).  sis_modconv_wino24_eligible depends on (cin, cout, h, w) only, never on the batch:
+ * cin % 8 == 0, cout % 64 == 0, h % 2 == 0, w % 4 == 0, w > 16 and a map of at least 512 pixels.  sis_modconv2d_wino24 is
+ * sis_modconv2d for such a layer (same operands and fused tail; u24 in place of wpk / wino_u; no workspace: never split-K);
+ * tiles_per_wg = 0 lets the launcher choose how many 512-pixel tiles a workgroup walks (> 0: the tests' override, must divide
+ * the tile count; the results do not depend on it). */
+int sis_modconv_prepack_wino24(float* u, const float* w, int cout, int cin, void* stream);
+int sis_modconv_wino24_eligible(int cin, int cout, int h, int w);
+int sis_modconv2d_wino24(float* out, const float* x, const float* u24, const float* s, const float* dscale,
+                         const float* noise, int64_t noise_batch_stride, const float* noise_weight, const float* bias,
+                         int batch, int cin, int cout, int h, int w, int fuse_act, int tiles_per_wg, void* stream);
+
 /* Modulated transposed convolution, stride 2, no padding, ks = 3: model.py:251-261 up to (not
  * including) the Blur: t[b,co,p,q] = dscale[b,co] * sum_{ci, 2h+kh=p, 2w+kw=q} wpk[ci][kh*3+kw][co]
  * * s[b,ci] * x[b,ci,h,w];  t is [B, Cout, 2H+1, t_row_stride] with the first 2W+1 floats of every row

@@ -1062,3 +1062,6 @@ int modconv_wino_launch(ConvParams& p, hipStream_t st, void* workspace, int64_t 
     if (p.ksplit > 1) modconv_splitk_finish_launch(p, st);
     return 0;
 }
+
+// Winograd F(2x4,3x3) form of the same layers: kernel, prepack and C entries
+#include "modconv_wino24.h"

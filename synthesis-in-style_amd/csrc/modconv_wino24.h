@@ -1,0 +1,418 @@
+// Stride-1 3x3 modulated convolution in Winograd F(2x4, 3x3) form: 2 output rows x 4 output columns per tile from a
+// 4 x 6 input patch, 24 multiplies per 8 outputs (24/72 of the direct form; F(2x2,3x3) in modconv_wino.hip: 16/36).
+// Included at the end of modconv_wino.hip (one translation unit: the helpers above are shared).
+//
+//   U[ci][xi][co] = (G2 g G4^T)[xi]     xi = 6 i + j, i = 0..3 (F(2,3) on the row axis), j = 0..5 (F(4,3), points
+//                                        0, +-1, +-2, inf, on the column axis); prepacked once per checkpoint
+//                                        (sis_modconv_prepack_wino24) as [ci][q][g][co][4]: wave q owns the columns
+//                                        j = 3 q + jj, jj = 0..2, and its 12 planes e = 3 i + jj = 4 g + k sit in
+//                                        three 16-byte LDS reads
+//   V[xi]         = (B2^T d B4)[xi]      once per workgroup and chunk into a second LDS image of the same order,
+//                                        one chunk ahead of the MFMAs: lane = tile, wave = (channel of the chunk, q),
+//                                        i.e. half a patch per lane (5 of the 6 patch columns: one aligned 16-byte
+//                                        read and one 4-byte read per row, the address of the latter selected by q)
+//   M[xi]        += U[xi] (co x ci) * V[xi] (ci x tile)      12 MFMA chains per wave (v_mfma_f32_32x32x2_f32)
+//   Y             = A2^T M A4            A2^T M is lane-local; the column sum mixes the two q waves of a (co, tile):
+//                                        each sends the 2 x 3 row sums of 8 accumulator rows to its partner through
+//                                        the idle U / V buffers and finalises the other 8 (layer tail, 16-byte stores)
+//
+// Workgroup = 8 waves = (co half) x (tile half) x q = 64 co x 64 tiles (512 pixels: 8 x 64 or 16 x 32), 4-channel
+// chunks: U and V 24 KB each per buffer, double-buffered, plus the raw input tile 2 x 11.25 KB: 121 KB of LDS.
+
+namespace {
+
+constexpr int W24_CC = 4;                       // input channels per chunk
+constexpr int W24_UF = W24_CC * 24 * WMBLK;     // floats of a weight chunk  [ch][q][g][co][4]
+constexpr int W24_VF = W24_CC * 24 * WTILES;    // floats of a V chunk       [ch][q][g][tile][4]
+constexpr int W24_XT = 720;                     // floats per channel of the staged input tile: 10 x 72 or 18 x 40
+constexpr int W24_XP = 3;                       // 64-lane float4 pieces of a channel (the last one shifted back to end with the tile)
+constexpr int W24_BAR = 19;                     // MFMA slot of a chunk behind which its barrier sits
+
+// u[ci][q][g][co][k]: plane e = 3 i + jj = 4 g + k of column half q (j = 3 q + jj), from w[co][ci][3][3]
+__global__ __launch_bounds__(256) void wino24_prepack_kernel(float* __restrict__ u, const float* __restrict__ w, int cout, int cin) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;  // idx = ci * cout + co
+    if (idx >= (int64_t)cout * cin) return;
+    const int co = (int)(idx % cout), ci = (int)(idx / cout);
+    const float* g = w + ((int64_t)co * cin + ci) * 9;
+    float t[4][3];  // G2 g
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float g0 = g[c], g1 = g[3 + c], g2 = g[6 + c];
+        t[0][c] = g0;
+        t[1][c] = 0.5f * (g0 + g1 + g2);
+        t[2][c] = 0.5f * (g0 - g1 + g2);
+        t[3][c] = g2;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float a = t[i][0], b = t[i][1], c = t[i][2];
+        const float o[6] = {0.25f * a,
+                            (-1.f / 6.f) * (a + b + c),
+                            (-1.f / 6.f) * (a - b + c),
+                            (1.f / 24.f) * a + (1.f / 12.f) * b + (1.f / 6.f) * c,
+                            (1.f / 24.f) * a - (1.f / 12.f) * b + (1.f / 6.f) * c,
+                            c};
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            const int q = j / 3, e = 3 * i + j % 3;
+            u[((((int64_t)ci * 2 + q) * 3 + (e >> 2)) * cout + co) * 4 + (e & 3)] = o[j];
+        }
+    }
+}
+
+__global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvParams p, const int tiles_per_wg, const int xcd_group) {
+    constexpr int CC = W24_CC, UF = W24_UF, VF = W24_VF, XT = W24_XT;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* Ul = lds;                  // [2][UF]
+    float* Vl = Ul + 2 * UF;          // [2][VF]   (Ul and Vl together: the column exchange of the epilogue, 96 KB)
+    float* Xl = Vl + 2 * VF;          // [2][CC * XT]
+    float* Sl = Xl + 2 * CC * XT;     // [Cin]     style row of the tile's sample
+    float* Dl = Sl + p.Cin;           // [WMBLK]   scale * demodulation
+    float* Bl = Dl + WMBLK;           // [WMBLK]   bias
+    float* Nl = Bl + WMBLK;           // [WTILES][2][4] noise_weight * noise of the tile's pixels
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, half = lane >> 5;
+    const int q = wave & 1, wn = (wave >> 1) & 1, wm = wave >> 2;
+
+    // workgroup order: as modconv_wino2_kernel (output-channel block fastest; xcd_group: the blocks of a pixel tile on one XCD)
+    const int n_co = p.Cout / WMBLK;
+    const int wg = xcd_group ? (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    const int o0 = (wg % n_co) * WMBLK;
+    const TileClass tc = p.cls[0];
+    const int thl = tc.th_log2, twl = tc.tw_log2;
+    const int tw = 1 << twl;
+    // staged input tile: rows h0-1 .. h0+th, columns w0-4 .. w0+tw+3 (16-byte aligned superset of the 1-pixel halo)
+    const int ew = tw + 8, ew4 = ew >> 2;
+    const int HW = p.H * p.W;
+    const int k_hi = p.Cin, k_last = k_hi - CC;
+
+    // weights: a chunk is 24 rows (ch, q, g) of 64 co x 4 floats = one 1 KB DMA instruction per row, rows wave + 8 it
+    const __amdgpu_buffer_rsrc_t u_rsrc = sis_buffer_rsrc(p.wpk + (int64_t)o0 * 4);
+    const unsigned u_voff = (unsigned)lane * 16u;
+    const unsigned u_row_bytes = (unsigned)p.Cout * 16u;
+    auto stage_u_piece = [&](int ci0, int buf, int it) {
+        sis_buffer_load_lds16(u_rsrc, Ul + buf * UF + (wave + it * 8) * 256, u_voff, (unsigned)(ci0 * 6 + wave + it * 8) * u_row_bytes);
+    };
+    // input tile: 4 channels x 3 pieces of 64 float4 = 12 DMA instructions per chunk; wave w moves pieces w and (w + 8) % 12
+    // (waves 4..7 repeat pieces 0..3: the same values to the same place, so that every wave runs the same instructions)
+    int xp_ch[2], xp_base[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int piece = k == 0 ? wave : (wave + 8) % (CC * W24_XP);
+        xp_ch[k] = piece / W24_XP;
+        xp_base[k] = min((piece % W24_XP) * 256, XT - 256);
+    }
+    struct TileState {
+        int b, h0, w0;
+        unsigned xv[2];                 // byte offset of this lane's float4 of each piece inside the channel plane
+        __amdgpu_buffer_rsrc_t x_rsrc;  // descriptor based at the tile's sample
+    } T;
+    auto tile_setup = [&](int pt, TileState& S, int lane) {
+        const int twi = pt % tc.ntw; pt /= tc.ntw;
+        const int thi = pt % tc.nth;
+        S.b = pt / tc.nth; S.h0 = thi << thl; S.w0 = twi << twl;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int f4 = (xp_base[k] >> 2) + lane;
+            const int r = f4 / ew4, c4 = f4 - r * ew4;
+            const int h = S.h0 - 1 + r, w = S.w0 - 4 + 4 * c4;
+            S.xv[k] = (h >= 0 && h < p.H && w >= 0 && w < p.W) ? (unsigned)(h * p.W + w) * 4u : BUF_OOB;
+        }
+        S.x_rsrc = sis_buffer_rsrc(p.x + (int64_t)S.b * p.Cin * HW);
+    };
+    auto stage_x_piece = [&](int ci0, int buf, int k) {
+        sis_buffer_load_lds16(T.x_rsrc, Xl + buf * CC * XT + xp_ch[k] * XT + xp_base[k], T.xv[k], (unsigned)((ci0 + xp_ch[k]) * HW) * 4u);
+    };
+    const int pt_first = wg / n_co, pt_step = gridDim.x / n_co;
+    const int txs = twl - 2;  // log2(tiles per tile row)
+    const float noise_w0 = (p.fuse && p.noise) ? p.noise_w[0] : 0.f;
+
+    // Everything below is compiled once per column half Q (wave-uniform): the two halves differ in the patch columns they read
+    // and in the transform's coefficients, and a branch inside the chunk would sit between its loads.
+    auto run = [&](auto qc) {
+        constexpr int Q = decltype(qc)::value;
+        // input transform: lane = tile, wave = (channel tch of the chunk, column half Q)
+        const int tch = wave >> 1;
+        const int txo = tch * XT + 2 * (lane >> txs) * ew + 4 * (lane & ((1 << txs) - 1));  // patch columns d0..d5 at + 3 .. + 8
+        constexpr int teo = Q == 0 ? 3 : 8;  // Q = 0 needs d0..d4, Q = 1 needs d1..d5: d1..d4 is the aligned float4 at + 4
+        const int tvo = (tch * 2 + Q) * 3 * (WTILES * 4) + lane * 4;
+        float sv = 1.f, de[4], ee[4][3], oo[4][3];
+        sis_f32x4 dm[4];
+        auto t_read = [&](const float* xb, int r) {
+            dm[r] = lds_ld4(xb + r * ew + 4);
+            de[r] = xb[r * ew + teo];
+        };
+        auto t_col = [&](int r) {  // (d B4)[r][3 Q + jj]
+            const float a = dm[r].x, b = dm[r].y, c = dm[r].z, d = dm[r].w, e = de[r];
+            if (Q == 0) {
+                const float u = fmaf(-4.f, b, d), v = fmaf(-4.f, a, c);
+                ee[r][0] = fmaf(4.f, e, fmaf(-5.f, b, d));
+                ee[r][1] = u + v;
+                ee[r][2] = u - v;
+            } else {
+                const float u = d - b, v = c - a;
+                ee[r][0] = fmaf(2.f, v, u);
+                ee[r][1] = fmaf(-2.f, v, u);
+                ee[r][2] = fmaf(4.f, a, fmaf(-5.f, c, e));
+            }
+        };
+        auto t_row = [&](int jj) {  // B2^T (d B4), scaled by the style
+            oo[0][jj] = (ee[0][jj] - ee[2][jj]) * sv;
+            oo[1][jj] = (ee[1][jj] + ee[2][jj]) * sv;
+            oo[2][jj] = (ee[2][jj] - ee[1][jj]) * sv;
+            oo[3][jj] = (ee[1][jj] - ee[3][jj]) * sv;
+        };
+        auto t_write = [&](float* vw) {
+            *reinterpret_cast<sis_f32x4*>(vw) = sis_f32x4{oo[0][0], oo[0][1], oo[0][2], oo[1][0]};
+            *reinterpret_cast<sis_f32x4*>(vw + WTILES * 4) = sis_f32x4{oo[1][1], oo[1][2], oo[2][0], oo[2][1]};
+            *reinterpret_cast<sis_f32x4*>(vw + 2 * WTILES * 4) = sis_f32x4{oo[2][2], oo[3][0], oo[3][1], oo[3][2]};
+        };
+        // A / B operands of this lane: float4 k of row (channel 2 cp + half, Q, g) at column co / tile
+        const int aoff = (half * 2 + Q) * 3 * (WMBLK * 4) + (wm * 32 + l31) * 4;    // + (12 cp + g) * WMBLK * 4
+        const int voff = (half * 2 + Q) * 3 * (WTILES * 4) + (wn * 32 + l31) * 4;   // + (12 cp + g) * WTILES * 4
+
+        sis_f32x16 acc[12];  // plane e = 3 i + jj of this wave's column half
+        sis_f32x4 ou[2], ov[2];
+
+        for (int k = 0; k < tiles_per_wg; ++k) {
+#pragma unroll
+            for (int e = 0; e < 12; ++e)
+#pragma unroll
+                for (int j = 0; j < 16; ++j) acc[e][j] = 0.f;
+            // Lane-derived values of the tile start and of the epilogue come from copies of the thread index that the compiler
+            // cannot see through: it would otherwise compute them once and hold (spill) them across the chunk loop, whose
+            // registers are all taken.
+            int tp = tid;
+            asm volatile("" : "+v"(tp));
+            tile_setup(pt_first + k * pt_step, T, tp & 63);
+            if (k > 0) __syncthreads();  // everyone is done with the previous tile's exchange area and tail operands
+            // first DMA of the tile: weights chunk 0, input chunks 0 and 1
+#pragma unroll
+            for (int it = 0; it < 3; ++it) stage_u_piece(0, 0, it);
+#pragma unroll
+            for (int kx = 0; kx < 2; ++kx) stage_x_piece(0, 0, kx);
+#pragma unroll
+            for (int kx = 0; kx < 2; ++kx) stage_x_piece(min(CC, k_last), 1, kx);
+            // style row and layer-tail operands of the tile
+            for (int e = tp; e < p.Cin; e += WNTHR) Sl[e] = p.s[(int64_t)T.b * p.Cin + e];
+            if (tp < WMBLK) {
+                Dl[tp] = p.dscale[(int64_t)T.b * p.Cout + o0 + tp];
+                Bl[tp] = (p.fuse && p.bias) ? p.bias[o0 + tp] : 0.f;
+            }
+            {
+                const int tt_ = tp >> 3, e = tp & 7;
+                const int yy = T.h0 + 2 * (tt_ >> txs) + (e >> 2), xx = T.w0 + 4 * (tt_ & ((1 << txs) - 1)) + (e & 3);
+                float nv = 0.f;
+                if (p.fuse && p.noise && yy < p.H && xx < p.W) nv = noise_w0 * p.noise[(int64_t)T.b * p.noise_bstride + yy * p.W + xx];
+                Nl[tp] = nv;
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();  // chunk 0 (and input chunk 1) landed, styles visible
+            sv = Sl[tch];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) t_read(Xl + txo, r);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) t_col(r);
+#pragma unroll
+            for (int jj = 0; jj < 3; ++jj) t_row(jj);
+            t_write(Vl + tvo);
+            __syncthreads();  // V(0) visible
+            ou[0] = lds_ld4(Ul + aoff);
+            ov[0] = lds_ld4(Vl + voff);
+
+            // One straight-line block per chunk c (see modconv_wino2_kernel): DMA weights(c+1) and input(c+2), transform(c+1) -> V,
+            // 24 MFMAs on U(c) / V(c), one side item per MFMA slot, the barrier at slot W24_BAR with the first operands of c+1
+            // behind it.  Operand group g = 3 cp + (float4 of the 12 planes) is requested at the first MFMA of group g - 1.
+            auto chunk = [&](auto parity, const int ci0) {
+                constexpr int cur = decltype(parity)::value, nxt = cur ^ 1;
+                const int uci = ci0 + CC >= k_hi ? 0 : ci0 + CC;   // (the last chunk's prefetches are not used: any valid chunk)
+                const int xci = min(ci0 + 2 * CC, k_last);
+                const int tci = min(ci0 + CC, k_last);
+                const float* Ub = Ul + cur * UF + aoff;
+                const float* Vb = Vl + cur * VF + voff;
+                const float* xb = Xl + nxt * CC * XT + txo;
+                float* vw = Vl + nxt * VF + tvo;
+#pragma unroll
+                for (int sl = 0; sl < 24; ++sl) {
+                    const int g = sl >> 2, part = sl & 3, slot = g & 1;
+                    const int e = (g % 3) * 4 + part;
+                    const float ua = part == 0 ? ou[slot].x : part == 1 ? ou[slot].y : part == 2 ? ou[slot].z : ou[slot].w;
+                    const float va = part == 0 ? ov[slot].x : part == 1 ? ov[slot].y : part == 2 ? ov[slot].z : ov[slot].w;
+                    acc[e] = __builtin_amdgcn_mfma_f32_32x32x2f32(ua, va, acc[e], 0, 0, 0);
+                    if (part == 0 && g < 5) {
+                        ou[slot ^ 1] = lds_ld4(Ub + (12 * ((g + 1) / 3) + (g + 1) % 3) * WMBLK * 4);
+                        ov[slot ^ 1] = lds_ld4(Vb + (12 * ((g + 1) / 3) + (g + 1) % 3) * WTILES * 4);
+                    }
+                    if (sl == 2 || sl == 6 || sl == 10) stage_u_piece(uci, nxt, (sl - 2) >> 2);
+                    if (sl == 13) stage_x_piece(xci, cur, 0);
+                    if (sl == 15) stage_x_piece(xci, cur, 1);
+                    if (sl == 1) { sv = Sl[tci + tch]; t_read(xb, 0); t_read(xb, 1); }
+                    if (sl == 3) t_read(xb, 2);
+                    if (sl == 5) { t_read(xb, 3); t_col(0); }
+                    if (sl == 7) t_col(1);
+                    if (sl == 9) t_col(2);
+                    if (sl == 11) t_col(3);
+                    if (sl == 12) t_row(0);
+                    if (sl == 14) t_row(1);
+                    if (sl == 16) t_row(2);
+                    if (sl == 17) t_write(vw);
+                    if (sl == W24_BAR) {
+                        // by this slot the wave has issued its DMA pieces, written its V(c+1) and read its last operands of U(c) / V(c)
+                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        __syncthreads();
+                    }
+                    if (sl == 23) {  // group 0 of the next chunk (slot 0: group 4 is done)
+                        ou[0] = lds_ld4(Ul + nxt * UF + aoff);
+                        ov[0] = lds_ld4(Vl + nxt * VF + voff);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            };
+            for (int ci0 = 0; ci0 < k_hi; ci0 += 2 * CC) {  // Cin % 8 == 0 (host-checked): buffer parity is a compile-time constant
+                chunk(std::integral_constant<int, 0>(), ci0);
+                chunk(std::integral_constant<int, 1>(), ci0 + CC);
+            }
+
+            // ---- epilogue.  m[r][jj] = (A2^T M)[r][column 3 Q + jj], r = 0, 1.  Wave Q finalises the accumulator rows j in
+            // [8 Q, 8 Q + 8) and hands its m of the other 8 rows to its partner: [pair][sender Q][8 rows][6][64 lanes] over Ul / Vl.
+            float mine[8][2][3];
+            int te = tid;
+            asm volatile("" : "+v"(te));
+            const int lane = te & 63, l31 = te & 31, half = (te >> 5) & 1;
+            float* xch = lds + (wave >> 1) * (2 * 48 * 64);
+#pragma unroll
+            for (int jo = 0; jo < 16; ++jo) {  // the rows that leave first: they free their registers
+                const int j = (jo + 8 * (1 - Q)) & 15;
+#pragma unroll
+                for (int jj = 0; jj < 3; ++jj) {
+                    const float a0 = acc[jj][j], a1 = acc[3 + jj][j], a2 = acc[6 + jj][j], a3 = acc[9 + jj][j];
+                    const float m0 = a0 + a1 + a2, m1 = a1 - a2 - a3;
+                    if ((j >> 3) == Q) {
+                        mine[j & 7][0][jj] = m0;
+                        mine[j & 7][1][jj] = m1;
+                    } else {
+                        xch[(Q * 48 + (j & 7) * 6 + jj) * 64 + lane] = m0;
+                        xch[(Q * 48 + (j & 7) * 6 + 3 + jj) * 64 + lane] = m1;
+                    }
+                }
+            }
+            __syncthreads();
+
+            const int t = wn * 32 + l31;
+            const int oh = T.h0 + 2 * (t >> txs), ow = T.w0 + 4 * (t & ((1 << txs) - 1));
+            if (oh < p.H && ow < p.W) {
+                const float slope = p.fuse ? 0.2f : 1.f, gain = p.fuse ? 1.4142135623730951f : 1.f;
+                const int cl0 = wm * 32 + 16 * Q + 4 * half;  // row j = 8 Q + jr sits at channel cl0 + (jr & 3) + 8 * (jr >> 2)
+                float* obase = p.out + ((int64_t)T.b * p.Cout + o0 + cl0) * HW + oh * p.W + ow;
+                const float* xin = xch + (1 - Q) * 48 * 64 + lane;
+                const sis_f32x4 nz0 = lds_ld4(Nl + t * 8), nz1 = lds_ld4(Nl + t * 8 + 4);
+#pragma unroll
+                for (int jr = 0; jr < 8; ++jr) {
+                    const int ro = (jr & 3) + 8 * (jr >> 2);
+                    const float dd = Dl[cl0 + ro], bb = Bl[cl0 + ro];
+                    float theirs[2][3];
+#pragma unroll
+                    for (int e = 0; e < 6; ++e) theirs[e / 3][e % 3] = xin[(jr * 6 + e) * 64];
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) {
+                        const float* ma = Q == 0 ? mine[jr][r] : theirs[r];  // columns j = 0..2
+                        const float* mb = Q == 0 ? theirs[r] : mine[jr][r];  // columns j = 3..5
+                        const float sa = ma[1] + ma[2], da = ma[1] - ma[2], sb = mb[0] + mb[1], db = mb[0] - mb[1];
+                        const float y[4] = {(ma[0] + sa) + sb, fmaf(2.f, db, da), fmaf(4.f, sb, sa), fmaf(8.f, db, da) + mb[2]};
+                        const sis_f32x4 nz = r == 0 ? nz0 : nz1;
+                        const float nzv[4] = {nz.x, nz.y, nz.z, nz.w};
+                        float o[4];
+#pragma unroll
+                        for (int x = 0; x < 4; ++x) {
+                            float val = y[x] * dd;
+                            val += nzv[x];
+                            val += bb;
+                            o[x] = fmaxf(val, val * slope) * gain;  // = (val > 0 ? val : 0.2 val) * sqrt(2) when the tail is on
+                        }
+                        *reinterpret_cast<sis_f32x4*>(obase + (int64_t)ro * HW + r * p.W) = sis_f32x4{o[0], o[1], o[2], o[3]};
+                    }
+                }
+            }
+        }
+    };
+    if (q == 0) run(std::integral_constant<int, 0>());
+    else run(std::integral_constant<int, 1>());
+}
+
+}  // namespace
+
+extern "C" int sis_modconv_prepack_wino24(float* u, const float* w, int cout, int cin, void* stream) {
+    SIS_REQUIRE(u && w, "sis_modconv_prepack_wino24: null pointer");
+    SIS_REQUIRE(cout > 0 && cin > 0, "sis_modconv_prepack_wino24: bad sizes");
+    hipLaunchKernelGGL(wino24_prepack_kernel, dim3(sis_cdiv((int64_t)cout * cin, 256)), dim3(256), 0, (hipStream_t)stream, u, w, cout, cin);
+    SIS_CHECK_LAUNCH("sis_modconv_prepack_wino24");
+    return 0;
+}
+
+// The F(2x4,3x3) kernel takes a layer by (Cin, Cout, H, W) alone: 64-channel output blocks, 8-channel input steps, and a
+// map that one-sample tiles of 512 pixels (8 x 64 or 16 x 32) cover -- W > 16, H * W >= 512 after rounding up to powers of two.
+static int wino24_plan(ConvParams& p, int cin, int cout, int h, int w) {
+    if (cin <= 0 || cout <= 0 || h <= 0 || w <= 0) return -1;
+    if (cin % 8 || cout % WMBLK || h % 2 || w % 4) return -1;
+    if ((int64_t)cin * h * w * 4 >= ((int64_t)1 << 31) || (int64_t)cin * cout * 96 >= ((int64_t)1 << 31)) return -1;  // 32-bit DMA offsets
+    p.slab = nullptr; p.ksplit = 1; p.kchunk = cin; p.npos_tiles = 0; p.ncls = 0; p.nb_max = 0;
+    mc_add_class(p, 512, 2, 1, 0, h, 0, w, 64, 1);
+    const TileClass& tc = p.cls[0];
+    if (tc.nb != 1 || tc.th_log2 + tc.tw_log2 != 9 || tc.tw_log2 < 5) return -1;
+    if (((1 << tc.th_log2) + 2) * ((1 << tc.tw_log2) + 8) != W24_XT) return -1;
+    const size_t lds = (size_t)(2 * W24_UF + 2 * W24_VF + 2 * W24_CC * W24_XT + cin + 2 * WMBLK + WTILES * 8) * sizeof(float);
+    if (lds > 160 * 1024) return -1;
+    return (int)lds;
+}
+
+extern "C" int sis_modconv_wino24_eligible(int cin, int cout, int h, int w) {
+    ConvParams p;
+    return wino24_plan(p, cin, cout, h, w) > 0 ? 1 : 0;
+}
+
+extern "C" int sis_modconv2d_wino24(float* out, const float* x, const float* u24, const float* s, const float* dscale,
+                                    const float* noise, int64_t noise_batch_stride, const float* noise_weight, const float* bias,
+                                    int batch, int cin, int cout, int h, int w, int fuse_act, int tiles_per_wg, void* stream) {
+    if (batch == 0) return 0;
+    SIS_REQUIRE(out && x && u24 && s && dscale, "sis_modconv2d_wino24: null pointer");
+    SIS_REQUIRE(batch > 0, "sis_modconv2d_wino24: non-positive size");
+    if (noise) SIS_REQUIRE(noise_weight, "sis_modconv2d_wino24: noise given without noise_weight");
+    ConvParams p;
+    const int lds = wino24_plan(p, cin, cout, h, w);
+    SIS_REQUIRE(lds > 0, "sis_modconv2d_wino24: shape %dx%d, %d -> %d not eligible (sis_modconv_wino24_eligible)", h, w, cin, cout);
+    SIS_REQUIRE((int64_t)batch * (cin > cout ? cin : cout) * h * w < ((int64_t)1 << 31), "sis_modconv2d_wino24: tensor too large");
+    SIS_REQUIRE(((((uintptr_t)x | (uintptr_t)u24 | (uintptr_t)out) & 15) == 0) && (!noise || ((uintptr_t)noise & 3) == 0),
+                "sis_modconv2d_wino24: pointers must be 16-byte aligned");
+    p.x = x; p.wpk = u24; p.s = s; p.dscale = dscale; p.noise = noise; p.noise_w = noise_weight; p.bias = bias;
+    p.out = out; p.noise_bstride = noise_batch_stride;
+    p.B = batch; p.Cin = cin; p.Cout = cout; p.H = h; p.W = w; p.OH = h; p.OW = w; p.ORS = w; p.fuse = fuse_act != 0;
+    p.cout_vec4 = 1;
+    const TileClass& tc = p.cls[0];
+    const int64_t tiles = (int64_t)batch * tc.nth * tc.ntw;  // one-sample tiles
+    p.npos_tiles = (int)tiles;
+    const int n_co = cout / WMBLK;
+    const int64_t blocks = tiles * n_co;
+    SIS_REQUIRE(blocks < ((int64_t)1 << 31), "sis_modconv2d_wino24: bad grid");
+    // pixel tiles per workgroup: as many as keep >= 1024 workgroups in flight (scheduling only: every tile is computed the same
+    // way whichever workgroup walks it); tiles_per_wg > 0 is the tests' override
+    int tpw = 1;
+    if (tiles_per_wg > 0) {
+        SIS_REQUIRE(tiles % tiles_per_wg == 0, "sis_modconv2d_wino24: %d tiles per workgroup do not divide %lld tiles", tiles_per_wg, (long long)tiles);
+        tpw = tiles_per_wg;
+    } else {
+        while (tpw * 2 <= 16 && tiles % (tpw * 2) == 0 && blocks / (tpw * 2) >= 1024) tpw *= 2;
+    }
+    const int64_t grid = blocks / tpw;
+    const int xcd_group = (double)cin * cout * 24 * sizeof(float) <= 5.0 * 1048576.0 && n_co > 1 && grid % (8 * n_co) == 0;
+    static bool have_attr = false;
+    if (!have_attr) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&modconv_wino24_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return sis_fail("modconv: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
+        have_attr = true;
+    }
+    sis_kernel_name = "modconv_wino24_kernel";
+    hipLaunchKernelGGL(modconv_wino24_kernel, dim3((unsigned)grid), dim3(WNTHR), (size_t)lds, (hipStream_t)stream, p, tpw, xcd_group);
+    SIS_CHECK_LAUNCH("modconv_wino24_kernel");
+    return 0;
+}

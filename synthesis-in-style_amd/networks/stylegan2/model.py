@@ -160,12 +160,15 @@ class ModulatedConv2d(nn.Module):
         key = (w.data_ptr(), w._version, w.device)
         if self._pack_key != key:
             self._pack = sis_hip.modconv_prepack(w.detach())
-            # stride-1 3x3 layers also keep the Winograd F(2x2,3x3) transform of the weights (2.25x fewer MFMA
-            # FLOPs); SIS_WINOGRAD=0 selects the direct kernel everywhere (bisecting / A-B runs)
-            self._wino = None
-            if (self.kernel_size == 3 and not self.upsample and not self.downsample and self.in_channel % 8 == 0
-                    and self.out_channel % 4 == 0 and os.environ.get("SIS_WINOGRAD", "1") != "0"):
-                self._wino = sis_hip.modconv_prepack_wino(w.detach())
+            # stride-1 3x3 layers also keep a Winograd transform of the weights: the 24 planes of F(2x4,3x3) (3x fewer MFMA
+            # FLOPs) for the map sizes that kernel takes, the 16 planes of F(2x2,3x3) (2.25x fewer) for the others.  Which of the
+            # two a layer needs depends on the map it is called with, so each is packed at its first use (winograd_operand)
+            # and a layer holds no planes it never runs on.  SIS_WINOGRAD=0 selects the direct kernel everywhere,
+            # SIS_WINO24=0 F(2x2,3x3) wherever a Winograd kernel runs (bisecting / A-B runs); both are read here, per pack.
+            self._wino = self._wino24 = None
+            self._wino_on = (self.kernel_size == 3 and not self.upsample and not self.downsample and self.in_channel % 8 == 0
+                             and self.out_channel % 4 == 0 and os.environ.get("SIS_WINOGRAD", "1") != "0")
+            self._wino24_on = self._wino_on and os.environ.get("SIS_WINO24", "1") != "0"
             # up-convolutions keep the 16 transformed planes of the fast-FIR kernel (25 instead of 36 multiplies per 2 x 2
             # input positions, csrc/modconv_upfir.hip); the launch falls back to the 4-phase kernel below 32 x 32
             self._fir = None
@@ -176,7 +179,19 @@ class ModulatedConv2d(nn.Module):
 
     def wino_weights(self):
         self.packed_weights()
+        if self._wino is None and self._wino_on:
+            self._wino = sis_hip.modconv_prepack_wino(self.weight.detach())
         return self._wino
+
+    def winograd_operand(self, h, w):
+        """The keyword of sis_hip.modconv2d that carries this layer's transformed weights for an h x w map: the F(2x4,3x3) planes
+        where that kernel takes (Cin, Cout, h, w) -- the batch plays no part -- and the F(2x2,3x3) planes (or None) otherwise."""
+        self.packed_weights()
+        if self._wino24_on and sis_hip.modconv_wino24_eligible(self.in_channel, self.out_channel, h, w):
+            if self._wino24 is None:
+                self._wino24 = sis_hip.modconv_prepack_wino24(self.weight.detach())
+            return {"wino24_u": self._wino24}
+        return {"wino_u": self.wino_weights()}
 
     def fir_weights(self):
         self.packed_weights()
@@ -198,7 +213,7 @@ class ModulatedConv2d(nn.Module):
         wpk, s, dscale = self.modulate(style)
         if self.upsample:
             return self.blur(sis_hip.modconv2d_up(input, wpk, s, dscale))
-        return sis_hip.modconv2d(input, wpk, s, dscale, self.kernel_size, wino_u=self.wino_weights())
+        return sis_hip.modconv2d(input, wpk, s, dscale, self.kernel_size, **self.winograd_operand(*input.shape[2:]))
 
     # ---- differentiable path (GAN training / latent projection) ---------------------------------
     def _forward_autograd(self, input, style):
@@ -310,7 +325,7 @@ class StyledConv(nn.Module):
         if noise is None:
             noise = input.new_empty(b, 1, h, w).normal_()
         return sis_hip.modconv2d(input, wpk, s, dscale, conv.kernel_size, noise, self.noise.weight, act.bias,
-                                 fuse_act=True, wino_u=conv.wino_weights(), out=out)
+                                 fuse_act=True, out=out, **conv.winograd_operand(h, w))
 
 
 class ToRGB(nn.Module):

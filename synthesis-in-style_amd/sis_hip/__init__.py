@@ -44,6 +44,9 @@ _SIGNATURES = {
     "sis_modconv2d": ([_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp] + [_i] * 7 + [_vp, _vp, _i64, _vp], _i),
     "sis_head_gemm_tile": ([], _i),
     "sis_modconv_prepack_wino": ([_vp, _vp, _i, _i, _vp], _i),
+    "sis_modconv_prepack_wino24": ([_vp, _vp, _i, _i, _vp], _i),
+    "sis_modconv_wino24_eligible": ([_i] * 4, _i),
+    "sis_modconv2d_wino24": ([_vp] * 6 + [_i64, _vp, _vp] + [_i] * 7 + [_vp], _i),
     "sis_last_kernel": ([], ctypes.c_char_p),
     "sis_conv3x3_prepack": ([_vp, _vp, _i, _i, _i, _vp], _i),
     "sis_conv3x3_prepack_both": ([_vp, _vp, _vp, _i, _i, _vp], _i),
@@ -508,6 +511,23 @@ def modconv_prepack_wino(weight):
     return u
 
 
+def modconv_prepack_wino24(weight):
+    """[1, Cout, Cin, 3, 3] -> Winograd F(2x4,3x3) transformed weights G2 g G4^T, [Cin, 2 column halves, 3, Cout, 4]."""
+    w = _f32(weight, "weight")
+    _, cout, cin, k, _ = w.shape
+    if k != 3:
+        raise RuntimeError("the Winograd transform is for 3x3 kernels")
+    u = torch.empty((cin, 2, 3, cout, 4), dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        _check(lib().sis_modconv_prepack_wino24(_ptr(u), _ptr(w), cout, cin, _stream()), "sis_modconv_prepack_wino24")
+    return u
+
+
+def modconv_wino24_eligible(cin, cout, h, w):
+    """True when the F(2x4,3x3) kernel takes a stride-1 3x3 layer of this shape; the batch size plays no part."""
+    return bool(lib().sis_modconv_wino24_eligible(int(cin), int(cout), int(h), int(w)))
+
+
 def conv3x3_supported(x, weight, dilation=1):
     """True when the plain Winograd path takes this layer in both directions (forward and data gradient): 3x3
     kernel, float32 NCHW; a dilation d is run as d*d independent convolutions of the stride-d sub-images, so the
@@ -906,12 +926,27 @@ def _out_or_new(out, shape, device, what):
     return out
 
 
-def modconv2d(x, wpk, s, dscale, ksize, noise=None, noise_weight=None, bias=None, fuse_act=False, wino_u=None, out=None):
+def modconv2d(x, wpk, s, dscale, ksize, noise=None, noise_weight=None, bias=None, fuse_act=False, wino_u=None, out=None,
+              wino24_u=None, wino24_tiles_per_wg=0):
+    """``wino24_u`` (modconv_prepack_wino24): the layer runs on the F(2x4,3x3) kernel where modconv_wino24_eligible says so,
+    whatever the batch; other shapes take the path they took without it.  ``wino24_tiles_per_wg``: tests only."""
     x = _f32(x, "input")
     batch, cin, h, w = x.shape
     cout = wpk.shape[2]
     noise, nbs = _noise_args(noise, batch, h, w)
     out = _out_or_new(out, (batch, cout, h, w), x.device, "modconv2d")
+    if wino24_u is not None and ksize == 3 and batch > 0 and modconv_wino24_eligible(cin, cout, h, w):
+        with torch.cuda.device(x.device):
+            # FLOPs recorded as direct form x 3/4: bench.py prices every kernel whose name contains "wino" at 16/36 of the
+            # recorded count, and 3/4 x 16/36 = 24/72 is what this kernel executes.
+            _check(_launch(None,
+                           0.75 * 2.0 * batch * cout * cin * 9 * h * w,
+                           4.0 * (x.numel() + out.numel() + wino24_u.numel()),
+                           lambda: lib().sis_modconv2d_wino24(_ptr(out), _ptr(x), _ptr(wino24_u), _ptr(s), _ptr(dscale), _ptr(noise),
+                                                              nbs, _ptr(noise_weight), _ptr(bias), batch, cin, cout, h, w,
+                                                              int(bool(fuse_act)), int(wino24_tiles_per_wg), _stream())),
+                   "sis_modconv2d_wino24")
+        return out
     ws = _workspace(x.device)
     wino = wino_u is not None and ksize == 3 and h % 2 == 0 and w % 2 == 0 and cin % 8 == 0 and cout % 4 == 0
     with torch.cuda.device(x.device):

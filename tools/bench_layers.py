@@ -1,5 +1,7 @@
 """Per-layer timing of the generator's convolution kernels (development tool, GPU box).
-usage: python tools/bench_layers.py [batch] [reps]   -> one line per layer: ms, TFLOP/s"""
+usage: python tools/bench_layers.py [batch] [reps] [layer, e.g. conv64]   -> one line per layer: ms, TFLOP/s
+SIS_WINOGRAD=0: direct kernel; SIS_WINO24=0: F(2x2,3x3) where F(2x4,3x3) would run (the generator's own switches).
+SIS_LAYER_LAUNCHES=1: per-launch times instead (median, min, max), the form the per-layer selection rule of DESIGN 3.2 reads."""
 import os
 import sys
 
@@ -15,6 +17,8 @@ B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 REPS = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 only = sys.argv[3] if len(sys.argv) > 3 else ""
 WINO = os.environ.get("SIS_WINOGRAD", "1") != "0"
+WINO24 = WINO and os.environ.get("SIS_WINO24", "1") != "0"
+LAUNCHES = os.environ.get("SIS_LAYER_LAUNCHES", "0") == "1"
 dev = torch.device("cuda:0")
 layers = [("conv", 512, 512, 4), ("up", 512, 512, 4), ("conv", 512, 512, 8), ("up", 512, 512, 8),
           ("conv", 512, 512, 16), ("up", 512, 512, 16), ("conv", 512, 512, 32), ("up", 512, 512, 32),
@@ -33,11 +37,27 @@ for kind, cin, cout, h in layers:
     noise = torch.randn(1, 1, oh, oh, device=dev)
     nw = torch.full((1,), 0.1, device=dev)
     bias = torch.zeros(cout, device=dev)
-    u = sis_hip.modconv_prepack_wino(w) if (WINO and kind == "conv") else None
-    f = (lambda: sis_hip.modconv2d(x, wpk, s, ds, 3, noise, nw, bias, fuse_act=True, wino_u=u)) if kind == "conv" else \
+    if kind == "conv" and WINO24 and sis_hip.modconv_wino24_eligible(cin, cout, h, h):
+        kw = {"wino24_u": sis_hip.modconv_prepack_wino24(w)}
+    else:
+        kw = {"wino_u": sis_hip.modconv_prepack_wino(w) if (WINO and kind == "conv") else None}
+    f = (lambda: sis_hip.modconv2d(x, wpk, s, ds, 3, noise, nw, bias, fuse_act=True, **kw)) if kind == "conv" else \
         (lambda: sis_hip.modconv2d_up(x, wpk, s, ds))
     f()
     torch.cuda.synchronize()
+    if LAUNCHES:
+        ts = []
+        for _ in range(REPS + 2):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            f()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        ts = sorted(ts[2:])
+        print(f"{kind:5s} {cin:4d}->{cout:4d} @{h:3d}  {sis_hip.lib().sis_last_kernel().decode():24s} median {ts[len(ts) // 2]:8.3f} ms  "
+              f"min {ts[0]:8.3f}  max {ts[-1]:8.3f}", flush=True)
+        continue
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(REPS):
