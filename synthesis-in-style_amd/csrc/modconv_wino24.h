@@ -27,6 +27,14 @@ constexpr int W24_VF = W24_CC * 24 * WTILES;    // floats of a V chunk       [ch
 constexpr int W24_XT = 720;                     // floats per channel of the staged input tile: 10 x 72 or 18 x 40
 constexpr int W24_XP = 3;                       // 64-lane float4 pieces of a channel (the last one shifted back to end with the tile)
 constexpr int W24_BAR = 19;                     // MFMA slot of a chunk behind which its barrier sits
+// MFMA slots of a chunk's five DMA instructions, all in front of the barrier: the two input pieces first (they come from HBM or
+// from the L2 of another XCD, and the barrier's vmcnt(0) waits for them), the three weight rows (L2-resident) behind them.  With
+// the input pieces at slots 13 and 15 -- four to six MFMAs in front of the wait -- every chunk stood at its barrier for the rest
+// of their latency: 1.77 / 1.93 / 2.02 ms per launch at 64^2 / 128^2 / 256^2 against 1.65 / 1.74 / 1.82 ms
+// (profiles/wino24_tile_pipeline.txt).  The piece goes to Xl[cur], whose last readers were the transforms of the previous chunk,
+// in front of that chunk's barrier.
+constexpr int W24_SX[2] = {2, 4};
+constexpr int W24_SU[3] = {6, 8, 10};
 
 // u[ci][q][g][co][k]: plane e = 3 i + jj = 4 g + k of column half q (j = 3 q + jj), from w[co][ci][3][3]
 __global__ __launch_bounds__(256) void wino24_prepack_kernel(float* __restrict__ u, const float* __restrict__ w, int cout, int cin) {
@@ -59,6 +67,22 @@ __global__ __launch_bounds__(256) void wino24_prepack_kernel(float* __restrict__
         }
     }
 }
+
+#ifdef SIS_WINO_TRACE
+// Development build only (tools/wino_trace.sh, tools/wino24_trace.py): per-wave cycle stamps around the tile boundary, 4 workgroups.
+// Slots of tile k: 0 chunk loop entered, 1 chunk loop left, 2 exchange written and its barrier passed, 3 stores issued,
+// 4 first DMA and operand loads of the tile issued, 5 vmcnt(0) and barrier passed.
+__device__ unsigned int sis_wino24_trace_tile[TR_NWG][8][16][8];
+#define W24_TRACE(slot)                                                                                           \
+    do {                                                                                                          \
+        if (blockIdx.x >= TR_WG0 && blockIdx.x < TR_WG0 + TR_NWG && k < 16) {                                     \
+            const unsigned int now_ = (unsigned int)__builtin_readcyclecounter();                                 \
+            if ((threadIdx.x & 63) == 0) sis_wino24_trace_tile[blockIdx.x - TR_WG0][wave][k][slot] = now_;        \
+        }                                                                                                         \
+    } while (0)
+#else
+#define W24_TRACE(slot) do {} while (0)
+#endif
 
 __global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvParams p, const int tiles_per_wg, const int xcd_group) {
     constexpr int CC = W24_CC, UF = W24_UF, VF = W24_VF, XT = W24_XT;
@@ -207,8 +231,10 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvPara
                 if (p.fuse && p.noise && yy < p.H && xx < p.W) nv = noise_w0 * p.noise[(int64_t)T.b * p.noise_bstride + yy * p.W + xx];
                 Nl[tp] = nv;
             }
+            W24_TRACE(4);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();  // chunk 0 (and input chunk 1) landed, styles visible
+            W24_TRACE(5);
             sv = Sl[tch];
 #pragma unroll
             for (int r = 0; r < 4; ++r) t_read(Xl + txo, r);
@@ -220,6 +246,7 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvPara
             __syncthreads();  // V(0) visible
             ou[0] = lds_ld4(Ul + aoff);
             ov[0] = lds_ld4(Vl + voff);
+            W24_TRACE(0);
 
             // One straight-line block per chunk c (see modconv_wino2_kernel): DMA weights(c+1) and input(c+2), transform(c+1) -> V,
             // 24 MFMAs on U(c) / V(c), one side item per MFMA slot, the barrier at slot W24_BAR with the first operands of c+1
@@ -244,9 +271,12 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvPara
                         ou[slot ^ 1] = lds_ld4(Ub + (12 * ((g + 1) / 3) + (g + 1) % 3) * WMBLK * 4);
                         ov[slot ^ 1] = lds_ld4(Vb + (12 * ((g + 1) / 3) + (g + 1) % 3) * WTILES * 4);
                     }
-                    if (sl == 2 || sl == 6 || sl == 10) stage_u_piece(uci, nxt, (sl - 2) >> 2);
-                    if (sl == 13) stage_x_piece(xci, cur, 0);
-                    if (sl == 15) stage_x_piece(xci, cur, 1);
+#pragma unroll
+                    for (int kx = 0; kx < 2; ++kx)
+                        if (sl == W24_SX[kx]) stage_x_piece(xci, cur, kx);
+#pragma unroll
+                    for (int it = 0; it < 3; ++it)
+                        if (sl == W24_SU[it]) stage_u_piece(uci, nxt, it);
                     if (sl == 1) { sv = Sl[tci + tch]; t_read(xb, 0); t_read(xb, 1); }
                     if (sl == 3) t_read(xb, 2);
                     if (sl == 5) { t_read(xb, 3); t_col(0); }
@@ -273,6 +303,7 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvPara
                 chunk(std::integral_constant<int, 0>(), ci0);
                 chunk(std::integral_constant<int, 1>(), ci0 + CC);
             }
+            W24_TRACE(1);
 
             // ---- epilogue.  m[r][jj] = (A2^T M)[r][column 3 Q + jj], r = 0, 1.  Wave Q finalises the accumulator rows j in
             // [8 Q, 8 Q + 8) and hands its m of the other 8 rows to its partner: [pair][sender Q][8 rows][6][64 lanes] over Ul / Vl.
@@ -298,6 +329,7 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvPara
                 }
             }
             __syncthreads();
+            W24_TRACE(2);
 
             const int t = wn * 32 + l31;
             const int oh = T.h0 + 2 * (t >> txs), ow = T.w0 + 4 * (t & ((1 << txs) - 1));
@@ -334,6 +366,7 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvPara
                     }
                 }
             }
+            W24_TRACE(3);
         }
     };
     if (q == 0) run(std::integral_constant<int, 0>());
@@ -341,6 +374,12 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvPara
 }
 
 }  // namespace
+
+#ifdef SIS_WINO_TRACE
+extern "C" int sis_wino24_trace_tile_read(unsigned int* host) {
+    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(sis_wino24_trace_tile), sizeof(unsigned int) * TR_NWG * 8 * 16 * 8);
+}
+#endif
 
 extern "C" int sis_modconv_prepack_wino24(float* u, const float* w, int cout, int cin, void* stream) {
     SIS_REQUIRE(u && w, "sis_modconv_prepack_wino24: null pointer");

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Development tool: builds lib/libsis_hip_trace.so (the product library with -DSIS_WINO_TRACE in modconv_wino.hip).
-# The trace build stamps the cycle counter four times per chunk per wave in 4 workgroups (tools/wino_trace.py reads it).
+# The trace build stamps the cycle counter four times per chunk per wave in 4 workgroups (tools/wino_trace.py reads it), and around
+# the tile boundary of modconv_wino24_kernel (tools/wino24_trace.py).
 set -e
 cd "$(dirname "$0")/../synthesis-in-style_amd/csrc"
 make -j8 >/dev/null
