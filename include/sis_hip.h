@@ -752,6 +752,31 @@ int sis_pixel_ensemble_head(const int64_t* full, const int64_t* proj, int nproj,
                             int hidden1, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DatasetGAN training (csrc/pixel_ensemble_train.h): one step of every member of a narrow PixelEnsembleClassifier
+ * (hidden widths 128 and 32, 2..31 classes, 1..10 members) on `npix` >= 2 pixels; fp32, deterministic (fixed summation orders,
+ * no atomics).  The members are batched along the column axis: w1 [members*128][features], b1 / g1 / be1 [members*128],
+ * w2 [members][32][128], b2 / g2 / be2 [members*32], w3 [members][classes][32], b3 [members][classes].
+ * _workspace_bytes: bytes of `workspace` for _tail (piece 0) or _l1_wgrad (piece 1); -1 for an unsupported shape.
+ * _gather: x[npix][features] from `layers` resident activation layers [images][c][res][res]; the table holds 4 int64 per layer
+ *   {pointer, c, res, first column}, once on the HOST (checked) and once on the DEVICE (read by the kernel); pixels int32
+ *   [npix][3] = (image, y, x); bilinear, align_corners=False, the source indices of _head; res == size is a plain read.
+ * _l1_forward: a1[npix][members*128] = relu(x w1^T + b1).
+ * _tail: BatchNorm 1 (batch statistics), layer 2, BatchNorm 2, layer 3, mean cross-entropy and their backward.
+ *   params {g1, be1, w2, b2, g2, be2, w3, b3}; running {mean1, var1, mean2, var2, tracked1, tracked2} (entries may be null;
+ *   momentum 0.1, unbiased variance; tracked: int64 [members], += 1); grads {dg1, dbe1, dw2, db2, dg2, dbe2, dw3, db3} (the order of params);
+ *   dz1[npix][members*128] = d loss / d (x w1^T + b1); loss[members]; logits (optional, tests) [members][npix][classes].
+ * _l1_wgrad: dw1[members*128][features] = dz1^T x (npix in slabs added in slab order), db1 = the column sums of dz1. */
+int64_t sis_pe_train_workspace_bytes(int piece, int pixels, int features, int members);
+int sis_pe_train_gather(const int64_t* table_host, const int64_t* table_dev, int layers, const int32_t* pixels, float* x, int npix,
+                        int features, int size, int images, void* stream);
+int sis_pe_train_l1_forward(const float* x, const float* w1, const float* b1, float* a1, int npix, int features, int members,
+                            void* stream);
+int sis_pe_train_tail(const float* a1, const int64_t* labels, const void* const* params, void* const* running, void* const* grads,
+                      float* dz1, float* loss, float* logits, void* workspace, int npix, int members, int classes, void* stream);
+int sis_pe_train_l1_wgrad(const float* dz1, const float* x, float* dw1, float* db1, void* workspace, int npix, int features,
+                          int members, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fitting spherical k-means activation catalogs (csrc/spherical_kmeans.hip): the arithmetic of
  * MiniBatchSphericalKMeans.fit (reference segmentation/gan_local_edit/spherical_kmeans.py:161-312) as called by
  * FactorCatalog.fit_predict (factor_catalog.py:64-67) from create_semantic_segmentation.py:114-129, on the NCHW activation

@@ -22,6 +22,7 @@
 // Every output element is computed by the same instruction sequence whatever the batch size or tile position: the labels of
 // an image do not depend on the batch it is labelled in.
 #include "sis_device.h"
+#include <algorithm>
 
 namespace {
 
@@ -50,6 +51,16 @@ struct PeProjParams {
 // Base pointer of the 32 channels [k0, k0 + 32) of sample b (a chunk lies inside one layer).
 __device__ __forceinline__ const float* chunk_base(const PeLayers& L, int k0, int b, int hw) {
     return k0 < L.c0 ? L.a0 + ((int64_t)b * L.c0 + k0) * hw : L.a1 + ((int64_t)b * L.c1 + (k0 - L.c0)) * hw;
+}
+
+// Bilinear source of destination index d (align_corners=False): src = (d + 0.5) * scale - 0.5 clamped at 0, scale = res / S;
+// lower neighbour i0, upper neighbour i1 clamped at res - 1, weight l1 of the upper one.  The label pass and the training
+// gather (pixel_ensemble_train.h) both take their taps from here: they see the same features.
+__device__ __forceinline__ void pe_bilinear_src(int d, float scale, int res, int& i0, int& i1, float& l1) {
+    const float s = fmaxf(((float)d + 0.5f) * scale - 0.5f, 0.f);
+    i0 = (int)s;
+    i1 = i0 + (i0 < res - 1 ? 1 : 0);
+    l1 = s - (float)i0;
 }
 
 // ------------------------------------------------------------------------------------------------ projection
@@ -251,10 +262,11 @@ __global__ __launch_bounds__(256) void pe_head_kernel(PeHeadParams p) {
             if (g >= p.nproj) break;
             const int res = p.pres[g];
             const float scale = (float)res / (float)p.S;
-            const float sy = fmaxf(((float)y + 0.5f) * scale - 0.5f, 0.f), sx = fmaxf(((float)x + 0.5f) * scale - 0.5f, 0.f);
-            const int y0 = (int)sy, x0 = (int)sx;
-            const int y1 = y0 + (y0 < res - 1 ? 1 : 0), x1 = x0 + (x0 < res - 1 ? 1 : 0);
-            const float ly1 = sy - (float)y0, ly0 = 1.f - ly1, lx1 = sx - (float)x0, lx0 = 1.f - lx1;
+            int y0, y1, x0, x1;
+            float ly1, lx1;
+            pe_bilinear_src(y, scale, res, y0, y1, ly1);
+            pe_bilinear_src(x, scale, res, x0, x1, lx1);
+            const float ly0 = 1.f - ly1, lx0 = 1.f - lx1;
             const float* base = p.proj[g] + (int64_t)b * res * res * p.M + n * H1 + 4 * h;
             const float* r00 = base + (int64_t)(y0 * res + x0) * p.M;
             const float* r01 = base + (int64_t)(y0 * res + x1) * p.M;
@@ -395,6 +407,8 @@ bool unpack_layers(PeLayers& L, const int64_t* d) {   // {act0, act1, ch0, ch1};
     return (L.c0 == 0 || (L.a0 && !(d[0] & 15))) && (L.c1 == 0 || (L.a1 && !(d[1] & 15)));
 }
 
+#include "pixel_ensemble_train.h"
+
 }  // namespace
 
 extern "C" int sis_pixel_ensemble_project(const int64_t* groups, int ngroups, int batch, int m, void* stream) {
@@ -461,6 +475,132 @@ extern "C" int sis_pixel_ensemble_head(const int64_t* full, const int64_t* proj,
     } else {
         hipLaunchKernelGGL((pe_head_kernel<256, 128, 64>), grid, dim3(256), 0, st, p);
         SIS_CHECK_LAUNCH("pe_head_kernel<256,128,64>");
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ training (pixel_ensemble_train.h)
+extern "C" int64_t sis_pe_train_workspace_bytes(int piece, int pixels, int features, int members) {
+    if (!pt_shape_ok(pixels, members) || features <= 0 || features % PE_KC) return -1;
+    if (piece == 0) return pt_tail_ws(pixels, members).total;
+    if (piece == 1) return pt_wgrad_ws(pixels, features, members);
+    return -1;
+}
+
+extern "C" int sis_pe_train_gather(const int64_t* table_host, const int64_t* table_dev, int layers, const int32_t* pixels, float* x,
+                                   int npix, int features, int size, int images, void* stream) {
+    if (npix <= 0) return 0;
+    SIS_REQUIRE(table_host && table_dev && pixels && x, "sis_pe_train_gather: null pointer");
+    SIS_REQUIRE(layers >= 1 && layers <= PT_MAX_LAYERS, "sis_pe_train_gather: %d layers (1..%d)", layers, PT_MAX_LAYERS);
+    SIS_REQUIRE(size >= 1 && (size & (size - 1)) == 0 && images >= 1, "sis_pe_train_gather: output size %d (a power of two), %d images",
+                size, images);
+    SIS_REQUIRE(features > 0 && features % PE_KC == 0, "sis_pe_train_gather: %d features (a multiple of %d)", features, PE_KC);
+    int64_t cols = 0;
+    for (int l = 0; l < layers; ++l) {   // {activations, channels, resolution, first column}: the columns tile [0, features)
+        const int64_t* d = table_host + 4 * l;
+        SIS_REQUIRE(d[0] && !(d[0] & 3) && d[1] >= 1 && d[3] == cols, "sis_pe_train_gather: layer %d: bad pointer, channel count or column", l);
+        SIS_REQUIRE(d[2] >= 1 && d[2] <= size && size % d[2] == 0, "sis_pe_train_gather: layer %d: resolution %d is no power-of-two "
+                    "fraction of %d", l, (int)d[2], size);
+        SIS_REQUIRE((int64_t)images * d[1] * d[2] * d[2] < (1LL << 40), "sis_pe_train_gather: layer %d too large", l);
+        cols += d[1];
+    }
+    SIS_REQUIRE(cols == features, "sis_pe_train_gather: the layers have %lld channels, the features %d", (long long)cols, features);
+    hipLaunchKernelGGL(pe_gather_kernel, dim3(npix, layers), dim3(256), 0, (hipStream_t)stream, table_dev, pixels, x, features, size, images);
+    SIS_CHECK_LAUNCH("pe_gather_kernel");
+    return 0;
+}
+
+extern "C" int sis_pe_train_l1_forward(const float* x, const float* w1, const float* b1, float* a1, int npix, int features, int members,
+                                       void* stream) {
+    SIS_REQUIRE(x && w1 && b1 && a1, "sis_pe_train_l1_forward: null pointer");
+    SIS_REQUIRE(npix >= 1 && npix <= (1 << 21), "sis_pe_train_l1_forward: %d pixels", npix);
+    SIS_REQUIRE(members >= 1 && members <= 10, "sis_pe_train_l1_forward: %d members (1..10)", members);
+    SIS_REQUIRE(features > 0 && features % PE_KC == 0, "sis_pe_train_l1_forward: %d features (a multiple of %d)", features, PE_KC);
+    SIS_REQUIRE(!(((intptr_t)x | (intptr_t)w1) & 15), "sis_pe_train_l1_forward: pointers must be 16-byte aligned");
+    hipLaunchKernelGGL(pe_l1_fwd_kernel, dim3(sis_cdiv(npix, PT_ROWS), members), dim3(256), 0, (hipStream_t)stream, x, w1, b1, a1, npix,
+                       features, members * PT_H1);
+    SIS_CHECK_LAUNCH("pe_l1_fwd_kernel");
+    return 0;
+}
+
+// params: {g1, be1, w2, b2, g2, be2, w3, b3}; running: {mean1, var1, mean2, var2, tracked1, tracked2} (each may be null);
+// grads: the gradients of params, in the same order
+extern "C" int sis_pe_train_tail(const float* a1, const int64_t* labels, const void* const* params, void* const* running,
+                                 void* const* grads, float* dz1, float* loss, float* logits, void* workspace, int npix, int members,
+                                 int classes, void* stream) {
+    SIS_REQUIRE(a1 && labels && params && running && grads && dz1 && loss && workspace, "sis_pe_train_tail: null pointer");
+    SIS_REQUIRE(npix >= 2, "sis_pe_train_tail: %d pixels: BatchNorm in training mode needs more than one row", npix);
+    SIS_REQUIRE(pt_shape_ok(npix, members), "sis_pe_train_tail: %d pixels, %d members (1..10)", npix, members);
+    SIS_REQUIRE(classes >= 2 && classes < PT_CP, "sis_pe_train_tail: %d classes (2..31)", classes);
+    for (int i = 0; i < 8; ++i) SIS_REQUIRE(params[i] && grads[i], "sis_pe_train_tail: null parameter or gradient %d", i);
+    SIS_REQUIRE(!((intptr_t)workspace & 255), "sis_pe_train_tail: the workspace must be 256-byte aligned");
+    const float *g1 = (const float*)params[0], *be1 = (const float*)params[1], *w2 = (const float*)params[2], *b2 = (const float*)params[3];
+    const float *g2 = (const float*)params[4], *be2 = (const float*)params[5], *w3 = (const float*)params[6], *b3 = (const float*)params[7];
+    float *dg1 = (float*)grads[0], *dbe1 = (float*)grads[1], *dw2 = (float*)grads[2], *db2 = (float*)grads[3];
+    float *dg2 = (float*)grads[4], *dbe2 = (float*)grads[5], *dw3 = (float*)grads[6], *db3 = (float*)grads[7];
+    const PtTailWs w = pt_tail_ws(npix, members);
+    char* ws = (char*)workspace;
+    double *stat1 = (double*)(ws + w.stat1), *stat2 = (double*)(ws + w.stat2), *rec3 = (double*)(ws + w.rec3), *rec2 = (double*)(ws + w.rec2);
+    float *mean1 = (float*)(ws + w.mean1), *rstd1 = (float*)(ws + w.rstd1), *mean2 = (float*)(ws + w.mean2), *rstd2 = (float*)(ws + w.rstd2);
+    float *a2 = (float*)(ws + w.a2), *dy2 = (float*)(ws + w.dy2);
+    const int N = members, M = N * PT_H1, M2 = N * PT_H2;
+    hipStream_t st = (hipStream_t)stream;
+
+    hipLaunchKernelGGL(pe_colsum_kernel<true>, dim3(M / 128, w.t1), dim3(128), 0, st, a1, stat1, npix, M);
+    SIS_CHECK_LAUNCH("pe_colsum_kernel");
+    hipLaunchKernelGGL(pe_bn_finish_kernel, dim3(sis_cdiv(M, 128)), dim3(128), 0, st, (const double*)stat1, w.t1, M, npix, mean1, rstd1,
+                       (float*)running[0], (float*)running[1], (int64_t*)running[4], N);
+    SIS_CHECK_LAUNCH("pe_bn_finish_kernel");
+    hipLaunchKernelGGL(pe_l2_fwd_kernel, dim3(w.t2, N), dim3(256), 0, st, a1, (const float*)mean1, (const float*)rstd1, g1, be1, w2, b2, a2,
+                       stat2, npix, N);
+    SIS_CHECK_LAUNCH("pe_l2_fwd_kernel");
+    hipLaunchKernelGGL(pe_bn_finish_kernel, dim3(sis_cdiv(M2, 128)), dim3(128), 0, st, (const double*)stat2, w.t2, M2, npix, mean2, rstd2,
+                       (float*)running[2], (float*)running[3], (int64_t*)running[5], N);
+    SIS_CHECK_LAUNCH("pe_bn_finish_kernel");
+    PtL3Params p3;
+    p3.a2 = a2; p3.mean2 = mean2; p3.rstd2 = rstd2; p3.g2 = g2; p3.be2 = be2; p3.W3 = w3; p3.b3 = b3; p3.labels = labels;
+    p3.dy2 = dy2; p3.logits = logits; p3.rec = rec3; p3.P = npix; p3.N = N; p3.C = classes;
+    hipLaunchKernelGGL(pe_l3_ce_kernel, dim3(w.t3, N), dim3(128), 0, st, p3);
+    SIS_CHECK_LAUNCH("pe_l3_ce_kernel");
+    hipLaunchKernelGGL(pe_finish3_kernel, dim3(N, sis_cdiv(PT_R3_LOSS + 1, 256)), dim3(256), 0, st, (const double*)rec3, w.t3, N, classes, npix,
+                       dw3, db3, dg2, dbe2, loss);
+    SIS_CHECK_LAUNCH("pe_finish3_kernel");
+    PtL2BwdParams p2;
+    p2.a1 = a1; p2.mean1 = mean1; p2.rstd1 = rstd1; p2.g1 = g1; p2.be1 = be1; p2.a2 = a2; p2.mean2 = mean2; p2.rstd2 = rstd2; p2.g2 = g2;
+    p2.dy2 = dy2; p2.dg2 = dg2; p2.dbe2 = dbe2; p2.W2 = w2; p2.dy1 = dz1; p2.rec = rec2; p2.P = npix; p2.N = N;
+    hipLaunchKernelGGL(pe_l2_bwd_kernel, dim3(w.tb, N), dim3(256), 0, st, p2);
+    SIS_CHECK_LAUNCH("pe_l2_bwd_kernel");
+    hipLaunchKernelGGL(pe_finish2_kernel, dim3(N, sis_cdiv(PT_R2, 256)), dim3(256), 0, st, (const double*)rec2, w.tb, N, dw2, db2, dg1, dbe1);
+    SIS_CHECK_LAUNCH("pe_finish2_kernel");
+    hipLaunchKernelGGL(pe_dz1_kernel, dim3(sis_cdiv((int64_t)npix * M, 256)), dim3(256), 0, st, dz1, a1, (const float*)mean1,
+                       (const float*)rstd1, g1, (const float*)dg1, (const float*)dbe1, npix, M);
+    SIS_CHECK_LAUNCH("pe_dz1_kernel");
+    return 0;
+}
+
+extern "C" int sis_pe_train_l1_wgrad(const float* dz1, const float* x, float* dw1, float* db1, void* workspace, int npix, int features,
+                                     int members, void* stream) {
+    SIS_REQUIRE(dz1 && x && dw1 && db1 && workspace, "sis_pe_train_l1_wgrad: null pointer");
+    SIS_REQUIRE(npix >= 1 && npix <= (1 << 21), "sis_pe_train_l1_wgrad: %d pixels", npix);
+    SIS_REQUIRE(members >= 1 && members <= 10, "sis_pe_train_l1_wgrad: %d members (1..10)", members);
+    SIS_REQUIRE(features > 0 && features % PE_KC == 0, "sis_pe_train_l1_wgrad: %d features (a multiple of %d)", features, PE_KC);
+    SIS_REQUIRE(!(((intptr_t)x | (intptr_t)dz1 | (intptr_t)dw1) & 15) && !((intptr_t)workspace & 255),
+                "sis_pe_train_l1_wgrad: operands must be 16-byte aligned, the workspace 256-byte aligned");
+    const int M = members * PT_H1, T = sis_cdiv(npix, PT_ROWS), nslab = pt_slabs(npix);
+    hipStream_t st = (hipStream_t)stream;
+    double* colsum = (double*)workspace;
+    float* slabs = (float*)((char*)workspace + pt_align((int64_t)T * M * 8));
+    hipLaunchKernelGGL(pe_colsum_kernel<false>, dim3(M / 128, T), dim3(128), 0, st, dz1, colsum, npix, M);
+    SIS_CHECK_LAUNCH("pe_colsum_kernel");
+    hipLaunchKernelGGL(pe_colsum_finish_kernel, dim3(sis_cdiv(M, 128)), dim3(128), 0, st, (const double*)colsum, db1, T, M);
+    SIS_CHECK_LAUNCH("pe_colsum_finish_kernel");
+    hipLaunchKernelGGL(pe_l1_wgrad_kernel, dim3(sis_cdiv(features, PT_ROWS), members, nslab), dim3(256), 0, st, dz1, x,
+                       nslab > 1 ? slabs : dw1, npix, features, M, pt_slab_rows(npix));
+    SIS_CHECK_LAUNCH("pe_l1_wgrad_kernel");
+    if (nslab > 1) {
+        const int64_t count = (int64_t)M * features;
+        hipLaunchKernelGGL(pe_slab_sum_kernel, dim3(sis_cdiv(count, 256)), dim3(256), 0, st, (const float*)slabs, dw1, count, nslab);
+        SIS_CHECK_LAUNCH("pe_slab_sum_kernel");
     }
     return 0;
 }

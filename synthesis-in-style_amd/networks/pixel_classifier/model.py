@@ -1,7 +1,8 @@
 """DatasetGAN's per-pixel MLP ensemble (reference: networks/pixel_classifier/model.py:13-121).
 
 Same constructor arguments, member naming and state_dict schema as the reference.  ``forward`` is the plain ATen
-``nn.Sequential`` (training and the A/B leg of tools/bench_dataset_gan.py).  Labelling a generator's activations on a HIP
+``nn.Sequential`` (the A/B leg of tools/bench_dataset_gan.py, and training on CPU tensors; on a HIP device the ensemble is
+trained by training/ensemble_step.py, all members per launch).  Labelling a generator's activations on a HIP
 device goes through ``PixelEnsembleClassifier.fused_weights`` and ``sis_hip.pixel_ensemble_label``
 (segmentation/dataset_gan_segmenter.py): eval mode only, BatchNorm folded into the following ``Linear``.
 """

@@ -166,6 +166,11 @@ _SIGNATURES = {
     "sis_adam_clip_step": ([_vp, _i, _vp, _vp, _vp, _vp], _i),
     "sis_pixel_ensemble_project": ([_vp, _i, _i, _i, _vp], _i),
     "sis_pixel_ensemble_head": ([_vp, _vp, _i] + [_vp] * 10 + [_i] * 5 + [_vp], _i),
+    "sis_pe_train_workspace_bytes": ([_i] * 4, _i64),
+    "sis_pe_train_gather": ([_vp, _vp, _i, _vp, _vp] + [_i] * 4 + [_vp], _i),
+    "sis_pe_train_l1_forward": ([_vp] * 4 + [_i] * 3 + [_vp], _i),
+    "sis_pe_train_tail": ([_vp] * 9 + [_i] * 3 + [_vp], _i),
+    "sis_pe_train_l1_wgrad": ([_vp] * 5 + [_i] * 3 + [_vp], _i),
     "sis_skm_state_doubles": ([], _i),
     "sis_skm_gather": ([_vp, _vp, _vp, _i64, _i, _i, _i, _vp], _i),
     "sis_skm_loop": ([_vp] * 5 + [_i] * 4 + [_d, _i, _d, _i64, _vp], _i),
@@ -316,14 +321,15 @@ def side_stream(device, beside=None, tries=8):
 
 
 def own_kernel_names():
-    """Names of every ``__global__`` function of csrc/*.hip (the library's own device symbols), for classifying profiler
-    records into own / vendor-library kernels."""
+    """Names of every ``__global__`` function of csrc/*.hip and csrc/*.h (the library's own device symbols; kernels also live
+    in headers a .hip file includes), for classifying profiler records into own / vendor-library kernels."""
     global _own_kernels
     if _own_kernels is None:
         import glob
         import re
         names = set()
-        for path in glob.glob(os.path.join(os.path.dirname(_HERE), "csrc", "*.hip")):
+        csrc = os.path.join(os.path.dirname(_HERE), "csrc")
+        for path in glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")):
             with open(path) as f:
                 text = f.read()
             for m in re.finditer(r"__global__\s+(?:__launch_bounds__\s*\([^)]*\)\s*)?(?:__attribute__\s*\(\(.*?\)\)\s*)?(?:static\s+)?void\s+"
@@ -2733,6 +2739,160 @@ def pixel_ensemble_label(full, groups, w1f, b1, w2t, b2, w3t, b3, classes, hidde
                                                              members, classes, hidden1, _stream())),
                "sis_pixel_ensemble_head")
     return labels, rgb, logits
+
+
+# ------------------------------------------------------------------------------ DatasetGAN training
+
+PE_TRAIN_HIDDEN = (128, 32)   # the narrow PixelClassifier (2..31 classes); the wide one is not on the fused path
+PE_TRAIN_MAX_MEMBERS = 10
+
+
+def pe_train_workspace_bytes(piece, pixels, features, members):
+    """Bytes of the workspace of ``pe_train_tail`` (piece 0) or ``pe_train_l1_wgrad`` (piece 1)."""
+    n = lib().sis_pe_train_workspace_bytes(int(piece), int(pixels), int(features), int(members))
+    if n < 0:
+        raise RuntimeError(f"pe_train: unsupported shape: {pixels} pixels (>= 2), {features} features (a multiple of 32), "
+                           f"{members} members (1..{PE_TRAIN_MAX_MEMBERS})")
+    return n
+
+
+def _pe_workspace(workspace, nbytes, device):
+    if workspace is None:
+        return torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+    if workspace.dtype != torch.uint8 or workspace.numel() < nbytes or workspace.device != device or workspace.data_ptr() % 256:
+        raise RuntimeError(f"pe_train: the workspace must be a 256-byte aligned uint8 device tensor of at least {nbytes} bytes")
+    return workspace
+
+
+def pe_train_layer_table(layers):
+    """(host words, device int64 [L, 4]) of resident activation layers [images, c, res, res] in feature order: {pointer, c, res,
+    first column} per layer.  Keep the layers alive as long as the table is used."""
+    words, col = [], 0
+    for t in layers:
+        require_device(t, "activations")
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 4 or t.shape[2] != t.shape[3]:
+            raise RuntimeError("pe_train: activation layers must be contiguous float32 [images, c, res, res]")
+        words += [t.data_ptr(), t.shape[1], t.shape[2], col]
+        col += t.shape[1]
+    return words, torch.tensor(words, dtype=torch.int64).view(-1, 4).to(layers[0].device)
+
+
+def pe_train_gather(layers, pixels, size, table=None, out=None):
+    """X [P, F]: the DatasetGAN features of P pixels (int32 [P, 3] = image, y, x) of resident activation layers
+    [images, c, res, res], bilinear with align_corners=False as the label pass samples them (csrc/pixel_ensemble_train.h)."""
+    require_device(pixels, "pixels")
+    if pixels.dtype != torch.int32 or pixels.dim() != 2 or pixels.shape[1] != 3 or not pixels.is_contiguous():
+        raise RuntimeError("pe_train_gather: pixels must be a contiguous int32 [P, 3] tensor")
+    words, dev_table = table if table is not None else pe_train_layer_table(layers)
+    npix, features, images = pixels.shape[0], sum(t.shape[1] for t in layers), layers[0].shape[0]
+    if any(t.shape[0] != images for t in layers):
+        raise RuntimeError("pe_train_gather: the layers hold different numbers of images")
+    if out is None:
+        out = torch.empty((npix, features), dtype=torch.float32, device=pixels.device)
+    host = (ctypes.c_int64 * len(words))(*words)
+    with torch.cuda.device(pixels.device):
+        _check(_launch("pe_gather_kernel", 7.0 * npix * features, 20.0 * npix * features,
+                       lambda: lib().sis_pe_train_gather(host, _ptr(dev_table), len(layers), _ptr(pixels), _ptr(out), npix, features,
+                                                         int(size), images, _stream())), "sis_pe_train_gather")
+    return out
+
+
+def pe_train_l1_forward(x, w1, b1, out=None):
+    """a1 [P, N*128] = relu(x w1^T + b1) for x [P, F], w1 [N*128, F] (the members' first layers stacked)."""
+    x, w1, b1 = _dense_f32(x, "x"), _dense_f32(w1, "w1"), _dense_f32(b1, "b1")
+    npix, features = x.shape
+    m = w1.shape[0]
+    if m % PE_TRAIN_HIDDEN[0] or tuple(w1.shape) != (m, features) or b1.numel() != m:
+        raise RuntimeError("pe_train_l1_forward: w1 must be [N*128, F] and b1 [N*128]")
+    if out is None:
+        out = torch.empty((npix, m), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(_launch("pe_l1_fwd_kernel", 2.0 * npix * features * m, 4.0 * (x.numel() + w1.numel() + out.numel()),
+                       lambda: lib().sis_pe_train_l1_forward(_ptr(x), _ptr(w1), _ptr(b1), _ptr(out), npix, features,
+                                                             m // PE_TRAIN_HIDDEN[0], _stream())), "sis_pe_train_l1_forward")
+    return out
+
+
+PE_TRAIN_PARAMS = ("g1", "be1", "w2", "b2", "g2", "be2", "w3", "b3")
+PE_TRAIN_RUNNING = ("mean1", "var1", "mean2", "var2", "tracked1", "tracked2")
+
+
+def pe_train_tail(a1, labels, params, classes, running=None, grads=None, dz1=None, loss=None, want_logits=False, workspace=None):
+    """Everything between the first layer's output and its gradient, for N members at once (csrc/pixel_ensemble_train.h).
+
+    a1 [P, N*128] (after ReLU); labels int64 [P]; params: dict of PE_TRAIN_PARAMS (g1 / be1 [N*128], w2 [N, 32, 128], b2 / g2 / be2
+    [N*32], w3 [N, C, 32], b3 [N, C]); running: dict with any of PE_TRAIN_RUNNING, updated in place (tracked: int64 [N]).
+    -> {"dz1": [P, N*128], "loss": [N], "grads": {d + name}, "logits": [N, P, C] or None}."""
+    a1 = _dense_f32(a1, "a1")
+    require_device(labels, "labels")
+    npix, m = a1.shape
+    h1, h2 = PE_TRAIN_HIDDEN
+    members = m // h1
+    if m % h1 or labels.dtype != torch.int64 or labels.numel() != npix or not labels.is_contiguous():
+        raise RuntimeError("pe_train_tail: a1 must be [P, N*128] and labels a contiguous int64 [P] tensor")
+    shapes = {"g1": m, "be1": m, "w2": members * h2 * h1, "b2": members * h2, "g2": members * h2, "be2": members * h2,
+              "w3": members * classes * h2, "b3": members * classes}
+    ps = [_dense_f32(params[k], k) for k in PE_TRAIN_PARAMS]
+    for k, t in zip(PE_TRAIN_PARAMS, ps):
+        if t.numel() != shapes[k]:
+            raise RuntimeError(f"pe_train_tail: {k} has {t.numel()} elements, expected {shapes[k]}")
+    nbytes = pe_train_workspace_bytes(0, npix, 32, members)
+    dev = a1.device
+    workspace = _pe_workspace(workspace, nbytes, dev)
+    if grads is None:
+        grads = {"d" + k: torch.empty(tuple(params[k].shape), dtype=torch.float32, device=dev) for k in PE_TRAIN_PARAMS}
+    gs = [grads["d" + k] for k in PE_TRAIN_PARAMS]
+    for k, t in zip(PE_TRAIN_PARAMS, gs):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != shapes[k] or t.device != dev:
+            raise RuntimeError(f"pe_train_tail: gradient d{k} must be a contiguous float32 tensor of {shapes[k]} elements")
+    running = running or {}
+    rs = []
+    for k in PE_TRAIN_RUNNING:
+        t = running.get(k)
+        if t is not None:
+            want = torch.int64 if k.startswith("tracked") else torch.float32
+            count = members if k.startswith("tracked") else (m if k.endswith("1") else members * h2)
+            if t.dtype != want or not t.is_contiguous() or t.numel() != count or t.device != dev:
+                raise RuntimeError(f"pe_train_tail: running['{k}'] must be a contiguous {want} tensor of {count} elements")
+        rs.append(t)
+    if dz1 is None:
+        dz1 = torch.empty((npix, m), dtype=torch.float32, device=dev)
+    if loss is None:
+        loss = torch.empty((members,), dtype=torch.float32, device=dev)
+    logits = torch.empty((members, npix, classes), dtype=torch.float32, device=dev) if want_logits else None
+    c_params = (ctypes.c_void_p * 8)(*[t.data_ptr() for t in ps])
+    c_grads = (ctypes.c_void_p * 8)(*[t.data_ptr() for t in gs])
+    c_running = (ctypes.c_void_p * 6)(*[None if t is None else t.data_ptr() for t in rs])
+    flops = 2.0 * npix * members * 3 * (h1 * h2 + h2 * classes)
+    with torch.cuda.device(dev):
+        _check(_launch("pe_train_tail", flops, 4.0 * 4 * a1.numel(),
+                       lambda: lib().sis_pe_train_tail(_ptr(a1), _ptr(labels), c_params, c_running, c_grads, _ptr(dz1), _ptr(loss),
+                                                       _ptr(logits), _ptr(workspace), npix, members, int(classes), _stream())),
+               "sis_pe_train_tail")
+    return {"dz1": dz1, "loss": loss, "grads": grads, "logits": logits}
+
+
+def pe_train_l1_wgrad(dz1, x, dw1=None, db1=None, workspace=None):
+    """(dw1 [N*128, F] = dz1^T x, db1 [N*128] = column sums of dz1) for dz1 [P, N*128], x [P, F]."""
+    dz1, x = _dense_f32(dz1, "dz1"), _dense_f32(x, "x")
+    npix, m = dz1.shape
+    features = x.shape[1]
+    if m % PE_TRAIN_HIDDEN[0] or x.shape[0] != npix:
+        raise RuntimeError("pe_train_l1_wgrad: dz1 must be [P, N*128] and x [P, F]")
+    members = m // PE_TRAIN_HIDDEN[0]
+    if features % 32 or not 1 <= members <= PE_TRAIN_MAX_MEMBERS:
+        raise RuntimeError(f"pe_train_l1_wgrad: {features} features (a multiple of 32), {members} members (1..{PE_TRAIN_MAX_MEMBERS})")
+    nbytes = lib().sis_pe_train_workspace_bytes(1, max(npix, 2), features, members)
+    workspace = _pe_workspace(workspace, nbytes, x.device)
+    if dw1 is None:
+        dw1 = torch.empty((m, features), dtype=torch.float32, device=x.device)
+    if db1 is None:
+        db1 = torch.empty((m,), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(_launch("pe_l1_wgrad_kernel", 2.0 * npix * features * m, 4.0 * (x.numel() + dz1.numel() + dw1.numel()),
+                       lambda: lib().sis_pe_train_l1_wgrad(_ptr(dz1), _ptr(x), _ptr(dw1), _ptr(db1), _ptr(workspace), npix, features,
+                                                           members, _stream())), "sis_pe_train_l1_wgrad")
+    return dw1, db1
 
 
 # ------------------------------------------------------------------------------ training-time augmentation (DESIGN.md §12)

@@ -3,7 +3,8 @@
 Only the reference's ``'wpi'`` branch exists here: JSON-listed ``[image | label]`` PNG pairs -> ``AugmentedSegmentationDataset``
 kept on the device -> ``DeviceSegmentationLoader`` (shuffled and ``drop_last`` for training, in index order and complete for
 validation, which is inflated by ``num_augmentations`` like the training set, as in the reference; split across ranks by stride as the reference's ``DistributedSampler``).  The DatasetGAN branches of the reference
-read activation tensors from disk and stay out (data/dataset_gan_dataset.py covers that training input).
+read activation tensors from disk; they are not loaded here but by ``train_pixel_ensemble.py`` (data/dataset_gan_dataset.py,
+``DeviceDatasetGANDataset``), whose batches are pixel indices, not images.
 """
 import argparse
 import os
@@ -15,7 +16,8 @@ def get_data_loader(dataset_json_path: Path, dataset_name: str, args: argparse.N
                     validation: bool = False, original_generator_config_path: Optional[Path] = None, rank: int = 0,
                     world_size: int = 1, device=None):
     if dataset_name != 'wpi':
-        raise NotImplementedError(f"dataset '{dataset_name}': only 'wpi' (JSON-listed PNG pairs) is loaded here")
+        hint = " ('dataset_gan' is loaded by train_pixel_ensemble.py: data/dataset_gan_dataset.py)" if dataset_name == 'dataset_gan' else ""
+        raise NotImplementedError(f"dataset '{dataset_name}': only 'wpi' (JSON-listed PNG pairs) is loaded here{hint}")
     if not getattr(args, 'class_to_color_map', None):
         raise ValueError("a PNG dataset needs --class-to-color-map (class name -> colour of the label halves)")
     if 'num_augmentations' not in config:   # the reference reads config['num_augmentations']; a default of 1 would train unaugmented
