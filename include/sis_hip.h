@@ -877,6 +877,54 @@ int sis_augment_warp(float* images, int64_t* segmented, const uint8_t* pixels, c
 int sis_elastic_field(float* field, float* workspace, float* noise_out, const float* noise, const float* alpha, const float* sigma,
                       const uint32_t* seeds, int num_fields, int height, int width, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Projection encoders, inference path (csrc/encoder_ops.h): the layers of the reference's U-Net-like W+
+ * encoders (networks/encoder/u_net_like_encoder.py:28-63 torchvision BasicBlocks, :73-78 the 1x1 heads, :94-114
+ * WPlusEncoder.forward) that sis_conv3x3 and sis_bn_act_fwd do not take.  fp32 NCHW; eval-mode BatchNorm enters folded:
+ * scale = gamma / sqrt(var + eps), shift = beta - mean * scale.  No host sync, no atomics, bit-reproducible.
+ * sis_enc_conv3x3_s2 (u_net_like_encoder.py:42-50, a stride-2 BasicBlock's conv1 + bn1 + relu and its downsample =
+ *   Conv2d(1x1, stride 2) + BatchNorm2d): y_main = relu(scale1 * conv3x3_s2_p1(x, w1) + shift1) and, when y_short is given,
+ *   y_short = scale_d * conv1x1_s2(x, wd) + shift_d (a convolution bias folded into shift_d), both [batch][cout][h/2][w/2],
+ *   from one read of x.  `packed` comes from sis_enc_conv3x3_s2_pack (w1 [cout][cin][3][3], wd [cout][cin] or null) and holds
+ *   sis_enc_conv3x3_s2_packed_floats floats; y_short needs an image packed with wd.  cin % 8 == 0, h and w even, and
+ *   the staged tile within 64 KiB of LDS: 32 * (640 + (2 r + 1) * (w + 1)) <= 65536 bytes with r = min(h / 2, 128 / (w / 2) if
+ *   w / 2 divides 128, else 128 / (w / 2) + 2) output rows per 128-pixel tile -- every power-of-two width up to 256, other
+ *   widths up to about 200 (sis_enc_conv3x3_s2_supported answers for a shape).
+ * sis_enc_stem (u_net_like_encoder.py:28-35, the start block from the image): y_main = relu(scale1 * conv3x3_p1(x, w1) + shift1),
+ *   y_short = scale_d * (conv1x1(x, wd) + bias_d) + shift_d (bias_d may be null), stride 1, 1 <= cin <= 4.
+ * sis_enc_block_tail (BasicBlock.forward's out = relu(bn2(conv2) + identity); u_net_like_encoder.py:102,106 to_noise /
+ *   intermediate_to_noise, :101,104 the adaptive_avg_pool2d): y = relu(scale * c + shift + residual) (residual may be null);
+ *   noise [batch][1][hw] = sum_c noise_w[c] * y[.][c][.] + noise_b[0] when noise is given; partial [batch][channels][tiles],
+ *   tiles = sis_enc_block_tail_tiles(hw), = the sums of y over 256-pixel tiles when partial is given.  hw % 4 == 0.  The
+ *   channels are split over workgroups (a split that depends on channels and hw only, not on the batch); the noise output
+ *   then needs noise_workspace of sis_enc_block_tail_workspace_floats(batch, channels, hw) floats (0: none needed), 16-byte
+ *   aligned, for the slices' sums, which a second launch adds in slice order.
+ * sis_enc_latent_heads (u_net_like_encoder.py:101,104 to_latent on the pooled map, :108-110 reverse + stack; :161 WEncoder;
+ *   :175,240 the sums of WWPlusEncoder / WNoNoiseEncoder): table (device) holds n_heads rows of 8 int64 {partial pointer,
+ *   weight pointer [latent][C], bias pointer [latent], C, tiles, hw, slot, 0}; out[b][slot][:] = W * (sum of the tile
+ *   partials / hw) + bias, out being [batch][n_slots][latent]; with sum_heads (n_slots = 1) out[b][0][:] = the sum of all heads
+ *   in table order.  The CALLER guarantees max_channels >= every C of the table and 0 <= slot < n_slots (the table is
+ *   device memory the entry cannot read; sis_hip.enc_heads_table builds and checks both); (max_channels + latent) * 4 <= 48 KiB. */
+int sis_enc_conv3x3_s2_supported(int cin, int cout, int h, int w);
+int64_t sis_enc_conv3x3_s2_packed_floats(int cin, int cout, int with_shortcut);
+int sis_enc_conv3x3_s2_pack(float* packed, const float* w1, const float* wd, int cin, int cout, void* stream);
+int sis_enc_conv3x3_s2(float* y_main, float* y_short, const float* x, const float* packed, const float* scale1,
+                       const float* shift1, const float* scale_d, const float* shift_d, int batch, int cin, int cout, int h,
+                       int w, void* stream);
+int sis_enc_stem_supported(int cin, int cout, int h, int w);
+int sis_enc_stem(float* y_main, float* y_short, const float* x, const float* w1, const float* wd, const float* bias_d,
+                 const float* scale1, const float* shift1, const float* scale_d, const float* shift_d, int batch, int cin,
+                 int cout, int h, int w, void* stream);
+int sis_enc_block_tail_supported(int channels, int hw);
+int sis_enc_block_tail_tiles(int hw);
+int64_t sis_enc_block_tail_workspace_floats(int batch, int channels, int hw);
+int sis_enc_block_tail(float* y, float* noise, float* partial, const float* c, const float* residual, const float* scale,
+                       const float* shift, const float* noise_w, const float* noise_b, float* noise_workspace, int batch,
+                       int channels, int hw, void* stream);
+int sis_enc_latent_heads_supported(int max_channels, int latent);
+int sis_enc_latent_heads(float* out, const int64_t* table, int n_heads, int batch, int latent, int n_slots, int sum_heads,
+                         int max_channels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

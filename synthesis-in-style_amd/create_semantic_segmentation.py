@@ -12,8 +12,13 @@ destination:
   cluster_arrays/{k}.npz             per layer the colour rendering uint8 [n, 3, H, W] of the label map (and the images)
   cluster_images/{k}.png             the renderings, nearest-resized to the largest layer, one row per layer
 
-Not reproduced: ``-i/--images`` (needs the projection autoencoder) and the pickled catalog objects (the .npy / .json pair replaces
-them).
+``-i FILE`` (a JSON list of image paths, relative to the file) fits the catalogs on real pages instead: each image goes through the
+reference's transform (utils/data_loading.py:38-42: PIL resize to image_size x image_size, / 255, (x - 0.5) / 0.5), the
+projection autoencoder encodes it, and the activations are those of decoding its latents (get_activations :74-86).  It needs
+a checkpoint with an ``'autoencoder'`` entry (``--w-only`` / ``--two-stem`` say which encoder the entry belongs to); without one
+``-i`` raises ``NotImplementedError``.
+
+Not reproduced: the pickled catalog objects (the .npy / .json pair replaces them).
 """
 import argparse
 import json
@@ -70,6 +75,52 @@ def get_activations(args, g, device):
     return buffers, torch.cat(images).numpy()
 
 
+def load_image_batch(paths, image_size, input_dim, device):
+    """The reference's data-loader transform (utils/data_loading.py:38-42) for a list of files -> float32 [n, input_dim, S, S]."""
+    from PIL import Image
+    out = torch.empty((len(paths), input_dim, image_size, image_size), dtype=torch.float32)
+    for i, path in enumerate(paths):
+        with Image.open(path) as handle:
+            image = handle.convert('L' if input_dim == 1 else 'RGB').resize((image_size, image_size), Image.BILINEAR)
+        pixels = torch.from_numpy(numpy.asarray(image, dtype=numpy.uint8).reshape(image_size, image_size, input_dim).copy())
+        out[i] = (pixels.permute(2, 0, 1).float() / 255 - 0.5) / 0.5
+    return out.to(device)
+
+
+def load_autoencoder(args, device):
+    """The projection autoencoder of a checkpoint's 'autoencoder' entry (networks.load_autoencoder_or_generator, which raises
+    NotImplementedError for a checkpoint without the entry); without a checkpoint there is nothing to encode with."""
+    import networks
+    if not args.checkpoint:
+        raise NotImplementedError("-i/--images needs the projection autoencoder: a checkpoint that holds an 'autoencoder' entry")
+    config = {'stylegan_variant': 2, 'image_size': args.image_size, 'latent_size': args.latent_size, 'n_mlp': args.n_mlp,
+              'channel_multiplier': args.channel_multiplier, 'input_dim': args.input_dim, 'w_only': args.w_only,
+              'two_stem': args.two_stem, 'disable_update_for': 'none', 'stylegan_checkpoint': args.checkpoint}
+    return networks.load_autoencoder_or_generator(argparse.Namespace(device=device, checkpoint=args.checkpoint), config).eval()
+
+
+def get_image_activations(args, autoencoder, device):
+    """``get_activations`` for ``-i``: encode the listed images, decode the latents, keep the decode's activations."""
+    from utils.dataset_creation import generate_images
+    list_file = Path(args.images)
+    with open(list_file) as f:
+        paths = [str(list_file.parent / p) for p in json.load(f)][:args.num_samples]
+    if not paths:
+        raise ValueError(f"{list_file} lists no images")
+    n, buffers, images = len(paths), None, []
+    for first in range(0, n, args.batch_size):
+        batch = {'input_image': load_image_batch(paths[first:first + args.batch_size], args.image_size, args.input_dim, device)}
+        acts, image = generate_images(batch, autoencoder, device)
+        if buffers is None:
+            buffers = {key: torch.empty((n,) + tuple(a.shape[1:]), dtype=torch.float32, device=device) for key, a in acts.items()
+                       if args.strip_activations_from is None
+                       or (a.shape[-2] > args.strip_activations_from and a.shape[-1] > args.strip_activations_from)}
+        for key, buf in buffers.items():
+            buf[first:first + image.shape[0]] = acts[key]
+        images.append(sis_hip.make_image_u8(image).permute(0, 3, 1, 2).cpu())
+    return buffers, torch.cat(images).numpy()
+
+
 def find_clusters(activations, cluster_counts, **fit_args):
     """{k: {layer: fitted MiniBatchSphericalKMeans}}: per layer one batched run over all cluster counts."""
     found = {k: {} for k in cluster_counts}
@@ -113,16 +164,20 @@ def save_cluster_visualizations(rendered, k, dest_dir):
 
 
 def main(args):
-    if args.images is not None:
-        raise NotImplementedError("-i/--images needs the projection autoencoder, which is not part of this port")
     lo, hi = args.cluster_range
     if not 1 <= lo < hi <= sis_hip.SKM_KMAX + 1:
         raise ValueError(f"cluster range {lo} {hi}: counts 1 .. {sis_hip.SKM_KMAX} are supported (the upper end is exclusive)")
     device = torch.device('cuda', 0)
-    torch.cuda.set_device(device)
-    dest = prepare_output_dir(args)
-    g = load_generator(args.checkpoint, args.image_size, args.latent_size, args.n_mlp, args.channel_multiplier, device)
-    activations, images = get_activations(args, g, device)
+    if args.images is not None:
+        autoencoder = load_autoencoder(args, device)   # raises without an 'autoencoder' checkpoint, before anything is written
+        torch.cuda.set_device(device)
+        dest = prepare_output_dir(args)
+        activations, images = get_image_activations(args, autoencoder, device)
+    else:
+        torch.cuda.set_device(device)
+        dest = prepare_output_dir(args)
+        g = load_generator(args.checkpoint, args.image_size, args.latent_size, args.n_mlp, args.channel_multiplier, device)
+        activations, images = get_activations(args, g, device)
     if not activations:
         raise ValueError("no activation layer is left after --strip-activations-from")
     counts = list(range(lo, hi))
@@ -145,7 +200,11 @@ def build_parser():
     parser.add_argument("-b", "--batch-size", default=10, type=int, help="batch size for generation of images")
     parser.add_argument("-n", "--num-samples", default=100, type=int, help="number of samples the clusters are fitted on")
     parser.add_argument("-c", "--cluster-range", nargs=2, default=[3, 24], type=int, help="cluster counts LO .. HI - 1")
-    parser.add_argument("-i", "--images", help="not implemented (needs the projection autoencoder)")
+    parser.add_argument("-i", "--images", help="JSON list of image paths (relative to the file): fit on the activations of their "
+                                               "reconstructions; needs a checkpoint with an 'autoencoder' entry")
+    parser.add_argument("--input-dim", type=int, default=3, choices=[1, 3], help="channels of the images the encoder takes")
+    parser.add_argument("--w-only", action="store_true", help="the checkpoint's encoder predicts one W latent (WWPlusEncoder)")
+    parser.add_argument("--two-stem", action="store_true", help="the checkpoint holds a two-stem autoencoder")
     parser.add_argument("-s", "--strip-activations-from", type=int, help="drop all activations of this size or smaller")
     parser.add_argument("--image-size", type=int, default=256)
     parser.add_argument("--latent-size", type=int, default=512)

@@ -277,3 +277,7 @@ extern "C" int sis_stem_conv_wgrad(void* dw, int dw_dtype, const void* x, int x_
     sis_kernel_name = "stem7_wgrad_kernel";
     return 0;
 }
+
+// the projection encoders' kernels: the 3-channel start block, the stride-2 3x3 convolution with its shortcut, the block tail
+// and the latent heads (networks/encoder/u_net_like_encoder.py)
+#include "encoder_ops.h"

@@ -4,16 +4,20 @@
 * ``load_weights`` (:22-29)                      checkpoint dict -> ``network.load_state_dict`` (optional ``key``, ``strict``);
 * ``get_stylegan2_generator`` (:36-41)           ``Generator(image_size, latent_size, n_mlp, channel_multiplier)`` + ``g_ema`` weights;
 * ``get_swagan_generator`` (:354-362)            the same for the wavelet generator;
-* ``get_autoencoder`` (:388-404) / ``load_autoencoder_or_generator`` (:415-423)
+* ``get_autoencoder`` (:326-353, :390-412) / ``load_autoencoder_or_generator`` (:415-423)
                                                  the object ``generate_images(batch, autoencoder, ...)`` and
-                                                 ``build_latent_and_noise_generator(autoencoder, ...)`` are handed: only its
-                                                 ``.decoder`` is on the hot path (utils/dataset_creation.py:36,50-57), so the
-                                                 generator-only branch (no ``stylegan_checkpoint`` key in the config: weights
-                                                 under ``'g_ema'``, strict) is what exists here.  The encoder families of the
-                                                 projection research code (out of scope) are not rebuilt: asking
-                                                 for the full-autoencoder branch raises ``NotImplementedError``.
+                                                 ``build_latent_and_noise_generator(autoencoder, ...)`` are handed.  With an
+                                                 ``input_dim`` in the config the encoder the reference would build for
+                                                 ``stylegan_variant`` 2 / ``'swagan'`` is built on the generator's own channel
+                                                 map (``w_only``, ``two_stem`` + ``disable_update_for``, ``dropout_autoencoder``);
+                                                 without one the holder carries the generator alone (``encode`` raises).  A config
+                                                 with ``stylegan_checkpoint`` loads the whole autoencoder from the checkpoint's
+                                                 ``'autoencoder'`` entry; the reference's fall-through for files without that
+                                                 entry (the file itself as a bare state_dict) is not provided.
 
-Imports are deferred into the functions: ``networks`` is the package every model module lives in.
+Imports of the model modules are deferred into the functions: ``networks`` is the package every model module lives in.  The one
+exception is ``networks.encoder.autoencoder`` (torch and the ``Latents`` container only), whose classes are re-exported here
+under the reference's names; the encoders themselves are imported where they are built.
 """
 import argparse
 from pathlib import Path
@@ -52,42 +56,55 @@ def get_swagan_generator(image_size, latent_size, n_mlp=8, channel_multiplier=2,
     return generator
 
 
-class StyleganAutoencoder(nn.Module):
-    """The (encoder, decoder) holder of networks/encoder/autoencoder.py:13-19 with the decoder only."""
-
-    def __init__(self, encoder, decoder):
-        super().__init__()
-        self.encoder = encoder
-        self.decoder = decoder
-        self.use_generated_noise = True
-
-    def encode(self, x):
-        if self.encoder is None:
-            raise NotImplementedError("this autoencoder holds a generator only (image encoding is out of scope)")
-        return self.encoder(x)
-
-    def forward(self, x):
-        latent_codes = self.encode(x)
-        image, _ = self.decoder([latent_codes.latent], input_is_latent=latent_codes.latent.dim() == 3,
-                                noise=latent_codes.noise)
-        return image
+from networks.encoder.autoencoder import DropoutStyleganAutoencoder, StyleganAutoencoder, TwoStemStyleganAutoencoder  # noqa: E402,F401
 
 
-def get_autoencoder(config: dict, init_ckpt: str = None) -> StyleganAutoencoder:
+def _encoder_classes(config: dict):
+    """(autoencoder class, encoder class(es)) the reference's get_stylegan_2_based_autoencoder / get_swagan_based_autoencoder
+    pick (:326-353, :390-393)."""
+    from networks.encoder.u_net_like_encoder import NoiseEncoder, WNoNoiseEncoder, WPlusEncoder, WPlusNoNoiseEncoder, WWPlusEncoder
+    w_only = bool(config.get('w_only', False))
+    if config['stylegan_variant'] == 2:
+        if config.get('two_stem', False):
+            return TwoStemStyleganAutoencoder, (WNoNoiseEncoder if w_only else WPlusNoNoiseEncoder, NoiseEncoder)
+        if config.get('code_dim', 0) > 0:
+            raise NotImplementedError("stylegan2 code dim training not yet implemented")   # the reference's own message
+        if config.get('dropout_autoencoder', False):
+            return DropoutStyleganAutoencoder, (WWPlusEncoder if w_only else WPlusEncoder,)
+    return StyleganAutoencoder, (WWPlusEncoder if w_only else WPlusEncoder,)
+
+
+def get_autoencoder(config: dict, init_ckpt: str = None) -> Union[StyleganAutoencoder, TwoStemStyleganAutoencoder]:
     assert config['stylegan_variant'] in [1, 2, 'swagan'], "Stylegan Variant Unknown"
     if config['stylegan_variant'] == 1:
         raise NotImplementedError("StyleGAN1 is not on the MI355X hot path (SURVEY.md §2)")
     make = get_swagan_generator if config['stylegan_variant'] == 'swagan' else get_stylegan2_generator
     generator = make(config['image_size'], config['latent_size'], n_mlp=config.get('n_mlp', 8),
                      channel_multiplier=config.get('channel_multiplier', 2), init_ckpt=init_ckpt, strict=False)
-    return StyleganAutoencoder(None, generator)
+    if config.get('input_dim') is None:
+        return StyleganAutoencoder(None, generator)   # generator-only configs of the dataset tools
+    autoencoder_class, encoder_classes = _encoder_classes(config)
+    encoders = [cls(config['image_size'], config['latent_size'], config['input_dim'], generator.channels, stylegan_variant=2)
+                for cls in encoder_classes]
+    if autoencoder_class is TwoStemStyleganAutoencoder:
+        disabled = config.get('disable_update_for', 'none')
+        return TwoStemStyleganAutoencoder(*encoders, generator, update_latent=disabled in ['noise', 'none'],
+                                          update_noise=disabled in ['latent', 'none'])
+    return autoencoder_class(encoders[0], generator)
 
 
-def load_autoencoder_or_generator(args: argparse.Namespace, config: dict) -> StyleganAutoencoder:
+def load_autoencoder_or_generator(args: argparse.Namespace, config: dict) -> Union[StyleganAutoencoder, TwoStemStyleganAutoencoder]:
     autoencoder = get_autoencoder(config).to(args.device)
     # the reference decides by this key whether the checkpoint holds a full autoencoder or just the generator
     if 'stylegan_checkpoint' in config:
-        raise NotImplementedError("full autoencoder checkpoints need the encoder networks (out of scope); "
-                                  "generator checkpoints ('g_ema') are supported")
+        if config.get('input_dim') is None:
+            raise NotImplementedError("a full autoencoder checkpoint needs 'input_dim' in the config (the encoder's input channels)")
+        weights = torch.load(args.checkpoint, map_location='cpu')
+        if 'autoencoder' not in weights:
+            raise NotImplementedError("the checkpoint has no 'autoencoder' entry: the reference then loads the file itself as a "
+                                      "bare state_dict, which is not provided here; generator checkpoints ('g_ema') are "
+                                      "loaded by configs without 'stylegan_checkpoint'")
+        autoencoder.load_state_dict(weights['autoencoder'], strict=True)
+        return autoencoder
     autoencoder.decoder = load_weights(autoencoder.decoder, args.checkpoint, key='g_ema')
     return autoencoder

@@ -185,6 +185,18 @@ _SIGNATURES = {
     "sis_cluster_segment": ([_vp] * 5 + [_i, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp], _i),
     "sis_augment_warp": ([_vp] * 9 + [_i64] + [_i] * 8 + [_vp], _i),
     "sis_elastic_field": ([_vp] * 7 + [_i, _i, _i, _vp], _i),
+    "sis_enc_conv3x3_s2_supported": ([_i] * 4, _i),
+    "sis_enc_conv3x3_s2_packed_floats": ([_i] * 3, _i64),
+    "sis_enc_conv3x3_s2_pack": ([_vp] * 3 + [_i, _i, _vp], _i),
+    "sis_enc_conv3x3_s2": ([_vp] * 8 + [_i] * 5 + [_vp], _i),
+    "sis_enc_stem_supported": ([_i] * 4, _i),
+    "sis_enc_stem": ([_vp] * 10 + [_i] * 5 + [_vp], _i),
+    "sis_enc_block_tail_supported": ([_i] * 2, _i),
+    "sis_enc_block_tail_tiles": ([_i], _i),
+    "sis_enc_block_tail_workspace_floats": ([_i] * 3, _i64),
+    "sis_enc_block_tail": ([_vp] * 10 + [_i] * 3 + [_vp], _i),
+    "sis_enc_latent_heads_supported": ([_i] * 2, _i),
+    "sis_enc_latent_heads": ([_vp, _vp] + [_i] * 6 + [_vp], _i),
 }
 
 
@@ -2985,3 +2997,182 @@ def augment_warp(pixels, classes, index, minv, lut, field_slot, field=None, back
                                                       int(background_id), out_h, out_w, int(bool(quantize)), _stream())),
                "sis_augment_warp")
     return {"images": images, "segmented": segmented}
+
+
+# ------------------------------------------------------------------------------ projection encoders (csrc/encoder_ops.h)
+
+
+def fold_batch_norm(bn, conv_bias=None):
+    """Eval-mode BatchNorm2d as (scale, shift) float32 [C]: scale = gamma / sqrt(var + eps), shift = beta - mean * scale
+    (+ scale * conv_bias: the bias of the convolution in front of it).  Computed in float64, rounded once."""
+    var, mean = bn.running_var.detach().double(), bn.running_mean.detach().double()
+    scale = torch.rsqrt(var + bn.eps)
+    if bn.weight is not None:
+        scale = scale * bn.weight.detach().double()
+    shift = -mean * scale
+    if bn.bias is not None:
+        shift = shift + bn.bias.detach().double()
+    if conv_bias is not None:
+        shift = shift + scale * conv_bias.detach().double()
+    return scale.float().contiguous(), shift.float().contiguous()
+
+
+def enc_conv3x3_s2_supported(cin, cout, h, w):
+    return bool(lib().sis_enc_conv3x3_s2_supported(int(cin), int(cout), int(h), int(w)))
+
+
+def enc_conv3x3_s2_pack(weight, shortcut_weight=None):
+    """[Cout, Cin, 3, 3] (+ the block's 1x1 stride-2 shortcut weight [Cout, Cin, 1, 1]) -> the k-major image of
+    ``enc_conv3x3_s2``: [Cin, 9 or 10, Cout padded to 64]."""
+    w = _f32(weight, "weight")
+    cout, cin = w.shape[0], w.shape[1]
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+        raise RuntimeError("enc_conv3x3_s2_pack: a [Cout, Cin, 3, 3] weight is needed")
+    wd = None
+    if shortcut_weight is not None:
+        wd = _f32(shortcut_weight, "shortcut weight")
+        if wd.numel() != cout * cin:
+            raise RuntimeError("enc_conv3x3_s2_pack: the shortcut weight must be [Cout, Cin, 1, 1]")
+    taps = 10 if wd is not None else 9
+    packed = torch.empty((cin, taps, -(-cout // 64) * 64), dtype=torch.float32, device=w.device)
+    assert packed.numel() == lib().sis_enc_conv3x3_s2_packed_floats(cin, cout, int(wd is not None))
+    with torch.cuda.device(w.device):
+        _check(lib().sis_enc_conv3x3_s2_pack(_ptr(packed), _ptr(w), _ptr(wd), cin, cout, _stream()), "sis_enc_conv3x3_s2_pack")
+    return packed
+
+
+def enc_conv3x3_s2(x, packed, cout, scale1, shift1, scale_d=None, shift_d=None):
+    """relu(scale1 * conv3x3_stride2_pad1(x) + shift1) and, with scale_d / shift_d (``packed`` then holds the shortcut
+    weights), scale_d * conv1x1_stride2(x) + shift_d from the same read of x -> (y_main, y_short or None)."""
+    x = _f32(x, "input")
+    batch, cin, h, w = x.shape
+    short = scale_d is not None
+    if packed.shape[0] != cin or packed.shape[1] != (10 if short else 9) or packed.shape[2] != -(-cout // 64) * 64:
+        raise RuntimeError(f"enc_conv3x3_s2: packed weights {tuple(packed.shape)} do not fit {cin} -> {cout} channels"
+                           f"{' with a shortcut' if short else ''}")
+    y = torch.empty((batch, cout, h // 2, w // 2), dtype=torch.float32, device=x.device)
+    ys = torch.empty((batch, cout, h // 2, w // 2), dtype=torch.float32, device=x.device) if short else None
+    flops = 2.0 * batch * cout * cin * (10 if short else 9) * (h // 2) * (w // 2)
+    with torch.cuda.device(x.device):
+        _check(_launch("enc_conv3x3_s2_kernel", flops, 4.0 * (x.numel() + (2 if short else 1) * y.numel() + packed.numel()),
+                       lambda: lib().sis_enc_conv3x3_s2(_ptr(y), _ptr(ys), _ptr(x), _ptr(packed), _ptr(scale1), _ptr(shift1), _ptr(scale_d),
+                                                        _ptr(shift_d), batch, cin, cout, h, w, _stream())), "sis_enc_conv3x3_s2")
+    return y, ys
+
+
+def enc_stem_supported(cin, cout, h, w):
+    return bool(lib().sis_enc_stem_supported(int(cin), int(cout), int(h), int(w)))
+
+
+def enc_stem(x, weight, scale1, shift1, shortcut_weight, shortcut_bias, scale_d, shift_d):
+    """The start block from <= 4 input channels: (relu(scale1 * conv3x3(x) + shift1), scale_d * (conv1x1(x) + bias) + shift_d)."""
+    x, w1, wd = _f32(x, "input"), _f32(weight, "weight"), _f32(shortcut_weight, "shortcut weight")
+    batch, cin, h, w = x.shape
+    cout = w1.shape[0]
+    if tuple(w1.shape) != (cout, cin, 3, 3) or wd.numel() != cout * cin:
+        raise RuntimeError("enc_stem: weights must be [Cout, Cin, 3, 3] and [Cout, Cin, 1, 1]")
+    y = torch.empty((batch, cout, h, w), dtype=torch.float32, device=x.device)
+    ys = torch.empty((batch, cout, h, w), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(_launch("enc_stem_kernel", 2.0 * batch * cout * cin * 10 * h * w, 4.0 * (x.numel() + 2 * y.numel()),
+                       lambda: lib().sis_enc_stem(_ptr(y), _ptr(ys), _ptr(x), _ptr(w1), _ptr(wd), _ptr(shortcut_bias), _ptr(scale1), _ptr(shift1),
+                                                  _ptr(scale_d), _ptr(shift_d), batch, cin, cout, h, w, _stream())), "sis_enc_stem")
+    return y, ys
+
+
+def enc_block_tail_supported(channels, hw):
+    return bool(lib().sis_enc_block_tail_supported(int(channels), int(hw)))
+
+
+def enc_block_tail_tiles(hw):
+    return int(lib().sis_enc_block_tail_tiles(int(hw)))
+
+
+def enc_block_tail(c, residual, scale, shift, noise_weight=None, noise_bias=None, want_pool=False, pool_out=None):
+    """y = relu(scale * c + shift + residual) -> (y, noise [B,1,H,W] or None, pool partials [B,C,tiles] or None);
+    ``noise_weight`` [1,C,1,1] / ``noise_bias`` [1]: the 1x1 convolution of y to one channel; ``want_pool``: per-tile sums of y
+    (``sis_enc_latent_heads`` finishes the average), written into ``pool_out`` when given."""
+    c = _f32(c, "input")
+    batch, ch, h, w = c.shape
+    hw = h * w
+    if residual is not None:
+        residual = _f32(residual, "residual")
+        if residual.shape != c.shape:
+            raise RuntimeError("enc_block_tail: the residual must have the input's shape")
+    y = torch.empty((batch, ch, h, w), dtype=torch.float32, device=c.device)
+    noise = torch.empty((batch, 1, h, w), dtype=torch.float32, device=c.device) if noise_weight is not None else None
+    partial = None
+    if want_pool:
+        tiles = enc_block_tail_tiles(hw)
+        partial = pool_out if pool_out is not None else torch.empty((batch, ch, tiles), dtype=torch.float32, device=c.device)
+        if tuple(partial.shape) != (batch, ch, tiles) or partial.dtype != torch.float32 or not partial.is_contiguous():
+            raise RuntimeError(f"enc_block_tail: pool_out must be a contiguous float32 [{batch}, {ch}, {tiles}] tensor")
+    nw = _f32(noise_weight, "noise weight") if noise_weight is not None else None
+    if nw is not None and nw.numel() != ch:
+        raise RuntimeError("enc_block_tail: the noise weight must be [1, C, 1, 1]")
+    nws = None
+    if nw is not None:
+        floats = lib().sis_enc_block_tail_workspace_floats(batch, ch, hw)
+        nws = torch.empty(floats, dtype=torch.float32, device=c.device) if floats else None   # the channel slices' noise sums
+    streams = 2 + (residual is not None)
+    with torch.cuda.device(c.device):
+        _check(_launch("enc_block_tail_kernel", 0.0, 4.0 * streams * c.numel(),
+                       lambda: lib().sis_enc_block_tail(_ptr(y), _ptr(noise), _ptr(partial), _ptr(c), _ptr(residual), _ptr(scale), _ptr(shift),
+                                                        _ptr(nw), _ptr(noise_bias), _ptr(nws), batch, ch, hw, _stream())), "sis_enc_block_tail")
+    return y, noise, partial
+
+
+ENC_HEAD_COLS = 8
+
+
+class EncHeadsTable:
+    """The pointer table of ``enc_latent_heads`` with what the launch must know about it: ``table`` int64 [n, 8] on the device,
+    ``max_channels`` (the largest C of its rows), ``slots`` (each head's output row) and the tensors it points into."""
+
+    def __init__(self, heads, device):
+        rows, self.slots, self.max_channels, self.batch, self.latent = [], [], 0, None, None
+        for partial, hw, weight, bias, slot in heads:
+            b, ch, tiles = partial.shape
+            if weight.dtype != torch.float32 or bias.dtype != torch.float32 or partial.dtype != torch.float32 \
+                    or not (weight.is_contiguous() and bias.is_contiguous() and partial.is_contiguous()):
+                raise RuntimeError("enc_heads_table: contiguous float32 tensors only")
+            for t in (partial, weight, bias):
+                require_device(t, "head tensor")
+            if weight.numel() != bias.numel() * ch or tiles != enc_block_tail_tiles(hw):
+                raise RuntimeError("enc_heads_table: a head needs weight [latent, C], bias [latent] and partials [B, C, tiles of hw]")
+            if self.batch not in (None, b) or self.latent not in (None, bias.numel()) or int(slot) < 0:
+                raise RuntimeError("enc_heads_table: the heads must share the batch and the latent size; slots are >= 0")
+            self.batch, self.latent = b, bias.numel()
+            self.max_channels = max(self.max_channels, ch)
+            self.slots.append(int(slot))
+            rows.append([partial.data_ptr(), weight.data_ptr(), bias.data_ptr(), ch, tiles, int(hw), int(slot), 0])
+        if not rows:
+            raise RuntimeError("enc_heads_table: no heads")
+        self.keep = [t for h in heads for t in (h[0], h[2], h[3])]   # the table holds their addresses
+        self.table = torch.tensor(rows, dtype=torch.int64).to(device)
+
+
+def enc_heads_table(heads, device):
+    """``EncHeadsTable`` for ``enc_latent_heads``: one row per head from (partials [B,C,tiles], hw, weight [latent,C(,1,1)],
+    bias [latent], slot).  The tensors must stay in place while the table is used."""
+    return EncHeadsTable(heads, device)
+
+
+def enc_latent_heads(heads, n_slots=None, sum_heads=False):
+    """Every to_latent head of an encode in one launch -> [B, n_slots, latent] (row ``slot`` of each head; every row must be some
+    head's, or it stays unwritten: ``n_slots`` defaults to the number of heads), or with ``sum_heads`` [B, latent]: the sum of
+    all heads in table order."""
+    if not isinstance(heads, EncHeadsTable):
+        raise RuntimeError("enc_latent_heads: the table comes from enc_heads_table")
+    table, batch, latent = heads.table, heads.batch, heads.latent
+    slots = 1 if sum_heads else int(len(heads.slots) if n_slots is None else n_slots)
+    if not sum_heads and (max(heads.slots) >= slots or len(set(heads.slots)) != len(heads.slots)):
+        raise RuntimeError(f"enc_latent_heads: slots {heads.slots} do not fit {slots} distinct output rows")
+    if not lib().sis_enc_latent_heads_supported(heads.max_channels, latent):
+        raise RuntimeError(f"enc_latent_heads: {heads.max_channels} channels with latent size {latent} do not fit the kernel")
+    out = torch.empty((batch, slots, latent), dtype=torch.float32, device=table.device)
+    with torch.cuda.device(table.device):
+        _check(_launch("enc_latent_heads_kernel", 0.0, 0.0,
+                       lambda: lib().sis_enc_latent_heads(_ptr(out), _ptr(table), table.shape[0], batch, latent, slots, int(bool(sum_heads)),
+                                                          heads.max_channels, _stream())), "sis_enc_latent_heads")
+    return out.view(batch, latent) if sum_heads else out

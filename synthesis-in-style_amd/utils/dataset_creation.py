@@ -9,8 +9,8 @@ create_dataset_for_segmentation.py:129-148 calls).  Same observable behaviour:
   noise=..., return_intermediate_activations=True, truncation=0.7 iff a mean latent is given)`` under
   ``torch.no_grad()``, return ``(activations, image)``.
 
-The image-encoding branch of the reference (``autoencoder.encode`` for non-``Latents`` batches) belongs
-to the projection research code and is out of scope.
+A dict batch ``{'input_image': ...}`` takes the reference's image-encoding branch: ``autoencoder.encode`` (the projection
+encoders, networks/encoder/), then the decoder with ``input_is_latent=autoencoder.is_wplus(latents)``.
 """
 import os
 from typing import Dict, Iterable, Optional, Tuple
@@ -51,12 +51,17 @@ def shard_range(num_images: int, rank: int, world_size: int) -> Tuple[int, int]:
 
 def generate_images(batch: Latents, autoencoder, device='cuda', mean_latent: Optional[torch.Tensor] = None) \
         -> Tuple[Dict[int, torch.Tensor], torch.Tensor]:
-    if not isinstance(batch, Latents):
-        raise NotImplementedError("only Latents batches are supported (image encoding is out of scope)")
-    latents = batch.to(device)
     with torch.no_grad():
+        if isinstance(batch, Latents):
+            latents, input_is_latent = batch.to(device), False
+        elif isinstance(batch, dict) and 'input_image' in batch:
+            # the reference's image batches (:44-47): encode, then decode W+ latents as latents and W latents through the mapping
+            latents = autoencoder.encode(batch['input_image'].to(device))
+            input_is_latent = autoencoder.is_wplus(latents)
+        else:
+            raise NotImplementedError("a batch is a Latents object or a dict holding 'input_image'")
         image, activations = autoencoder.decoder(
-            [latents.latent], input_is_latent=False, noise=latents.noise, return_intermediate_activations=True,
+            [latents.latent], input_is_latent=input_is_latent, noise=latents.noise, return_intermediate_activations=True,
             truncation=0.7 if mean_latent is not None else 1, truncation_latent=mean_latent)
     return activations, image
 
