@@ -925,6 +925,36 @@ int sis_enc_latent_heads_supported(int max_channels, int latent);
 int sis_enc_latent_heads(float* out, const int64_t* table, int n_heads, int batch, int latent, int n_slots, int sum_heads,
                          int max_channels, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * GAN training from an image list (csrc/gan_train_ops.h).  fp32 NCHW; no host sync, no atomics, every sum in a
+ * fixed order: bit-reproducible.
+ * sis_gan_image_batch (utils/data_loading.py:38-42, transforms.ToTensor + Normalize((0.5,) * 3, (0.5,) * 3) of a batch the
+ *   DataLoader collates): images uint8 [n_images][3][size][size] resident on the device, ids int32 [batch] (device) ->
+ *   out float32 [batch][3][size][size] = (v / 255 - 0.5) / 0.5 with true fp32 divisions in that order, bit-equal to the
+ *   reference's transform.  An id outside 0 .. n_images - 1 yields a NaN sample and reads nothing.  16-byte stores when
+ *   3 * size * size % 4 == 0 (every even size), out 16-byte and images 4-byte aligned; one element per thread otherwise.
+ * sis_phase_split / sis_phase_merge (F.pixel_unshuffle / F.pixel_shuffle by 2; the reference has no counterpart: it runs
+ *   networks/stylegan2/model.py:564-609 ConvLayer(downsample=True) as Blur + stride-2 conv2d): x [batch][channels][h][w] <->
+ *   phases [batch][4 channels][h/2][w/2], phases[b][4 c + 2 py + px][i][j] = x[b][c][2 i + py][2 j + px]; `channels`, h, w are
+ *   those of x in both calls.  h and w even (sis_phase_split_supported).  The two are inverses and mutual adjoints.  16-byte
+ *   accesses on both sides when w % 8 == 0 and both pointers are 16-byte aligned.
+ * sis_down_weight_compose (model.py:564-609 with :55-73 Blur, :94-131 EqualConv2d): Blur(pad = (2, 2), fir [4][4]) followed by
+ *   conv2d(stride 2, padding 0) with scale * w, w [cout][cin][3][3], is ONE 6 x 6 stride-2 kernel
+ *   K[m][n] = scale * sum_{i,j} w[i][j] * fir[3 - (m - i)][3 - (n - j)], which over the phases of its input is the 3 x 3 stride-1
+ *   padding-1 convolution with w_phases [cout][4 cin][3][3], w_phases[co][4 ci + 2 py + px][a][b] = K[co][ci][2 a + py][2 b + px].
+ *   fir is device memory, NORMALISED taps as Blur holds them.  Only a 4 x 4 fir (sis_down_weight_compose_supported).
+ * sis_down_weight_compose_adjoint: the transpose of that linear map, dw_phases [cout][4 cin][3][3] -> dw [cout][cin][3][3],
+ *   scale included.  w_phases / dw_phases 16-byte aligned. */
+int sis_gan_image_batch(float* out, const uint8_t* images, const int* ids, int64_t n_images, int batch, int size, void* stream);
+int sis_phase_split_supported(int h, int w);
+int sis_phase_split(float* phases, const float* x, int batch, int channels, int h, int w, void* stream);
+int sis_phase_merge(float* x, const float* phases, int batch, int channels, int h, int w, void* stream);
+int sis_down_weight_compose_supported(int fir_h, int fir_w);
+int sis_down_weight_compose(float* w_phases, const float* w, const float* fir, int fir_h, int fir_w, float scale, int cout, int cin,
+                            void* stream);
+int sis_down_weight_compose_adjoint(float* dw, const float* dw_phases, const float* fir, int fir_h, int fir_w, float scale, int cout,
+                                    int cin, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -281,3 +281,7 @@ extern "C" int sis_stem_conv_wgrad(void* dw, int dw_dtype, const void* x, int x_
 // the projection encoders' kernels: the 3-channel start block, the stride-2 3x3 convolution with its shortcut, the block tail
 // and the latent heads (networks/encoder/u_net_like_encoder.py)
 #include "encoder_ops.h"
+
+// GAN training from an image list: the loader's batch gather, and the phase split / weight composition that run a discriminator
+// downsampling layer on the Winograd kernels (train_stylegan_2.py, networks/hip_conv.py down_conv3x3)
+#include "gan_train_ops.h"

@@ -15,6 +15,10 @@ Autograd: the data gradient is the same kernel with adjoint weights (``sis_conv3
 axes swapped, taps rotated by 180 degrees); the weight gradient is ``sis_conv3x3_wgrad`` (Winograd-domain GEMM over
 the tile axis, csrc/conv_wgrad_wino.hip) where its tile plan applies (channels % 64) and there is enough work, ATen's
 ``convolution_backward`` otherwise.
+
+``down_conv3x3`` runs a discriminator downsampling layer (blur + 3x3 stride-2 convolution) as ``conv3x3`` over the four pixel
+phases of its input (``phase_split`` + ``compose_down_weight``, csrc/gan_train_ops.h), twice differentiable on the same kernels;
+measured slower than blur + library on the whole GAN step, so its switch is off by default.
 """
 import os
 
@@ -152,6 +156,100 @@ def conv3x3(input, weight, dilation=1, prepacked=None, defer_wgrad=False):
     """Differentiable stride-1 3x3 convolution with padding = dilation on the Winograd kernel (caller checks
     eligibility with ``sis_hip.conv3x3_supported``)."""
     return _Conv3x3Function.apply(input, weight, dilation, prepacked, defer_wgrad)
+
+
+class _PhaseSplit(Function):
+    """[B,C,H,W] -> [B,4C,H/2,W/2] (``sis_phase_split``).  Its adjoint is the merge, applied through ``_PhaseMerge`` so that a
+    gradient of a gradient (R1) stays on the two kernels."""
+
+    @staticmethod
+    def forward(ctx, input):
+        return sis_hip.phase_split(input)
+
+    @staticmethod
+    def backward(ctx, grad_phases):
+        return _PhaseMerge.apply(grad_phases.contiguous())
+
+
+class _PhaseMerge(Function):
+    @staticmethod
+    def forward(ctx, phases):
+        return sis_hip.phase_merge(phases)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        return _PhaseSplit.apply(grad_output.contiguous())
+
+
+class _ComposeDownWeight(Function):
+    """(W [Cout,Cin,3,3], f [4,4], scale) -> W' [Cout,4Cin,3,3] (``sis_down_weight_compose``); linear in W, no gradient for f."""
+
+    @staticmethod
+    def forward(ctx, weight, fir, scale):
+        ctx.save_for_backward(fir)
+        ctx.scale = scale
+        return sis_hip.down_weight_compose(weight, fir, scale)
+
+    @staticmethod
+    def backward(ctx, grad_phases):
+        fir, = ctx.saved_tensors
+        return _ComposeDownWeightAdjoint.apply(grad_phases.contiguous(), fir, ctx.scale), None, None
+
+
+class _ComposeDownWeightAdjoint(Function):
+    @staticmethod
+    def forward(ctx, grad_phases, fir, scale):
+        ctx.save_for_backward(fir)
+        ctx.scale = scale
+        return sis_hip.down_weight_compose_adjoint(grad_phases, fir, scale)
+
+    @staticmethod
+    def backward(ctx, grad_weight):
+        fir, = ctx.saved_tensors
+        return _ComposeDownWeight.apply(grad_weight.contiguous(), fir, ctx.scale), None, None
+
+
+def phase_split(input):
+    """Differentiable (any order) ``F.pixel_unshuffle(input, 2)`` on the HIP kernel: the four pixel phases as channels (c, py, px)."""
+    return _PhaseSplit.apply(input)
+
+
+def phase_merge(phases):
+    """Differentiable ``F.pixel_shuffle(phases, 2)``: the inverse and adjoint of ``phase_split``."""
+    return _PhaseMerge.apply(phases)
+
+
+def compose_down_weight(weight, fir, scale):
+    """Differentiable weight of the stride-1 convolution over the phases that equals Blur(pad 2, ``fir``) + stride-2 convolution
+    with ``scale * weight`` (csrc/gan_train_ops.h states the algebra)."""
+    return _ComposeDownWeight.apply(weight, fir, scale)
+
+
+def down_conv3x3_supported(input, weight, fir):
+    """The polyphase route takes this downsampling layer: float32 NCHW on the device, 4 x 4 FIR, and the Winograd path takes the
+    half-resolution convolution over 4 Cin channels in both directions (W % 8 == 0, H % 4 == 0, Cout % 8 == 0, tile plan)."""
+    if not (input.is_cuda and input.dtype == torch.float32 and input.dim() == 4 and weight.dim() == 4 and weight.dtype == torch.float32
+            and tuple(weight.shape[2:]) == (3, 3) and weight.shape[1] == input.shape[1] and fir.dtype == torch.float32
+            and not torch.is_autocast_enabled() and sis_hip.down_weight_compose_supported(fir)):
+        return False
+    b, cin, h, w = input.shape
+    if h % 2 or w % 2:
+        return False
+    return sis_hip.conv3x3_shape_supported(b, 4 * cin, weight.shape[0], h // 2, w // 2)
+
+
+def down_conv3x3(input, weight, fir, scale):
+    """Blur(pad = (2, 2), ``fir``) followed by a 3x3 stride-2 convolution without padding with ``scale * weight`` -- a discriminator
+    downsampling layer (networks/stylegan2/discriminator.py ConvLayer) -- as ONE stride-1 convolution over the pixel phases of the
+    input: ``conv3x3(phase_split(x), compose_down_weight(W, f, scale))``.  Forward, both gradients and the second-order terms of the
+    R1 penalty run on the Winograd kernels; no blur pass, no layout transposes.  Shapes the Winograd path declines run the
+    two-operator formulation on the library and are counted (``sis_hip.library_call("gan.down_conv3x3")``)."""
+    if down_conv3x3_supported(input, weight, fir) and gan_winograd_enabled():
+        return conv3x3(phase_split(input.contiguous()), compose_down_weight(weight, fir, scale))
+    from networks.stylegan2.op import upfirdn2d
+    if input.is_cuda:
+        sis_hip.library_call("gan.down_conv3x3")
+    return F.conv2d(upfirdn2d(input, fir, pad=(2, 2)), weight * scale, stride=2)
 
 
 _F32_POINTWISE = os.environ.get('SIS_F32_POINTWISE', '1') != '0'  # 0: fp32 1x1 convolutions stay on the library (A/B runs)

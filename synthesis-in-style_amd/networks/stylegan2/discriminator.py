@@ -14,17 +14,24 @@ How a layer executes on MI355X:
   Winograd-domain weight gradient, and the second-order terms the R1 penalty needs -- ``_Conv3x3Backward``);
 * blur = ``upfirdn2d`` and bias + leaky-ReLU * sqrt(2) = ``fused_leaky_relu`` on the HIP kernels of ``networks.
   stylegan2.op`` through their (twice differentiable) autograd Functions;
-* stride-2 and 1x1 convolutions stay on the library (MIOpen / hipBLASLt), which autograd can differentiate twice.
+* stride-2 and 1x1 convolutions stay on the library (MIOpen / hipBLASLt), which autograd can differentiate twice;
+* with ``_POLYPHASE`` on, a (blur, 3x3 stride-2 conv) pair runs as ONE stride-1 Winograd convolution over the four pixel
+  phases of its input (``networks.hip_conv.down_conv3x3``); child modules and state_dict keys are the same either way.
 """
 import math
+import os
 
 import torch
 from torch import nn
 from torch.nn import functional as F
 
 import sis_hip
-from networks.hip_conv import conv3x3, gan_winograd_enabled
+from networks.hip_conv import conv3x3, down_conv3x3, gan_winograd_enabled
 from .op import FusedLeakyReLU
+
+# SIS_GAN_POLYPHASE=1 (or ``polyphase_downsample: true`` in train_stylegan_2.py's config): downsampling 3x3 layers run as one
+# Winograd convolution over the pixel phases of their input (``networks.hip_conv.down_conv3x3``).  Default off: DESIGN.md §5.
+_POLYPHASE = os.environ.get("SIS_GAN_POLYPHASE", "0") == "1"
 
 
 class ScaledLeakyReLU(nn.Module):
@@ -98,6 +105,17 @@ class ConvLayer(nn.Sequential):
         if activate:
             layers.append(FusedLeakyReLU(out_channel) if bias else ScaledLeakyReLU(0.2))
         super().__init__(*layers)
+        self._down3x3 = bool(downsample) and kernel_size == 3
+
+    def forward(self, input):
+        if _POLYPHASE and self._down3x3 and input.is_cuda:
+            blur, conv = self[0], self[1]
+            if conv.bias is None and tuple(blur.pad) == (2, 2) and tuple(blur.kernel.shape) == (4, 4):
+                out = down_conv3x3(input, conv.weight, blur.kernel, conv.scale)   # (declined shapes: blur + library inside, counted)
+                for layer in list(self)[2:]:
+                    out = layer(out)
+                return out
+        return super().forward(input)
 
 
 class ResBlock(nn.Module):

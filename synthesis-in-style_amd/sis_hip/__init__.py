@@ -197,6 +197,13 @@ _SIGNATURES = {
     "sis_enc_block_tail": ([_vp] * 10 + [_i] * 3 + [_vp], _i),
     "sis_enc_latent_heads_supported": ([_i] * 2, _i),
     "sis_enc_latent_heads": ([_vp, _vp] + [_i] * 6 + [_vp], _i),
+    "sis_gan_image_batch": ([_vp, _vp, _vp, _i64, _i, _i, _vp], _i),
+    "sis_phase_split_supported": ([_i] * 2, _i),
+    "sis_phase_split": ([_vp, _vp] + [_i] * 4 + [_vp], _i),
+    "sis_phase_merge": ([_vp, _vp] + [_i] * 4 + [_vp], _i),
+    "sis_down_weight_compose_supported": ([_i] * 2, _i),
+    "sis_down_weight_compose": ([_vp, _vp, _vp, _i, _i, _f, _i, _i, _vp], _i),
+    "sis_down_weight_compose_adjoint": ([_vp, _vp, _vp, _i, _i, _f, _i, _i, _vp], _i),
 }
 
 
@@ -557,10 +564,15 @@ def conv3x3_supported(x, weight, dilation=1):
     d = int(dilation)
     if d < 1 or h % d or w % d:
         return False
-    cout, cin = weight.shape[0], weight.shape[1]
+    return conv3x3_shape_supported(b * d * d, weight.shape[1], weight.shape[0], h // d, w // d)
+
+
+def conv3x3_shape_supported(batch, cin, cout, h, w):
+    """``conv3x3_supported`` for a float32 device tensor [batch, cin, h, w] and a [cout, cin, 3, 3] weight that need not exist yet
+    (``networks.hip_conv.down_conv3x3`` asks for the phase-split form of its operands)."""
     if cout % 8 or cin % 8:
         return False
-    key = (b * d * d, cin, cout, h // d, w // d)
+    key = (int(batch), int(cin), int(cout), int(h), int(w))
     hit = _conv3x3_ok.get(key)
     if hit is None:
         hit = bool(lib().sis_conv3x3_eligible(*key)) and bool(lib().sis_conv3x3_eligible(key[0], cout, cin, key[3], key[4]))
@@ -3176,3 +3188,98 @@ def enc_latent_heads(heads, n_slots=None, sum_heads=False):
                        lambda: lib().sis_enc_latent_heads(_ptr(out), _ptr(table), table.shape[0], batch, latent, slots, int(bool(sum_heads)),
                                                           heads.max_channels, _stream())), "sis_enc_latent_heads")
     return out.view(batch, latent) if sum_heads else out
+
+
+# ------------------------------------------------------------------------------ GAN training (csrc/gan_train_ops.h)
+
+
+def gan_image_batch(images, ids):
+    """Resident uint8 [N, 3, S, S] and int32 ids [B] (both on the device) -> float32 [B, 3, S, S] = (v / 255 - 0.5) / 0.5, the
+    reference loader's ToTensor + Normalize(0.5, 0.5) of the listed samples.  The caller keeps the ids inside 0 .. N - 1 (an id
+    outside yields a NaN sample)."""
+    require_device(images, "images")
+    require_device(ids, "ids")
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[1] != 3 or images.shape[2] != images.shape[3]:
+        raise RuntimeError(f"gan_image_batch: uint8 [N, 3, S, S] images are needed, got {images.dtype} {tuple(images.shape)}")
+    if ids.dtype != torch.int32 or ids.dim() != 1 or ids.numel() == 0 or ids.device != images.device:
+        raise RuntimeError("gan_image_batch: int32 [B] ids on the images' device are needed")
+    images, ids = images.contiguous(), ids.contiguous()
+    n, _, size, _ = images.shape
+    out = torch.empty((ids.numel(), 3, size, size), dtype=torch.float32, device=images.device)
+    with torch.cuda.device(images.device):
+        _check(_launch("gan_image_batch_kernel", 0.0, 5.0 * out.numel(),
+                       lambda: lib().sis_gan_image_batch(_ptr(out), _ptr(images), _ptr(ids), n, ids.numel(), size, _stream())),
+               "sis_gan_image_batch")
+    return out
+
+
+def phase_split_supported(h, w):
+    return bool(lib().sis_phase_split_supported(int(h), int(w)))
+
+
+def phase_split(x):
+    """[B, C, H, W] -> [B, 4C, H/2, W/2], channel order (c, py, px): ``F.pixel_unshuffle(x, 2)``."""
+    x = _f32(x, "input")
+    if x.dim() != 4 or not phase_split_supported(x.shape[2], x.shape[3]):
+        raise RuntimeError(f"phase_split: a [B, C, H, W] tensor with even H and W is needed, got {tuple(x.shape)}")
+    b, c, h, w = x.shape
+    out = torch.empty((b, 4 * c, h // 2, w // 2), dtype=torch.float32, device=x.device)
+    if x.numel():
+        with torch.cuda.device(x.device):
+            _check(_launch("phase_split_kernel", 0.0, 8.0 * x.numel(),
+                           lambda: lib().sis_phase_split(_ptr(out), _ptr(x), b, c, h, w, _stream())), "sis_phase_split")
+    return out
+
+
+def phase_merge(phases):
+    """[B, 4C, H/2, W/2] -> [B, C, H, W]: ``F.pixel_shuffle(phases, 2)``, the inverse and the adjoint of ``phase_split``."""
+    p = _f32(phases, "phases")
+    if p.dim() != 4 or p.shape[1] % 4:
+        raise RuntimeError(f"phase_merge: a [B, 4C, H/2, W/2] tensor is needed, got {tuple(p.shape)}")
+    b, c4, h2, w2 = p.shape
+    out = torch.empty((b, c4 // 4, 2 * h2, 2 * w2), dtype=torch.float32, device=p.device)
+    if p.numel():
+        with torch.cuda.device(p.device):
+            _check(_launch("phase_split_kernel", 0.0, 8.0 * p.numel(),
+                           lambda: lib().sis_phase_merge(_ptr(out), _ptr(p), b, c4 // 4, 2 * h2, 2 * w2, _stream())), "sis_phase_merge")
+    return out
+
+
+def down_weight_compose_supported(fir):
+    """True for the 4 x 4 FIR (the [1, 3, 3, 1] blur of every discriminator layer); other tap counts stay on blur + library."""
+    return fir.dim() == 2 and bool(lib().sis_down_weight_compose_supported(int(fir.shape[0]), int(fir.shape[1])))
+
+
+def _down_weight_args(weight, fir, channels_factor, what):
+    w, f = _f32(weight, what), _f32(fir, "fir")
+    if not down_weight_compose_supported(f):
+        raise RuntimeError(f"{what}: a {tuple(f.shape)} FIR is not supported (4 x 4 only)")
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or w.shape[1] % channels_factor or f.device != w.device:
+        raise RuntimeError(f"{what}: a [Cout, {'4 Cin' if channels_factor == 4 else 'Cin'}, 3, 3] weight on the FIR's device is needed, "
+                           f"got {tuple(w.shape)}")
+    return w, f
+
+
+def down_weight_compose(weight, fir, scale):
+    """W [Cout, Cin, 3, 3], normalised FIR taps [4, 4], scale -> W' [Cout, 4 Cin, 3, 3]: Blur(pad 2) + stride-2 convolution with
+    scale * W as a stride-1 padding-1 convolution over the ``phase_split`` of the layer's input."""
+    w, f = _down_weight_args(weight, fir, 1, "down_weight_compose")
+    cout, cin = w.shape[0], w.shape[1]
+    out = torch.empty((cout, 4 * cin, 3, 3), dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        _check(_launch("down_weight_compose_kernel", 2.0 * 36 * 9 * cout * cin, 4.0 * (w.numel() + out.numel()),
+                       lambda: lib().sis_down_weight_compose(_ptr(out), _ptr(w), _ptr(f), 4, 4, float(scale), cout, cin, _stream())),
+               "sis_down_weight_compose")
+    return out
+
+
+def down_weight_compose_adjoint(grad_phases, fir, scale):
+    """dW' [Cout, 4 Cin, 3, 3] -> dW [Cout, Cin, 3, 3]: the transpose of ``down_weight_compose`` (scale included)."""
+    g, f = _down_weight_args(grad_phases, fir, 4, "down_weight_compose_adjoint")
+    cout, cin = g.shape[0], g.shape[1] // 4
+    out = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=g.device)
+    with torch.cuda.device(g.device):
+        _check(_launch("down_weight_adjoint_kernel", 2.0 * 16 * 9 * cout * cin, 4.0 * (g.numel() + out.numel()),
+                       lambda: lib().sis_down_weight_compose_adjoint(_ptr(out), _ptr(g), _ptr(f), 4, 4, float(scale), cout, cin, _stream())),
+               "sis_down_weight_compose_adjoint")
+    return out

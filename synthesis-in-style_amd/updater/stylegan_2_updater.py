@@ -149,7 +149,8 @@ class Stylegan2Updater(Updater):
         return {"perceputal_path_loss": penalty.detach(), "perceptual_path_lengths": lengths.mean().detach()}  # (sic) reference keys
 
     def update_core(self):
-        batch = {key: value.to(self.device) for key, value in next(self.iterators['images']).items()}
+        # (next_batch: a finite loader -- one pass = one epoch -- is restarted at its end)
+        batch = {key: value.to(self.device) for key, value in self.next_batch('images').items()}
         images, report = batch['image'], get_current_reporter().add_observation
         report(self.update_discriminator(images), 'discriminator')
         if self.iteration % self.d_reg_interval == 0:
