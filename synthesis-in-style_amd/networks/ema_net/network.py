@@ -384,7 +384,7 @@ class EMANet(BaseSegmenter):
         self.fc2 = HipConv2d(256, num_classes, 1)
         self.crit = CrossEntropyLoss2d(ignore_index=ignore_label, reduction='none')
         self.ignore_label = ignore_label
-        for m in self.modules():   # every weight is used once per forward: weight gradients may be batched (hip_conv._may_defer)
+        for m in self.modules():   # every weight is used once per forward: weight gradients may be batched (sis_hip.may_complete_late)
             if isinstance(m, HipConv2d):
                 m._defer_wgrad = True
 

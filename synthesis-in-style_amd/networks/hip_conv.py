@@ -69,18 +69,12 @@ def _conv3x3_wgrad(input, grad_output, weight_shape, d, input_s=None, grad_outpu
                                                False, (0, 0), 1, (False, True, False))[1]
 
 
-def _may_defer(flag, weight):
-    """A layer's weight gradient may wait for ``sis_hip.flush_deferred`` (batched with the other layers of its shape) when the
-    owner of the layer said so (``HipConv2d._defer_wgrad``: its weight is used ONCE per forward) and the weight is a parameter
-    without a gradient in place -- autograd then takes the tensor as it is; with one in place it would add the unwritten result."""
-    return bool(flag) and weight.is_leaf and weight.grad is None and not weight._backward_hooks   # (a tensor hook would read the unwritten gradient)
-
-
 class _Conv3x3Function(Function):
     @staticmethod
     def forward(ctx, input, weight, dilation, prepacked=None, defer=False):
         """``prepacked``: (forward image, adjoint image) of ``weight`` when a ``sis_hip.WinogradPackBank`` wrote them for this step;
-        ``defer``: see ``_may_defer``."""
+        ``defer``: the owner of the layer uses its weight ONCE per forward (``HipConv2d._defer_wgrad``), so the weight gradient may
+        wait for ``sis_hip.flush_deferred`` where ``sis_hip.may_complete_late`` allows."""
         ctx.defer = defer
         input_s = _space_to_batch(input, dilation)
         if prepacked is not None:
@@ -98,7 +92,7 @@ class _Conv3x3Function(Function):
         input, weight, input_s, u_adjoint = ctx.saved_tensors
         grad_input, grad_weight = _Conv3x3Backward.apply(grad_output.contiguous(), input, weight, ctx.dilation,
                                                          ctx.needs_input_grad[0], ctx.needs_input_grad[1], input_s, u_adjoint,
-                                                         _may_defer(ctx.defer, weight) and not torch.is_grad_enabled())
+                                                         ctx.defer and sis_hip.may_complete_late((weight,)))
         return grad_input, grad_weight, None, None, None
 
 
@@ -322,7 +316,7 @@ class _Pointwise(Function):
         if ctx.needs_input_grad[1]:
             if _F32_POINTWISE and sis_hip.conv1x1_wgrad_f32_supported(grad_output, input):
                 grad_weight = sis_hip.conv1x1_wgrad_f32(grad_output, input, for_param=weight.data_ptr(),   # csrc/conv1x1_wgrad_f32.hip
-                                                        defer=_may_defer(ctx.defer, weight) and not torch.is_grad_enabled())
+                                                        defer=ctx.defer and sis_hip.may_complete_late((weight,)))
             else:
                 sis_hip.library_call("hip_conv._Pointwise.wgrad")
                 grad_weight = torch.bmm(g, input.view(b, cin, h * w).transpose(1, 2)).sum(0).view(cout, cin, 1, 1)
@@ -360,7 +354,7 @@ class _PointwiseWithSkip(Function):
         if ctx.needs_input_grad[1]:
             if sis_hip.conv1x1_wgrad_f32_supported(grad_output, input):
                 grad_weight = sis_hip.conv1x1_wgrad_f32(grad_output, input, for_param=weight.data_ptr(),
-                                                        defer=_may_defer(ctx.defer, weight) and not torch.is_grad_enabled())
+                                                        defer=ctx.defer and sis_hip.may_complete_late((weight,)))
             else:
                 sis_hip.library_call("hip_conv._PointwiseWithSkip.wgrad")
                 b, cin, h, w = input.shape
@@ -543,7 +537,9 @@ class _ConvBf16Function(Function):
             key = None if pad_out else weight.data_ptr()   # the parameter's arena slice (sis_hip.grad_out); a padded weight is a copy
             # (deferred: same-shape layers of the trunk in one launch at the end of its backward; plain stride-1 layers only --
             # the zero-stuffed / sampled / padded operands above are temporaries of this call)
-            later = ctx.defer_wgrad and ctx.stride == 1 and not pad_out and scatter is None and grad_weight is None
+            # (no parameter to ask about: the weight is the trunk's standardised one, whose consumer flushes first, see forward)
+            later = (ctx.defer_wgrad and ctx.stride == 1 and not pad_out and scatter is None and grad_weight is None
+                     and sis_hip.may_complete_late(()))
             if k == 3 and s == 1 and sis_hip.conv_bf16_wgrad_supported(b, cin, cout, h, w):
                 grad_weight = sis_hip.conv_bf16_wgrad(input, gy, weight.dtype, for_param=key, defer=later)
             elif k == 1 and s == 1 and _PW_WGRAD_OWN and sis_hip.conv1x1_bf16_wgrad_supported(b, cin, cout, h * w):

@@ -336,7 +336,6 @@ def _wgrad_plan(out_features, in_features):
 
 
 _FUSE_BLOCK_CAST = os.environ.get('SIS_FUSE_BLOCK_CAST', '1') != '0'   # 0: every block casts its own output gradient (A/B runs)
-_NEXT_BLOCK_CAST = {}   # (gradient address, dropout site, backward id) -> its bf16 dropout-cast, handed from block i's backward to block i - 1's
 _FUSE_BIAS_GRAD = os.environ.get('SIS_FUSE_BIAS_GRAD', '1') != '0'   # 0: bias gradients as column-sum launches of their own (A/B runs)
 _WGRAD_STREAMS = {}  # device -> side stream of the weight-gradient GEMMs (process-wide, like the generator's ToRGB stream)
 _WGRAD_SIDE = int(os.environ.get('SIS_WGRAD_STREAM', '0'))   # 1: weight-gradient GEMMs + column sums on a side stream (measured 273 vs 277 images/s: off); 2: column sums only
@@ -480,18 +479,17 @@ class _FusedBlockFn(Function):
         # ---- MLP
         # d(fc2 output), bf16: written by the NEXT block's LayerNorm backward together with the gradient it was cast from (below);
         # the last block -- or a gradient that did not come straight from there -- casts here
-        gl2 = _NEXT_BLOCK_CAST.pop((g3.data_ptr(), site + 2, torch._C._current_graph_task_id()), None) if _FUSE_BLOCK_CAST else None
+        gl2 = S.backward_scope.take(("block cast", site + 2), g3) if _FUSE_BLOCK_CAST else None
         if gl2 is None:
             gl2 = S.dropout_bwd_cast(g3, seed, site + 2, p_mlp)
         k_qkv, k_o, k_f1, k_f2 = ctx.weight_keys
-        # (a gradient may only be deferred while its parameters hold none: autograd would add the unwritten tensor on the spot)
-        new_qkv, new_o, new_f1, new_f2 = (all(p.grad is None and not p._backward_hooks for p in group) for group in ctx.linear_params)   # (a tensor hook would read the unwritten gradient)
+        new_qkv, new_o, new_f1, new_f2 = (S.may_complete_late(group) for group in ctx.linear_params)
         d_w2, d_b2 = wg.run(gl2, act, hid, mlp, k_f2, defer=new_f2)
         d_pre = dgrad(gl2, w2, w2_t, S.EPI_GELU_BWD, pre=pre)   # pre = gelu'(h) * dropout factor, stored by fc1's forward epilogue
         d_w1, d_b1 = wg.run(d_pre, h2, mlp, hid, k_f1, defer=new_f1)
         d_h2 = dgrad(d_pre, w1, w1_t)
         # LN2 backward + the skip connection's gradient, and d(out-projection output) = that sum through the proj dropout
-        fresh1, fresh2 = (all(p.grad is None and not p._backward_hooks for p in pair) for pair in ctx.norm_params)   # no gradient in place, no tensor hook: deferrable
+        fresh1, fresh2 = (S.may_complete_late(pair, wgrad=False) for pair in ctx.norm_params)
         g2, d_ln2_w, d_ln2_b, gl1 = S.layer_norm_bwd_fused(d_h2, x2, mean2, rstd2, ln2_w, residual_grad=g3, cast_seed=seed,
                                                            cast_site=site, cast_p=p_proj, defer=fresh2)
         # ---- attention
@@ -505,10 +503,8 @@ class _FusedBlockFn(Function):
         prev_site = site - 2 if (_FUSE_BLOCK_CAST and site >= 4) else None
         g1, d_ln1_w, d_ln1_b, cast_prev = S.layer_norm_bwd_fused(d_h1, x2d, mean1, rstd1, ln1_w, residual_grad=g2, cast_seed=seed,
                                                                  cast_site=prev_site, cast_p=p_mlp, defer=fresh1)
-        if site == 0:
-            _NEXT_BLOCK_CAST.clear()
-        elif cast_prev is not None:
-            _NEXT_BLOCK_CAST[(g1.data_ptr(), prev_site, torch._C._current_graph_task_id())] = cast_prev
+        if cast_prev is not None:   # for the block that receives g1 as it is now (kept until the end of this backward at the latest)
+            S.backward_scope.hand_over(("block cast", prev_site), g1, cast_prev)
         wg.join()
         d_q, d_k, d_v = d_wqkv.split(hid, 0)
         d_qb, d_kb, d_vb = d_bqkv.split(hid, 0)

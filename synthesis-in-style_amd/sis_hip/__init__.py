@@ -13,8 +13,11 @@ made contiguous, kernels enqueued on the current stream, no host sync).
 import collections
 import ctypes
 import os
+import weakref
 
 import torch
+
+from . import backward_scope
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", os.environ.get("SIS_HIP_LIB", "libsis_hip.so"))  # (override: same-box A/B
@@ -671,7 +674,7 @@ def conv3x3_wgrad(x, grad_output, for_param=None, defer=False):
     batch, cin, h, w = x.shape
     cout = gy.shape[1]
     dw = grad_out(for_param, (cout, cin, 3, 3), torch.float32, x.device)
-    if defer and _conv_wgrad_deferrable():
+    if defer and _flush_at_end():
         _defer_conv_wgrad("f3", x, gy, dw, (batch, cin, cout, h, w))
         return dw
     ws = _workspace(x.device)
@@ -692,18 +695,15 @@ def modconv_demod(s, wsq, scale, demodulate):
     return out
 
 
-# ---- gradient arena: where a parameter's gradient is WRITTEN.  The data-parallel wrap (training/grad_exchange.py) keeps every
-# gradient in flat fp32 buckets that the collectives and the fused SGD read in place.  autograd assigns a gradient that arrives
-# for a parameter without one (no copy), so a weight-gradient kernel that writes its result straight into the parameter's
-# bucket slice -- and returns a fresh view of it -- puts the gradient where the exchange wants it with no gather copy at all
-# (the copy was 139 / 424 MB per EMANet / TransUNet iteration).  ``grad_arena_register`` maps a
-# parameter's storage address to its slice; ``grad_out(key, ...)`` is what the weight-gradient bindings allocate through.
+# ---- gradient arena: where a parameter's gradient is WRITTEN.  autograd keeps the tensor it is handed for a parameter without a
+# gradient, so a weight-gradient kernel that writes into a fresh view of the parameter's slice of the data-parallel wrap's flat
+# fp32 buckets (training/grad_exchange.py) puts the gradient where the exchange and the fused SGD read it, with no gather copy.
+# ``grad_arena_register`` maps a parameter's storage address to its slice; the bindings allocate through ``grad_out(key, ...)``.
 _GRAD_ARENA = {}   # parameter data_ptr -> [weakref to the parameter, flat fp32 buffer, element offset, numel, owner id, handed out]
 
 
 def grad_arena_register(owner, params, flats, offsets):
     """``params[i]``'s gradient lives at ``flats[i][offsets[i] : offsets[i] + params[i].numel()]`` (fp32, contiguous)."""
-    import weakref
     for prm, flat, off in zip(params, flats, offsets):
         _GRAD_ARENA[prm.data_ptr()] = [weakref.ref(prm), flat, int(off), prm.numel(), id(owner), False]
 
@@ -772,44 +772,44 @@ def grad_out_fused(keys, rows, cols, device):
     return torch.empty((sum(rows), cols), dtype=torch.float32, device=device)
 
 
-# ---- deferred reductions.  A training step is full of tiny second-stage launches (sums of split-K slabs, of per-workgroup partial
-# rows) whose results nothing reads before the optimizer or the gradient exchange: TransUNet's step had 169 of them, 1.6 ms of
-# 23.7 -- mostly kernel boundaries.  Inside an autograd backward a binding may therefore DEFER such a reduction: the
-# first-stage kernel runs, its partial results stay in their buffer, and the job joins a queue that ONE launch per kind drains
-# (``flush_deferred``) at the end of the backward (an engine callback), before a data-parallel bucket leaves, before the fused
-# SGD step, or on request.  Until the flush the result tensors (``.grad`` of the parameters) hold no valid data, so a call site
-# may only defer a gradient whose parameter has NO gradient yet (``defer=`` of the bindings: with one in place autograd adds the
-# new tensor to it immediately -- gradient accumulation over two backwards keeps the undeferred path).  Outside a backward (tests
-# calling a binding directly) nothing is deferred.  SIS_DEFER_REDUCES=0 switches it off (A/B runs).
-_DEFER = os.environ.get("SIS_DEFER_REDUCES", "1") != "0"
+# ---- late gradients.  A training step is full of tiny second-stage launches (sums of split-K slabs, of per-workgroup partial rows)
+# and same-shape weight-gradient products whose results nothing reads before the optimizer or the gradient exchange.  Inside a
+# backward a binding may leave such work to ONE launch per kind at the end of the backward (``flush_deferred``; also run before a
+# data-parallel bucket leaves and before the fused optimizer step): its result tensor is handed to autograd now and WRITTEN then.
+# THE RULE: that is done only where ``may_complete_late`` says that autograd keeps the tensor and nobody reads it before the
+# flush; every call site computes ``defer=`` through it.  Outside a backward nothing is ever queued.
+_DEFER = os.environ.get("SIS_DEFER_REDUCES", "1") != "0"        # 0: every reduction where its partial results appear (A/B runs)
+_DEFER_WGRAD = os.environ.get("SIS_DEFER_WGRAD", "1") != "0"   # 0: every weight gradient where its operands appear (A/B runs)
 _deferred = {"ln": [], "wgrad": {}, "conv": {}}   # wgrad: (tokens, out, in, lda, ldb, device) -> [(grad, x, dw, db addresses, storages)]
-_deferred_task = [None]         # the running backward has its end-of-backward callback queued (reset by the callback itself:
-                                # graph task ids are not unique across backwards)
-
-_defer_blockers = set()   # ids of wrappers that read a gradient the moment autograd hands it over (torch's DistributedDataParallel)
+_defer_blockers = set()         # ids of wrappers that read a gradient the moment autograd hands it over (torch's DistributedDataParallel)
+_defer_wgrad_blockers = set()   # ids of data-parallel wrappers with more than one rank: their buckets leave DURING the backward,
+                                # overlapped with it -- a weight gradient held back to its end would put the exchange behind it
 
 
 def block_deferral(owner, blocked=True):
     """No deferred completion of gradients while ``owner`` lives: for consumers that read ``.grad`` inside the backward."""
     (_defer_blockers.add if blocked else _defer_blockers.discard)(id(owner))
+    if blocked:
+        weakref.finalize(owner, _defer_blockers.discard, id(owner))
 
 
-def deferring():
-    """True inside an autograd backward with deferral switched on; queues the end-of-backward flush on first use per backward."""
-    if not _DEFER or _defer_blockers:
-        return False
-    task = torch._C._current_graph_task_id()
-    if task < 0:
-        return False
-    if _deferred_task[0] != task:
-        torch.autograd.Variable._execution_engine.queue_callback(_end_of_backward)
-        _deferred_task[0] = task
-    return True
+def block_wgrad_deferral(owner, blocked=True):
+    (_defer_wgrad_blockers.add if blocked else _defer_wgrad_blockers.discard)(id(owner))
 
 
-def _end_of_backward():
-    _deferred_task[0] = None
-    flush_deferred()
+def may_complete_late(params, wgrad=True):
+    """The gradients of ``params`` may be written as late as ``flush_deferred``: deferral is switched on and not blocked (``wgrad``:
+    for a weight-gradient product, which has a switch and a blocker of its own beside those of the reductions), a backward is
+    running with grad mode off, and every parameter is a leaf without a gradient and without hooks
+    (``backward_scope.taken_as_is``).  ``params`` may be empty: a call site whose consumer flushes before it reads."""
+    return (_DEFER and not _defer_blockers and not (wgrad and (_defer_wgrad_blockers or not _DEFER_WGRAD))
+            and backward_scope.taken_as_is(params))
+
+
+def _flush_at_end():
+    """Queues ``flush_deferred`` for the end of the running backward (False outside one).  Jobs still pending from ANOTHER
+    backward (one that raised, or the enclosing one of a nested backward) are completed first: they own their storages."""
+    return backward_scope.at_end("sis_hip.flush_deferred", lambda: flush_deferred(), first=lambda: flush_deferred())
 
 
 def _hold(*tensors):
@@ -823,15 +823,6 @@ def deferred_pending():
     return len(_deferred["ln"]) + sum(len(v) for v in _deferred["wgrad"].values()) + sum(len(v) for v in _deferred["conv"].values())
 
 
-_DEFER_WGRAD = os.environ.get("SIS_DEFER_WGRAD", "1") != "0"   # 0: the encoder's weight-gradient GEMMs where their operands appear
-_defer_wgrad_blockers = set()   # ids of data-parallel wrappers with more than one rank: their buckets leave DURING the backward,
-                                # overlapped with it -- a gradient held back to its end would put the exchange behind it
-
-
-def block_wgrad_deferral(owner, blocked=True):
-    (_defer_wgrad_blockers.add if blocked else _defer_wgrad_blockers.discard)(id(owner))
-
-
 def deferred_wgrad_pending():
     return any(_deferred["wgrad"].values()) or any(_deferred["conv"].values())
 
@@ -842,10 +833,6 @@ def _defer_conv_wgrad(kind, x, grad_output, dw, dims):
     workgroup count.  ``dw`` is valid after the flush only; the caller guarantees that nothing reads it before."""
     key = (kind,) + tuple(dims) + (dw.dtype, x.device)
     _deferred["conv"].setdefault(key, []).append((x.data_ptr(), grad_output.data_ptr(), dw.data_ptr(), _hold(x, grad_output, dw)))
-
-
-def _conv_wgrad_deferrable():
-    return _DEFER_WGRAD and not _defer_wgrad_blockers and not torch.is_grad_enabled() and deferring()
 
 
 def _flush_conv_wgrads():
@@ -883,13 +870,13 @@ def defer_wgrad_bias(grad, x, dw=None):
     """Queues the weight / bias gradient of a Linear layer (``gemm_bf16_wgrad_bias``'s operands) for the batched launch of
     ``flush_deferred`` -- one pointer-table GEMM per Linear shape for all queued layers, each contracting its whole token axis per
     tile (no split-K slabs, no reduction launches: 2.61 -> 2.02 ms for the twelve blocks of ViT-B at 8 192 tokens,
-    tools/bench_wgrad_multi.py).  Returns (dw, db): allocated now, VALID ONLY AFTER THE FLUSH (the caller checked that the
-    parameters hold no gradient yet, see the comment above).  None when the operands do not qualify (the caller then multiplies
-    on the spot)."""
-    if not (_DEFER_WGRAD and grad.dim() == 2 and x.dim() == 2 and grad.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
+    tools/bench_wgrad_multi.py).  Returns (dw, db): allocated now, VALID ONLY AFTER THE FLUSH (the caller asked
+    ``may_complete_late`` for the layer's parameters).  None outside a backward and when the operands do not qualify (the caller
+    then multiplies on the spot)."""
+    if not (grad.dim() == 2 and x.dim() == 2 and grad.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
             and grad.stride(1) == 1 and x.stride(1) == 1 and grad.shape[0] == x.shape[0] and grad.stride(0) % 8 == 0
             and x.stride(0) % 8 == 0 and grad.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0 and grad.shape[1] % 4 == 0
-            and x.shape[1] % 4 == 0 and not _defer_wgrad_blockers and deferring()):
+            and x.shape[1] % 4 == 0 and _flush_at_end()):
         return None
     k, m = grad.shape
     n = x.shape[1]
@@ -1392,15 +1379,15 @@ def conv_bf16_wgrad_supported(batch, cin, cout, h, w):
 
 def conv_bf16_wgrad(x, grad_output, out_dtype=torch.float32, for_param=None, defer=False):
     """dL/dw [Cout,Cin,3,3] (float32 or bfloat16) of a stride-1, padding-1 3x3 convolution from its bf16 input and dL/dy.
-    ``defer``: inside a backward the launch may wait for ``flush_deferred`` (batched with the other layers of its shape); the
-    caller then guarantees that nobody reads the result before the flush."""
+    ``defer`` (the caller's ``may_complete_late``): the launch waits for ``flush_deferred``, batched with the other layers of its
+    shape."""
     require_device(x, "input")
     if x.dtype != torch.bfloat16 or grad_output.dtype != torch.bfloat16 or not x.is_contiguous() or not grad_output.is_contiguous():
         raise RuntimeError("conv_bf16_wgrad: input and grad_output must be contiguous bfloat16 tensors")
     b, cin, h, w = x.shape
     cout = grad_output.shape[1]
     dw = grad_out(for_param, (cout, cin, 3, 3), out_dtype, x.device)
-    if defer and _conv_wgrad_deferrable():
+    if defer and _flush_at_end():
         _defer_conv_wgrad(3, x, grad_output, dw, (b, cin, cout, h, w))
         return dw
     ws = _workspace(x.device)
@@ -1587,7 +1574,7 @@ def conv1x1_bf16_wgrad(x, grad_output, out_dtype=torch.float32, for_param=None, 
     if grad_output.shape[0] != b or grad_output[0, 0].numel() != pixels:
         raise RuntimeError("conv1x1_bf16_wgrad: input and grad_output disagree on batch / plane size")
     dw = grad_out(for_param, (cout, cin, 1, 1), out_dtype, x.device)
-    if defer and _conv_wgrad_deferrable():   # (as conv_bf16_wgrad)
+    if defer and _flush_at_end():   # (as conv_bf16_wgrad)
         _defer_conv_wgrad(1, x, grad_output, dw, (b, cin, cout, pixels))
         return dw
     ws = _workspace(x.device)
@@ -1919,9 +1906,8 @@ def layer_norm_fwd(x, gamma, beta, eps, out_dtype=None):
 
 def layer_norm_bwd_fused(grad_y, x, mean, rstd, gamma, residual_grad=None, cast_seed=None, cast_site=None, cast_p=0.0, defer=False):
     """LayerNorm backward of a pre-norm residual block: dx = residual_grad + LN'(grad_y); with ``cast_site`` also returns
-    bf16(dx * dropout factor of that site) -> (dx, dgamma, dbeta, cast or None).  ``defer``: the caller vouches that the two
-    parameters hold NO gradient yet (autograd will then take dgamma / dbeta as ``.grad`` as they are -- with a gradient in place it
-    would ADD them on the spot); inside a backward their reduction then joins the deferred queue (``flush_deferred``)."""
+    bf16(dx * dropout factor of that site) -> (dx, dgamma, dbeta, cast or None).  ``defer`` (the caller's
+    ``may_complete_late`` for the two parameters): the reduction to dgamma / dbeta joins the deferred queue (``flush_deferred``)."""
     x = x.contiguous()
     g = grad_y.contiguous()
     n = x.shape[-1]
@@ -1933,7 +1919,7 @@ def layer_norm_bwd_fused(grad_y, x, mean, rstd, gamma, residual_grad=None, cast_
     if residual_grad is not None:
         residual_grad = _f32(residual_grad, "residual_grad")
     ws = torch.empty(lib().sis_layer_norm_workspace_floats(n), dtype=torch.float32, device=x.device)
-    if defer and deferring():   # d(gamma) / d(beta) by the batched reduction at the end of the backward (flush_deferred)
+    if defer and _flush_at_end():   # d(gamma) / d(beta) by the batched reduction at the end of the backward (flush_deferred)
         with torch.cuda.device(x.device):
             _check(lib().sis_layer_norm_bwd_fused_partial(_ptr(dx), _ptr(ws), _ptr(g), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(gamma),
                                                           _DTYPE_CODE[x.dtype], _DTYPE_CODE[g.dtype], rows, n, _ptr(residual_grad),
@@ -2213,7 +2199,7 @@ def conv1x1_wgrad_f32(grad_output, input, for_param=None, defer=False):
     cout = grad_output.shape[1]
     L = lib()
     dw = grad_out(for_param, (cout, cin, 1, 1), torch.float32, input.device)
-    if (defer and _conv_wgrad_deferrable() and grad_output.dtype == torch.float32 and input.dtype == torch.float32
+    if (defer and _flush_at_end() and grad_output.dtype == torch.float32 and input.dtype == torch.float32
             and grad_output.is_contiguous() and input.is_contiguous() and grad_output.data_ptr() % 16 == 0 and input.data_ptr() % 16 == 0):
         _defer_conv_wgrad("f1", input, grad_output, dw, (b, cin, cout, h * w))
         return dw

@@ -39,6 +39,8 @@ import torch
 import torch.distributed as dist
 from torch import nn
 
+from sis_hip import backward_scope
+
 
 _DEBUG = os.environ.get("SIS_DP_DEBUG", "0") == "1"
 # Collectives straight into librccl.so (ctypes on the communicator ProcessGroupNCCL owns: a few microseconds of host time each,
@@ -209,7 +211,6 @@ class BucketedDataParallel(nn.Module):
         self.buckets: Optional[List[_Bucket]] = None
         self._bucket_of = {}
         self._order: List[torch.Tensor] = []      # discovery: parameters in the order their gradients became ready
-        self._callback_queued = False
         self._flushed = 0
         # copied_elems / in_place_elems: gradient elements the gather had to copy / found already written into their bucket slice
         self.stats = {"backwards": 0, "collectives": 0, "discovery_backwards": 0, "copied_elems": 0, "in_place_elems": 0}
@@ -284,10 +285,8 @@ class BucketedDataParallel(nn.Module):
 
     # ---- backward ----------------------------------------------------------------------------------------------------
     def _on_grad(self, param):
-        if not self._callback_queued:
-            # runs once the engine has finished THIS backward (the mechanism DDP's reducer and FSDP use)
-            torch.autograd.Variable._execution_engine.queue_callback(self._finish)
-            self._callback_queued = True
+        # ``_finish`` runs once the engine has finished THIS backward; ``_begin`` at its first gradient (one that raised ran no ``_finish``)
+        backward_scope.at_end(self, self._finish, first=self._begin)
         if self.buckets is None:
             self._order.append(param)
             return
@@ -298,6 +297,8 @@ class BucketedDataParallel(nn.Module):
         bucket.pending -= 1
         if bucket.pending == 0:
             self._flush(bucket)
+
+    _on_grad.completes_late_gradients = True   # (``_flush``, before it reads a gradient: backward_scope.taken_as_is)
 
     @torch.no_grad()
     def _gather(self, bucket: _Bucket):
@@ -369,7 +370,6 @@ class BucketedDataParallel(nn.Module):
     @torch.no_grad()
     def _finish(self):
         """End of a backward: discovery -> fix the plan and reduce everything now; otherwise join the side stream."""
-        self._callback_queued = False
         self.stats["backwards"] += 1
         if self.buckets is None:
             self.stats["discovery_backwards"] += 1
@@ -387,7 +387,7 @@ class BucketedDataParallel(nn.Module):
             if not self._joined:
                 torch.cuda.current_stream(self.device).wait_stream(self._comm_stream)
                 self._joined = True
-            self._reset()
+            self._release_slices()
             raise RuntimeError(f"BucketedDataParallel: buckets {missing} did not receive all of their gradients in this backward "
                                "(a parameter used in the first iteration was unused now)")
         for work in self._pending:
@@ -396,19 +396,17 @@ class BucketedDataParallel(nn.Module):
         if not self._joined:
             torch.cuda.current_stream(self.device).wait_stream(self._comm_stream)   # optimizer.step() reads the buckets
             self._joined = True
-        self._reset()
+        self._release_slices()
 
-    def _reset(self):
-        self._flushed = 0
+    def _begin(self):
+        self._flushed, self._postponed = 0, []
+        for b in self.buckets or []:
+            b.pending = len(b.params)
+
+    def _release_slices(self):
         if self._on_gpu:
-            try:
-                import sis_hip
-                sis_hip.grad_arena_reset(self)   # every bucket slice may be handed to a weight-gradient kernel again
-            except ImportError:
-                pass
-        if self.buckets is not None:
-            for b in self.buckets:
-                b.pending = len(b.params)
+            import sis_hip
+            sis_hip.grad_arena_reset(self)   # every bucket slice may be handed to a weight-gradient kernel again
 
     def _plan(self):
         """Buckets of <= bucket_cap_mb in readiness order (the first bucket is the first to be complete in every later

@@ -104,6 +104,59 @@ def test_ddp_wrap_world_size_2_gloo(flavour):
     assert out[0][3] != out[1][3], "batch-norm statistics must be per-rank"
 
 
+def _failed_backward_worker(rank, world, port, out):
+    sys.path.insert(0, os.path.join(ROOT, "synthesis-in-style_amd"))
+    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from training.grad_exchange import BucketedDataParallel
+        torch.manual_seed(0)
+        net = _TinySegmenter()
+        ddp = BucketedDataParallel(net, bucket_cap_mb=1)
+        gen = torch.Generator().manual_seed(100)
+        x = torch.randn(2, 3, 8, 8, generator=gen)
+        y = torch.randint(0, 3, (2, 8, 8), generator=gen)
+        nn.functional.cross_entropy(ddp(x), y).backward()                   # discovery: fixes the bucket plan
+        n_params = len(list(net.parameters()))
+        ddp.zero_grad(set_to_none=True)
+
+        def boom(grad):
+            raise ZeroDivisionError("raised inside the backward")
+
+        arm = net.bn.register_forward_hook(lambda mod, inp, res: res.register_hook(boom) and None)
+        raised = False
+        try:   # the head's gradients arrive, then the hook on the head's input raises: no end-of-backward callback runs
+            nn.functional.cross_entropy(ddp(x), y).backward()
+        except ZeroDivisionError:
+            raised = True
+        arm.remove()
+        arrived = n_params - sum(b.pending for b in ddp.buckets)
+        ddp.zero_grad(set_to_none=True)
+        before = ddp.stats["backwards"]
+        x2 = torch.randn(2, 3, 8, 8, generator=gen)
+        nn.functional.cross_entropy(ddp(x2), y).backward()
+        torch.manual_seed(0)
+        solo = _TinySegmenter()
+        nn.functional.cross_entropy(solo(x2), y).backward()
+        expect = {id(p): q.grad for p, q in zip(net.parameters(), solo.parameters())}
+        in_buckets = all(p.grad.data_ptr() == view.data_ptr() and torch.allclose(view, expect[id(p)], atol=1e-6)
+                         for b in ddp.buckets for p, view in zip(b.params, b.views))
+        out[rank] = (raised, arrived, n_params, ddp.stats["backwards"] - before, in_buckets)
+    finally:
+        dist.destroy_process_group()
+
+
+def test_bucketed_wrap_exchanges_again_after_a_backward_that_raised():
+    """A backward that raises runs no end-of-backward callback.  The next backward must still queue ``_finish`` (the exchange)
+    and count its buckets from the start, whatever the failed one left half-way."""
+    out = mp.Manager().dict()
+    mp.spawn(_failed_backward_worker, args=(1, _free_port(), out), nprocs=1, join=True)
+    raised, arrived, n_params, finished, in_buckets = out[0]
+    assert raised and 0 < arrived < n_params, (raised, arrived, n_params)   # it failed after SOME gradients had been counted
+    assert finished == 1, "the backward after the failed one did not run _finish"
+    assert in_buckets, "the buckets do not hold the gradients of the backward after the failed one"
+
+
 class _TinyEmaShaped(nn.Module):
     """CPU stand-in with EMANet's optimizer-relevant shape: conv weights / norm scales / biases in three groups and
     one parameter that never receives a gradient (EMANet's ``emau.conv1``: find_unused_parameters)."""
