@@ -955,6 +955,28 @@ int sis_down_weight_compose(float* w_phases, const float* w, const float* fir, i
 int sis_down_weight_compose_adjoint(float* dw, const float* dw_phases, const float* fir, int fir_h, int fir_w, float scale, int cout,
                                     int cin, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * PNG files of the dataset's [image | label] pairs, encoded on the device (csrc/png_encode.h).  Integer
+ * arithmetic only; two encodes of the same input give the same bytes.
+ * sis_png_capacity (create_dataset_for_segmentation.py:84-90, save_image): the per-image stride of the output buffer in bytes
+ *   for files of `height` rows and `width_total` = image width + label width pixels: with F = height * (1 + 3 * width_total)
+ *   filtered bytes, 57 + 2 + ceil((10 + 9 F) / 8) + 4 rounded up to a multiple of 16.  Host query; 0 for a size < 1.
+ * sis_png_encode_pairs_workspace_bytes (:84-90, save_image): bytes of device workspace of one call (row offsets, checksums).
+ * sis_png_encode_pairs (:84-90, save_image; :62-67 the concatenation of image and label, here never materialised): image
+ *   uint8 [n][height][image_width][3], label uint8 [n][height][label_width][3] or null with label_width 0 (device) ->
+ *   out[i * out_stride ...] the complete PNG file of pair i (8-bit RGB, width image_width + label_width, one IDAT: filter
+ *   Sub on every row, one deflate block with the fixed Huffman codes, run-length matches at distance 1; the byte format is
+ *   stated in DESIGN.md §14) and sizes[i] its length in bytes (int32, device).  The entry clears all n * out_stride bytes
+ *   itself.  ihdr_crc: CRC-32 of "IHDR" + its 13 data bytes (it depends on the two sizes only; the caller computes it).
+ *   Declines with an error code and launches nothing when n, height or image_width is < 1, label_width < 0 (or not 0 without
+ *   a label, or 0 with one), image_width + label_width > 4096, n > 65535, out_stride < sis_png_capacity or no multiple of 16,
+ *   out not 16-byte aligned, or the workspace smaller than the query says. */
+int64_t sis_png_capacity(int height, int width_total);
+int64_t sis_png_encode_pairs_workspace_bytes(int n, int height);
+int sis_png_encode_pairs(uint8_t* out, int* sizes, const uint8_t* image, const uint8_t* label, int n, int height, int image_width,
+                         int label_width, int64_t out_stride, uint32_t ihdr_crc, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

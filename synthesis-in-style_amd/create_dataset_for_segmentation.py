@@ -30,6 +30,13 @@ reference shifts the later ids instead).
 reference's :52-81) labels every image with a trained PixelEnsembleClassifier instead
 (segmentation/dataset_gan_segmenter.py, fused on the device); the label half of the PNG is then the class-colour image.
 
+``--png-encoder device`` (default ``pil``: the loop above, unchanged): the label image is built on the device in every branch
+and ``sis_hip.png_encode_pairs`` turns each ``[image | label]`` pair into a complete PNG file on the label side stream
+(csrc/png_encode.h, DESIGN.md §14: filter Sub, one fixed-Huffman deflate block with run-length matches -- larger files than
+PIL's, the same pixels); the host copies the finished files to pinned memory and only writes them, on ``--png-writers``
+threads (default 4, at most 8), under the same directory layout and file names.  The writers are drained before the split
+files are written and when the loop ends; an exception of a writer is raised in the main thread.
+
 Multi-GPU (BASELINE.json configs[2]: 100k images on 8 GPUs): one process per GPU (``torch.distributed.run`` or
 manual RANK/WORLD_SIZE), rank r generates the image-id range ``shard_range(num_images, r, world)``; no collective.
 The latent stream is one global seeded stream: every rank draws the whole stream in batch order and keeps its own
@@ -49,12 +56,53 @@ import torch
 import sis_hip  # noqa: F401  (fails loudly at import when libsis_hip.so is missing: there is no CPU path)
 from networks import get_stylegan2_generator
 from segmentation.gan_local_edit.factor_catalog import FactorCatalog
-from utils.dataset_creation import label_and_encode, seeded_latents, shard_range
+from utils.dataset_creation import encode_pairs_on_device, label_and_encode, seeded_latents, shard_range
+
+PNG_ENCODERS = ("pil", "device")
+MAX_PNG_WRITERS = 8
+
+
+def png_writer_count(requested) -> int:
+    """``--png-writers`` clamped to 1 .. 8 (a fixed small pool: never sized by the host's CPU count)."""
+    return max(1, min(MAX_PNG_WRITERS, int(4 if requested is None else requested)))
+
+
+def image_path(image_id: int, base_dir: Path, name_format: str = "{id}.png") -> Path:
+    return base_dir / str(image_id // 100000) / str(image_id // 1000) / name_format.format(id=image_id)
+
+
+def write_file(dest: Path, data) -> None:
+    dest.parent.mkdir(exist_ok=True, parents=True)
+    with open(dest, "wb") as f:
+        f.write(data)
+
+
+class PngWriterPool:
+    """A few threads that write finished files; ``drain`` waits for all of them and re-raises a writer's exception in the
+    caller.  ``keep_in_flight`` bounds the backlog (and with it the pinned buffers that are alive)."""
+
+    def __init__(self, writers: int):
+        from concurrent.futures import ThreadPoolExecutor
+        self.pool = ThreadPoolExecutor(max_workers=png_writer_count(writers), thread_name_prefix="png-writer")
+        self.futures = []
+
+    def submit(self, dest: Path, data) -> None:
+        self.futures.append(self.pool.submit(write_file, dest, data))
+
+    def drain(self, keep_in_flight: int = 0) -> None:
+        while len(self.futures) > keep_in_flight:
+            self.futures.pop(0).result()
+
+    def close(self) -> None:
+        try:
+            self.drain()
+        finally:
+            self.pool.shutdown(wait=True)
 
 
 def save_image(image: numpy.ndarray, image_id: int, base_dir: Path, name_format: str = "{id}.png"):
     from PIL import Image
-    dest = base_dir / str(image_id // 100000) / str(image_id // 1000) / name_format.format(id=image_id)
+    dest = image_path(image_id, base_dir, name_format)
     dest.parent.mkdir(exist_ok=True, parents=True)
     Image.fromarray(image).save(str(dest))
 
@@ -106,6 +154,9 @@ def cluster_based_segmenter(args, creation_config, image_size):
 
 
 def build_dataset(args, creation_config, rank=0, world_size=1):
+    encoder = getattr(args, 'png_encoder', None) or 'pil'
+    if encoder not in PNG_ENCODERS:
+        raise ValueError(f"--png-encoder {encoder!r}: one of {PNG_ENCODERS}")
     device = torch.device('cuda', rank % max(torch.cuda.device_count(), 1))
     torch.cuda.set_device(device)
     g = load_generator(args.checkpoint, creation_config.get('image_size', 256), creation_config.get('latent_size', 512),
@@ -124,12 +175,30 @@ def build_dataset(args, creation_config, rank=0, world_size=1):
     lo, hi = shard_range(args.num_images, rank, world_size)
     dropped = []
     save_dir = Path(args.save_to) if args.save_to else None
+    on_device = encoder == 'device' and save_dir is not None
+    writers = PngWriterPool(getattr(args, 'png_writers', None)) if on_device else None
+    name_format = f"{{id:0{max(4, len(str(args.num_images)))}d}}.png"
     torch.random.manual_seed(creation_config.get('seed', 1))
     done = 0
 
+    def label_image_on_device(pixels, labels):
+        """The label half of the pair as uint8 [B, H, W, 3] on the device: the four branches of ``flush`` below."""
+        if cluster_segmenter is not None:
+            return labels["cluster_segmenter"][1]
+        if dataset_gan is not None:
+            return labels["dataset_gan"]
+        if label_layer in labels:
+            k = catalogs[label_layer].cluster_centers.shape[0]
+            lab = labels[label_layer]
+            if lab.shape[-1] != pixels.shape[2]:
+                lab = torch.nn.functional.interpolate(lab[:, None].float(), size=pixels.shape[1:3], mode='nearest')[:, 0].long()
+            grey = (lab * 255 // max(k - 1, 1)).to(torch.uint8)
+            return grey[..., None].expand(-1, -1, -1, 3).contiguous()
+        return torch.zeros_like(pixels)
+
     def flush(job):
         """Host side of a finished batch: wait for its label pass, then encode / write the files."""
-        first_id, pixels, labels, ready = job
+        first_id, pixels, labels, ready, files = job
         if ready is not None:
             ready.synchronize()
         keep = None
@@ -137,6 +206,15 @@ def build_dataset(args, creation_config, rank=0, world_size=1):
             keep = ~labels["cluster_segmenter"][2].cpu().numpy().astype(bool)
             dropped.extend(first_id + int(i) for i in numpy.nonzero(~keep)[0])
         if save_dir is None:
+            return
+        if files is not None:   # encoded on the device: the host only writes buffer[i, :sizes[i]]
+            buffer, sizes, encoded = files
+            encoded.synchronize()
+            buffer, sizes = buffer.numpy(), sizes.numpy()
+            for idx in range(buffer.shape[0]):
+                if keep is None or keep[idx]:
+                    writers.submit(image_path(first_id + idx, save_dir, name_format), memoryview(buffer[idx, :int(sizes[idx])]))
+            writers.drain(keep_in_flight=2 * args.batch_size)
             return
         rgb = pixels.cpu().numpy()
         if cluster_segmenter is not None:
@@ -154,8 +232,9 @@ def build_dataset(args, creation_config, rank=0, world_size=1):
             lab_img = numpy.zeros_like(rgb)
         save_generated_images(rgb, lab_img, first_id, save_dir, args.num_images, keep)
 
-    pending = None
-    with torch.no_grad():
+    def run_batches():
+        nonlocal done
+        pending = None
         for first in range(0, args.num_images, args.batch_size):
             n = min(args.batch_size, args.num_images - first)
             z = seeded_latents(args.batch_size, g.style_dim, device)[:n]  # the whole stream is drawn on every rank (pinned) ...
@@ -174,13 +253,23 @@ def build_dataset(args, creation_config, rank=0, world_size=1):
             # side stream; the next batch's forward is issued first.  Without a cluster-based labeller the call is the one it
             # always was (callers wrap label_and_encode with its earlier signature).
             extra = {} if cluster_segmenter is None else {"cluster_segmenter": cluster_segmenter}
-            job = (a,) + label_and_encode(image, acts, catalogs, dataset_gan, **extra)
+            pixels, labels, ready = label_and_encode(image, acts, catalogs, dataset_gan, **extra)
+            # device encoder: label image, PNG files and their copy to pinned memory follow the label pass on its stream
+            files = encode_pairs_on_device(pixels, lambda: label_image_on_device(pixels, labels), ready) if on_device else None
+            job = (a, pixels, labels, ready, files)
             if pending is not None:
                 flush(pending)
             pending = job
             done += b - a
         if pending is not None:
             flush(pending)
+
+    try:
+        with torch.no_grad():
+            run_batches()
+    finally:
+        if writers is not None:
+            writers.close()   # drained here: before the caller writes the split files, and on every way out
     torch.cuda.synchronize()
     args.dropped_image_ids = dropped   # the labeller's drop decisions of this rank (empty without a cluster-based labeller)
     return done, (lo, hi)
@@ -221,7 +310,7 @@ def main(args):
     print(f"rank {rank}/{world}: generated image ids [{lo}, {hi}) = {done} images{note}", flush=True)
 
 
-if __name__ == "__main__":
+def build_parser():
     parser = argparse.ArgumentParser(description="Generate a synthetic dataset with a StyleGAN2 generator on MI355X")
     parser.add_argument("checkpoint", nargs='?', default=None, help="generator checkpoint holding 'g_ema' (omit: random weights)")
     parser.add_argument("config", nargs='?', default=None, help="json: image_size, latent_size, seed, catalogs{layer: centres.npy}, label_layer; "
@@ -235,6 +324,15 @@ if __name__ == "__main__":
     parser.add_argument("--classifier-path", help="trained PixelEnsembleClassifier checkpoint (segmenter_type \"dataset_gan\")")
     parser.add_argument("--num-clusters", type=int, default=-1, help="K of catalogs/K.json and merged_classes_K.json "
                         "(segmenter_type \"black_white_handwritten_printed\")")
+    parser.add_argument("--png-encoder", choices=PNG_ENCODERS, default="pil", help="pil: PIL on the host, one file at a time; "
+                        "device: the PNG files are encoded on the device (fixed-Huffman deflate: larger files, the same pixels) "
+                        "and the host only writes them")
+    parser.add_argument("--png-writers", type=png_writer_count, default=4, help="file-writer threads of --png-encoder device "
+                        "(clamped to 1..8)")
     parser.add_argument("-ssd", "--semantic-segmentation-base-dir", type=Path, help="directory that holds catalogs/ and "
                         "merged_classes_K.json, as create_semantic_segmentation.py and the annotation step leave it")
-    main(parser.parse_args())
+    return parser
+
+
+if __name__ == "__main__":
+    main(build_parser().parse_args())

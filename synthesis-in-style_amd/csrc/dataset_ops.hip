@@ -777,3 +777,6 @@ extern "C" int sis_make_image_u8(uint8_t* out, const float* x, int batch, int ch
     SIS_CHECK_LAUNCH("make_image_kernel");
     return 0;
 }
+
+// the PNG files of the [image | label] pairs, encoded on the device (create_dataset_for_segmentation.py:84-90, save_image)
+#include "png_encode.h"

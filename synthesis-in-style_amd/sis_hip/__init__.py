@@ -207,6 +207,9 @@ _SIGNATURES = {
     "sis_down_weight_compose_supported": ([_i] * 2, _i),
     "sis_down_weight_compose": ([_vp, _vp, _vp, _i, _i, _f, _i, _i, _vp], _i),
     "sis_down_weight_compose_adjoint": ([_vp, _vp, _vp, _i, _i, _f, _i, _i, _vp], _i),
+    "sis_png_capacity": ([_i, _i], _i64),
+    "sis_png_encode_pairs_workspace_bytes": ([_i, _i], _i64),
+    "sis_png_encode_pairs": ([_vp] * 4 + [_i] * 4 + [_i64, ctypes.c_uint32, _vp, _i64, _vp], _i),
 }
 
 
@@ -3269,3 +3272,53 @@ def down_weight_compose_adjoint(grad_phases, fir, scale):
                        lambda: lib().sis_down_weight_compose_adjoint(_ptr(out), _ptr(g), _ptr(f), 4, 4, float(scale), cout, cin, _stream())),
                "sis_down_weight_compose_adjoint")
     return out
+
+
+# ------------------------------------------------------------------------------ PNG pairs (csrc/png_encode.h)
+
+
+def png_capacity(height, width_total):
+    """Bytes per image of the output buffer of ``png_encode_pairs`` (the largest file the format can produce, rounded to 16)."""
+    return int(lib().sis_png_capacity(int(height), int(width_total)))
+
+
+def png_ihdr_crc(width_total, height):
+    """CRC-32 of the IHDR chunk of an 8-bit RGB image: it depends on the two sizes only, so the host computes it."""
+    import struct
+    import zlib
+    return zlib.crc32(b"IHDR" + struct.pack(">IIBBBBB", int(width_total), int(height), 8, 2, 0, 0, 0))
+
+
+def png_encode_pairs(image_u8, label_u8=None, out=None):
+    """uint8 [N, H, W, 3] images and, optionally, uint8 [N, H, Wl, 3] labels (device) -> (buffer uint8 [N, stride], sizes int32
+    [N]): ``buffer[i, :sizes[i]]`` is the complete PNG file of ``[image i | label i]`` (the reference's save_image of the
+    concatenated pair, create_dataset_for_segmentation.py:84-90), encoded on the device; the pair itself is never put together.
+    ``out``: a contiguous uint8 [N, stride] buffer to write into, stride >= ``png_capacity(H, W + Wl)`` and a multiple of 16."""
+    require_device(image_u8, "image")
+    if image_u8.dtype != torch.uint8 or image_u8.dim() != 4 or image_u8.shape[3] != 3:
+        raise RuntimeError(f"png_encode_pairs: uint8 [N, H, W, 3] images are needed, got {image_u8.dtype} {tuple(image_u8.shape)}")
+    image_u8 = image_u8.contiguous()
+    n, h, w, _ = image_u8.shape
+    wl = 0
+    if label_u8 is not None:
+        require_device(label_u8, "label")
+        if label_u8.dtype != torch.uint8 or label_u8.dim() != 4 or label_u8.shape[3] != 3 or label_u8.shape[:2] != image_u8.shape[:2] \
+                or label_u8.device != image_u8.device:
+            raise RuntimeError(f"png_encode_pairs: uint8 [{n}, {h}, Wl, 3] labels on the images' device are needed, got {label_u8.dtype} "
+                               f"{tuple(label_u8.shape)}")
+        label_u8 = label_u8.contiguous()
+        wl = label_u8.shape[2]
+    stride = png_capacity(h, w + wl)
+    if out is None:
+        out = torch.empty((n, stride), dtype=torch.uint8, device=image_u8.device)   # (the entry clears it)
+    elif out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != n or not out.is_contiguous() or out.device != image_u8.device:
+        raise RuntimeError(f"png_encode_pairs: out must be a contiguous uint8 [{n}, stride] tensor on the images' device")
+    sizes = torch.empty((n,), dtype=torch.int32, device=image_u8.device)
+    ws_bytes = lib().sis_png_encode_pairs_workspace_bytes(n, h)
+    ws = torch.empty((max(ws_bytes, 4) // 4,), dtype=torch.int32, device=image_u8.device)
+    with torch.cuda.device(image_u8.device):
+        _check(_launch("png_emit_kernel", 0.0, 2.0 * 3 * n * h * (w + wl) + 2.0 * out.numel(),   # rows read twice; memset + files
+                       lambda: lib().sis_png_encode_pairs(_ptr(out), _ptr(sizes), _ptr(image_u8), _ptr(label_u8), n, h, w, wl, out.shape[1],
+                                                          png_ihdr_crc(w + wl, h), _ptr(ws), ws.numel() * 4, _stream())),
+               "sis_png_encode_pairs")
+    return out, sizes

@@ -105,3 +105,23 @@ def label_and_encode(image: torch.Tensor, activations: Dict[int, torch.Tensor], 
     for t in [image] + read:
         t.record_stream(side)  # the caching allocator must not hand these blocks out again before the side pass has read them
     return pixels, labels, side.record_event()
+
+
+def encode_pairs_on_device(pixels: torch.Tensor, label_image, ready: Optional[torch.cuda.Event] = None):
+    """The PNG files of ``[pixels | label_image()]`` (create_dataset_for_segmentation.py:84-90 of the reference, save_image)
+    encoded on the device and copied to PINNED host memory.  ``pixels``: uint8 [B, H, W, 3] as ``label_and_encode`` returns
+    them, ``label_image``: a callable that builds the uint8 [B, H, W, 3] label half on the device, ``ready``: the event
+    ``label_and_encode`` returned.  With an event everything is issued on the label side stream, behind the label pass, so it
+    runs beside the next batch's forward like that pass; without one (SIS_LABEL_STREAM=0) on the current stream.  Returns
+    (buffer uint8 [B, stride] host, sizes int32 [B] host, event): synchronise on the event, then ``buffer[i, :sizes[i]]``
+    is file i."""
+    device = pixels.device
+    side = _LABEL_STREAMS.get(device) if ready is not None else None
+    stream = side if side is not None else torch.cuda.current_stream(device)
+    with torch.cuda.stream(stream):
+        buffer, sizes = sis_hip.png_encode_pairs(pixels, label_image())
+        host_buffer = torch.empty(buffer.shape, dtype=torch.uint8, pin_memory=True)
+        host_sizes = torch.empty(sizes.shape, dtype=torch.int32, pin_memory=True)
+        host_buffer.copy_(buffer, non_blocking=True)
+        host_sizes.copy_(sizes, non_blocking=True)
+        return host_buffer, host_sizes, stream.record_event()
