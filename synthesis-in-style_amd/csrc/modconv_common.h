@@ -1,5 +1,6 @@
-// Shared between the two modulated-convolution kernels (modconv_mfma.hip: register-staged, any shape;
-// modconv_mfma2.hip: LDS-DMA double-buffered fast path).
+// Shared by the modulated-convolution kernels (modconv_mfma.hip: register-staged, any shape; modconv_mfma2.hip: LDS-DMA
+// double-buffered; modconv_wino.hip / modconv_wino24.h: Winograd) and their C entries (modconv_entries.hip): the kernel
+// argument, the tile and split-K planning, and one launcher per kernel file.
 #pragma once
 #include "sis_device.h"
 
@@ -47,6 +48,24 @@ struct ConvCfg {
 
 static inline int mc_ilog2_ceil(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
+// "No tile classes yet" and "no split-K": what a plan starts from, and what a launcher that declined leaves to be redone.
+static inline void mc_reset_tiles(ConvParams& p) { p.npos_tiles = 0; p.ncls = 0; p.nb_max = 0; }
+static inline void mc_reset_splitk(ConvParams& p) { p.ksplit = 1; p.kchunk = p.Cin; p.slab = nullptr; }
+
+// Everything of a launch that the tile plan does not decide.  A plain convolution passes null s / dscale / noise / bias.
+static inline ConvParams mc_params(float* out, const float* x, const float* wpk, const float* s, const float* dscale,
+                                   const float* noise, int64_t noise_bstride, const float* noise_w, const float* bias,
+                                   int batch, int cin, int cout, int h, int w, int oh, int ow, int ors, bool fuse) {
+    ConvParams p;
+    p.x = x; p.wpk = wpk; p.s = s; p.dscale = dscale; p.noise = noise; p.noise_w = noise_w; p.bias = bias;
+    p.out = out; p.noise_bstride = noise_bstride;
+    p.B = batch; p.Cin = cin; p.Cout = cout; p.H = h; p.W = w; p.OH = oh; p.OW = ow; p.ORS = ors; p.fuse = fuse;
+    p.cout_vec4 = (cout % 4 == 0) && (((uintptr_t)wpk & 15) == 0);
+    mc_reset_tiles(p);
+    mc_reset_splitk(p);
+    return p;
+}
+
 // Adds a tile class covering positions [h0,h1) x [w0,w1) with tiles of at most npos positions.
 static inline void mc_add_class(ConvParams& p, int npos, int ext, int batch, int h0, int h1, int w0, int w1,
                                 int tw_cap, int nb_cap) {
@@ -82,9 +101,42 @@ static inline void mc_set_padded_xt(ConvParams& p, int pad_lo, int ext) {
     }
 }
 
-// modconv_mfma2.hip: returns 0 on success, 1 on error, -1 when the shape is not eligible for the fast path.
-int modconv_v2_launch(ConvParams& p, int mode, int ks, hipStream_t st, void* workspace, int64_t workspace_bytes);
-// modconv_wino.hip: Winograd F(2x2,3x3) path for stride-1 3x3 layers (p.wpk must then hold the transformed weights).
+
+// Tile plan of the Winograd F(2x2,3x3) kernels: one class of 16 x 16-pixel regions (conflict-free patch reads), rows staged
+// as the 16-byte aligned superset of the halo (left pad 4, right pad 4).
+static inline void mc_wino_tiles(ConvParams& p) {
+    mc_reset_tiles(p);
+    mc_add_class(p, 256, 2, p.B, 0, p.H, 0, p.W, 16, 16);
+    TileClass& tc = p.cls[0];
+    tc.xt = tc.nb * ((1 << tc.th_log2) + 2) * ((1 << tc.tw_log2) + 8);
+}
+
+// Chooses the K split of a kernel with `mblk` output channels per workgroup and `cc` input channels per chunk: below
+// `min_blocks` (tile x oc-block) workgroups, enough slices to reach `target`, slices a multiple of the chunk size and at
+// least two chunks long, and the slabs [ksplit][B][Cout][OH][ORS] must fit the caller's workspace (none: no split).
+static inline void mc_plan_splitk(ConvParams& p, int mblk, int cc, int min_blocks, int target, void* workspace,
+                                  int64_t workspace_bytes) {
+    mc_reset_splitk(p);
+    const int64_t blocks = (int64_t)p.npos_tiles * sis_cdiv(p.Cout, mblk);
+    if (blocks >= min_blocks || p.Cin < 4 * cc || !workspace) return;
+    int want = (int)((target + blocks - 1) / blocks);
+    const int max_split = p.Cin / (2 * cc);
+    if (want > max_split) want = max_split;
+    const int64_t out_bytes = (int64_t)p.B * p.Cout * p.OH * p.ORS * 4;
+    if ((int64_t)want * out_bytes > workspace_bytes) want = (int)(workspace_bytes / out_bytes);
+    if (want < 2) return;
+    p.kchunk = sis_cdiv(sis_cdiv(p.Cin, want), cc) * cc;
+    p.ksplit = sis_cdiv(p.Cin, p.kchunk);
+    p.slab = (float*)workspace;
+}
+
+// One launcher per kernel file.  Each returns 0 on success, 1 on error (sis_last_error), -1 when the shape is not the
+// kernel's: the caller (modconv_entries.hip) then tries the next one.
+// modconv_wino.hip: Winograd F(2x2,3x3), stride-1 3x3 layers; p.wpk holds the transformed weights, tiles from mc_wino_tiles.
 int modconv_wino_launch(ConvParams& p, hipStream_t st, void* workspace, int64_t workspace_bytes, bool plan_only = false);
-// Block tile of the fast path for `mode` (positions per tile depend on the selected wave layout).
-int modconv_v2_tile(int mode, int* mblk, int* npos);
+// modconv_mfma2.hip: LDS-DMA kernel.  Rewrites every class's xt to the padded-row form BEFORE it can still decline.
+int modconv_v2_launch(ConvParams& p, int mode, int ks, hipStream_t st, void* workspace, int64_t workspace_bytes);
+// modconv_mfma.hip: register-staged kernel, any shape; wants exact-halo xt and no split-K.
+int modconv_v1_launch(ConvParams& p, int mode, int ks, hipStream_t st);
+// modconv_mfma2.hip: adds the K slices of p.slab in slice order and applies the epilogue.
+int modconv_splitk_finish_launch(const ConvParams& p, hipStream_t st);

@@ -277,130 +277,11 @@ int launch(ConvParams& p, hipStream_t st) {
     return 0;
 }
 
-int check_common(const char* name, const void* out, const void* x, const void* wpk, const void* s, const void* dscale,
-                 int batch, int cin, int cout, int h, int w, int oh, int ow) {
-    SIS_REQUIRE(out && x && wpk && s && dscale, "%s: null pointer", name);
-    SIS_REQUIRE(batch > 0 && cin > 0 && cout > 0 && h > 0 && w > 0, "%s: non-positive size", name);
-    SIS_REQUIRE((int64_t)batch * cin * h * w < ((int64_t)1 << 31) && (int64_t)batch * cout * oh * ow < ((int64_t)1 << 31),
-                "%s: tensor too large for 32-bit plane offsets", name);
-    return 0;
-}
-
 }  // namespace
 
-static void init_params(ConvParams& p) {
-    p.slab = nullptr; p.ksplit = 1; p.npos_tiles = 0; p.ncls = 0; p.nb_max = 0;
-}
-
-extern "C" int sis_modconv2d(float* out, const float* x, const float* wpk, const float* s, const float* dscale,
-                             const float* noise, int64_t noise_batch_stride, const float* noise_weight,
-                             const float* bias, int batch, int cin, int cout, int h, int w, int ksize, int fuse_act,
-                             const float* wino_u, void* workspace, int64_t workspace_bytes, void* stream) {
-    if (batch == 0) return 0;
-    if (check_common("sis_modconv2d", out, x, wpk, s, dscale, batch, cin, cout, h, w, h, w)) return 1;
-    SIS_REQUIRE(ksize == 1 || ksize == 3, "sis_modconv2d: kernel size %d not supported (1 or 3)", ksize);
-    if (noise) SIS_REQUIRE(noise_weight, "sis_modconv2d: noise given without noise_weight");
-    ConvParams p;
-    init_params(p);
-    p.x = x; p.wpk = wpk; p.s = s; p.dscale = dscale; p.noise = noise; p.noise_w = noise_weight; p.bias = bias;
-    p.out = out; p.noise_bstride = noise_batch_stride;
-    p.B = batch; p.Cin = cin; p.Cout = cout; p.H = h; p.W = w; p.OH = h; p.OW = w; p.ORS = w; p.fuse = fuse_act != 0;
-    p.kchunk = cin;
-    p.cout_vec4 = (cout % 4 == 0) && (((uintptr_t)wpk & 15) == 0);
-    mc_add_class(p, 256, ksize - 1, batch, 0, h, 0, w, 32, 16);
-    if (wino_u && ksize == 3 && w % 4 == 0 && h % 2 == 0) {
-        // Winograd tiles: 16x16-pixel regions (conflict-free patch reads), rows staged as 16-byte aligned supersets
-        ConvParams pw = p;
-        pw.npos_tiles = 0; pw.ncls = 0; pw.nb_max = 0;
-        mc_add_class(pw, 256, 2, batch, 0, h, 0, w, 16, 16);
-        TileClass& tcw = pw.cls[0];
-        tcw.xt = tcw.nb * ((1 << tcw.th_log2) + 2) * ((1 << tcw.tw_log2) + 8);
-        pw.wpk = wino_u;
-        const int rcw = modconv_wino_launch(pw, (hipStream_t)stream, workspace, workspace_bytes);
-        if (rcw >= 0) return rcw;
-    }
-    const int rc = modconv_v2_launch(p, 0, ksize, (hipStream_t)stream, workspace, workspace_bytes);
-    if (rc >= 0) return rc;
-    p.ksplit = 1; p.kchunk = cin; p.slab = nullptr;
-    p.npos_tiles = 0; p.ncls = 0; p.nb_max = 0;
-    mc_add_class(p, 256, ksize - 1, batch, 0, h, 0, w, 32, 16);  // exact-halo tiles for the register-staged kernel
-    if (ksize == 3) return launch<0, 3>(p, (hipStream_t)stream);
-    return launch<0, 1>(p, (hipStream_t)stream);
-}
-
-// Plain (unmodulated) 3x3 convolution, stride 1, padding 1, on the Winograd kernel: unit style, unit demodulation,
-// no epilogue.  Used for the segmentation networks' 3x3 layers (forward, and data gradient with adjoint weights).
-static int conv3x3_plan(ConvParams& p, float* out, const float* x, const float* u, int batch, int cin, int cout, int h,
-                        int w) {
-    if (batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0) return -1;
-    if ((int64_t)batch * (cin > cout ? cin : cout) * h * w >= ((int64_t)1 << 31)) return -1;
-    if (w % 4 != 0 || h % 2 != 0 || cin % 8 != 0 || cout % 4 != 0) return -1;
-    init_params(p);
-    p.x = x; p.wpk = u; p.s = nullptr; p.dscale = nullptr; p.noise = nullptr; p.noise_w = nullptr; p.bias = nullptr;
-    p.out = out; p.noise_bstride = 0;
-    p.B = batch; p.Cin = cin; p.Cout = cout; p.H = h; p.W = w; p.OH = h; p.OW = w; p.ORS = w; p.fuse = 0;
-    p.kchunk = cin;
-    p.cout_vec4 = (((uintptr_t)u & 15) == 0);
-    mc_add_class(p, 256, 2, batch, 0, h, 0, w, 16, 16);
-    TileClass& tc = p.cls[0];
-    tc.xt = tc.nb * ((1 << tc.th_log2) + 2) * ((1 << tc.tw_log2) + 8);
-    return 0;
-}
-
-extern "C" int sis_conv3x3_eligible(int batch, int cin, int cout, int h, int w) {
-    ConvParams p;
-    if (conv3x3_plan(p, nullptr, nullptr, nullptr, batch, cin, cout, h, w) < 0) return 0;
-    return modconv_wino_launch(p, nullptr, nullptr, 0, true) == 0 ? 1 : 0;
-}
-
-extern "C" int sis_conv3x3(float* out, const float* x, const float* u, int batch, int cin, int cout, int h, int w,
-                           void* workspace, int64_t workspace_bytes, void* stream) {
-    if (batch == 0) return 0;
-    SIS_REQUIRE(out && x && u, "sis_conv3x3: null pointer");
-    ConvParams p;
-    SIS_REQUIRE(conv3x3_plan(p, out, x, u, batch, cin, cout, h, w) == 0,
-                "sis_conv3x3: needs W %% 4 == 0, H %% 2 == 0, Cin %% 8 == 0, Cout %% 4 == 0 and < 2^31 elements "
-                "(got %d x %dx%d, %d -> %d)", batch, h, w, cin, cout);
-    const int rc = modconv_wino_launch(p, (hipStream_t)stream, workspace, workspace_bytes);
-    SIS_REQUIRE(rc >= 0, "sis_conv3x3: shape %dx%d, %d -> %d not eligible for the Winograd kernel", h, w, cin, cout);
-    return rc;
-}
-
-extern "C" int sis_modconv2d_up(float* t, const float* x, const float* wpk, const float* s, const float* dscale,
-                                int batch, int cin, int cout, int h, int w, int t_row_stride, void* workspace,
-                                int64_t workspace_bytes, void* stream) {
-    if (batch == 0) return 0;
-    const int oh = 2 * h + 1, ow = 2 * w + 1;
-    if (t_row_stride <= 0) t_row_stride = ow;
-    SIS_REQUIRE(t_row_stride >= ow, "sis_modconv2d_up: row stride %d smaller than 2W+1 = %d", t_row_stride, ow);
-    if (check_common("sis_modconv2d_up", t, x, wpk, s, dscale, batch, cin, cout, h, w, oh, t_row_stride)) return 1;
-    ConvParams p;
-    init_params(p);
-    p.x = x; p.wpk = wpk; p.s = s; p.dscale = dscale; p.noise = nullptr; p.noise_w = nullptr; p.bias = nullptr;
-    p.out = t; p.noise_bstride = 0;
-    p.B = batch; p.Cin = cin; p.Cout = cout; p.H = h; p.W = w; p.OH = oh; p.OW = ow; p.ORS = t_row_stride; p.fuse = 0;
-    p.kchunk = cin;
-    p.cout_vec4 = (cout % 4 == 0) && (((uintptr_t)wpk & 15) == 0);
-    int mblk, npos;
-    modconv_v2_tile(1, &mblk, &npos);
-    for (int pass = 0; pass < 2; ++pass) {
-        const int np = pass == 0 ? npos : 128;
-        p.npos_tiles = 0; p.ncls = 0; p.nb_max = 0;
-        mc_add_class(p, np, 1, batch, 0, h, 0, w, 32, 8);          // interior positions
-        mc_add_class(p, np, 1, batch, h, h + 1, 0, w, np, h >= 16 ? 4 : 8);  // last row (T[2H, 0..2W-1]); 16 x 16: 8 style rows here made the grid's LDS 86 KB, one workgroup per CU
-        // last col (T[0..2H-1, 2W]): one position per row, each staged as a padded 8-float row, and the corner: capped at
-        // 64 rows / 4 samples per tile.  The grid's LDS size follows its LARGEST class: uncapped, the last column's staging
-        // area (2 x 65 x 8 floats per channel) and the corner's 8 style rows made it 120 KB -- one workgroup per CU for
-        // every tile of the layer (measured with hipOccupancyMaxActiveBlocksPerMultiprocessor; 74-80 KB now: two per CU).
-        // (4x4 and 8x8 layers keep 8 samples per edge tile: they are split-K / launch bound, more tiles cost them 30-50 %.)
-        const int edge_nb = h >= 16 ? 4 : 8;
-        mc_add_class(p, np < 64 ? np : 64, 1, batch, 0, h, w, w + 1, 1, edge_nb);
-        mc_add_class(p, np, 1, batch, h, h + 1, w, w + 1, 1, edge_nb);   // corner    (T[2H, 2W])
-        if (pass == 0) {
-            const int rc = modconv_v2_launch(p, 1, 3, (hipStream_t)stream, workspace, workspace_bytes);
-            if (rc >= 0) return rc;
-        }
-    }
-    p.ksplit = 1; p.kchunk = cin; p.slab = nullptr;
-    return launch<1, 3>(p, (hipStream_t)stream);
+int modconv_v1_launch(ConvParams& p, int mode, int ks, hipStream_t st) {
+    if (mode == 1 && ks == 3) return launch<1, 3>(p, st);
+    if (mode == 0 && ks == 3) return launch<0, 3>(p, st);
+    if (mode == 0 && ks == 1) return launch<0, 1>(p, st);
+    return -1;
 }

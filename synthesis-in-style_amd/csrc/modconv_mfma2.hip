@@ -471,61 +471,23 @@ int launch_v2(ConvParams& p, hipStream_t st) {
     SIS_OCC_REPORT((modconv_v2_kernel<MODE, KS, C>), C::THREADS, lds);
     hipLaunchKernelGGL((modconv_v2_kernel<MODE, KS, C>), dim3((unsigned)bx, p.ksplit), dim3(C::THREADS), lds, st, p, xt_max);
     SIS_CHECK_LAUNCH("modconv_v2_kernel");
-    if (p.ksplit > 1) {
-        const int64_t total = (int64_t)p.B * p.Cout * p.OH * p.ORS;
-        const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-        hipLaunchKernelGGL(modconv_splitk_finish, dim3(blocks), dim3(256), 0, st, p, total, total);
-        SIS_CHECK_LAUNCH("modconv_splitk_finish");
-    }
-    return 0;
+    return p.ksplit > 1 ? modconv_splitk_finish_launch(p, st) : 0;
 }
+
+// Wave layouts: 128 co x 256 px per workgroup for the stride-1 modes, 64 co x 128 positions for the transposed one.  The 3x3
+// layouts have 8 waves, 4 per SIMD (3-10 % faster than the 4-wave layouts they replaced: more waves to cover barrier skew).
+typedef V2Cfg<0, 3, 2, 4, 2, 2, 4> Conv3B;   // 512 thr, wave 64 co x 64 px,  2 WG/CU
+typedef V2Cfg<0, 1, 2, 2, 2, 4, 2> Conv1A;   // 256 thr, wave 64 co x 128 px, 2 WG/CU
+typedef V2Cfg<1, 3, 2, 4, 1, 1, 4> UpB;      // 512 thr, wave 32 co x 32 pos x 4 phases
 
 }  // namespace
 
-void modconv_splitk_finish_launch(const ConvParams& p, hipStream_t st) {
+int modconv_splitk_finish_launch(const ConvParams& p, hipStream_t st) {
     const int64_t total = (int64_t)p.B * p.Cout * p.OH * p.ORS;
     const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
     hipLaunchKernelGGL(modconv_splitk_finish, dim3(blocks), dim3(256), 0, st, p, total, total);
-}
-
-// Chooses the K split: enough (tile x oc-block x slice) workgroups to give every CU ~2, slices a
-// multiple of the chunk size, and the slabs must fit the caller's workspace.
-static void plan_splitk(ConvParams& p, int mblk, int cc, int64_t workspace_bytes) {
-    p.ksplit = 1; p.kchunk = p.Cin; p.slab = nullptr;
-    const int64_t blocks = (int64_t)p.npos_tiles * sis_cdiv(p.Cout, mblk);
-    static const int min_blocks = getenv("SIS_SPLITK_MIN_BLOCKS") ? atoi(getenv("SIS_SPLITK_MIN_BLOCKS")) : 384;
-    static const int target = getenv("SIS_SPLITK_TARGET") ? atoi(getenv("SIS_SPLITK_TARGET")) : 512;
-    if (blocks >= min_blocks || p.Cin < 4 * cc) return;
-    int want = (int)((target + blocks - 1) / blocks);
-    const int max_split = p.Cin / (2 * cc);
-    if (want > max_split) want = max_split;
-    const int64_t out_bytes = (int64_t)p.B * p.Cout * p.OH * p.ORS * 4;
-    if ((int64_t)want * out_bytes > workspace_bytes) want = (int)(workspace_bytes / out_bytes);
-    if (want < 2) return;
-    int kchunk = sis_cdiv(sis_cdiv(p.Cin, want), cc) * cc;
-    p.kchunk = kchunk;
-    p.ksplit = sis_cdiv(p.Cin, kchunk);
-}
-
-// Wave layouts (SIS_CONV_CFG=<mode0><mode1> digits select experiments; default "11": the 8-wave layouts,
-// 4 waves per SIMD, measured 3-10 % faster than the 4-wave ones: more waves to cover barrier skew).
-typedef V2Cfg<0, 3, 2, 2, 2, 4, 2> Conv3A;   // 256 thr, 128 co x 256 px, wave 64x128, 2 WG/CU
-typedef V2Cfg<0, 3, 2, 4, 2, 2, 4> Conv3B;   // 512 thr, 128 co x 256 px, wave 64x64,  2 WG/CU (4 waves/SIMD)
-typedef V2Cfg<0, 1, 2, 2, 2, 4, 2> Conv1A;
-typedef V2Cfg<1, 3, 1, 4, 2, 1, 2> UpA;      // 256 thr, 64 co x 128 pos, wave 64 co x 32 pos x 4 phases
-typedef V2Cfg<1, 3, 2, 4, 1, 1, 4> UpB;      // 512 thr, 64 co x 128 pos, wave 32 co x 32 pos x 4 phases
-typedef V2Cfg<1, 3, 1, 8, 2, 1, 2> UpC;      // 512 thr, 64 co x 256 pos, wave 64 co x 32 pos x 4 phases
-
-int modconv_v2_tile(int mode, int* mblk, int* npos) {
-    static int cfg = -1;
-    if (cfg < 0) {
-        const char* e = getenv("SIS_CONV_CFG");
-        cfg = (e && e[0] >= '0' && e[0] <= '9' && e[1] >= '0' && e[1] <= '9') ? (e[0] - '0') * 10 + (e[1] - '0') : 11;
-    }
-    const int c = mode == 0 ? cfg / 10 : cfg % 10;
-    if (mode == 0) { *mblk = 128; *npos = 256; }
-    else { *mblk = 64; *npos = c == 2 ? 256 : 128; }
-    return c;
+    SIS_CHECK_LAUNCH("modconv_splitk_finish");
+    return 0;
 }
 
 int modconv_v2_launch(ConvParams& p, int mode, int ks, hipStream_t st, void* workspace, int64_t workspace_bytes) {
@@ -534,13 +496,10 @@ int modconv_v2_launch(ConvParams& p, int mode, int ks, hipStream_t st, void* wor
     for (int c = 0; c < p.ncls; ++c)
         if (p.cls[c].w0 % 4 != 0) return -1;
     mc_set_padded_xt(p, mode == 0 ? ks / 2 : 1, mode == 0 ? ks - 1 : 1);
-    int mblk, npos;
-    const int c = modconv_v2_tile(mode, &mblk, &npos);
-    plan_splitk(p, mblk, cc, workspace ? workspace_bytes : 0);
-    if (p.ksplit > 1) p.slab = (float*)workspace;
-    if (mode == 0 && ks == 3) return c == 1 ? launch_v2<0, 3, Conv3B>(p, st) : launch_v2<0, 3, Conv3A>(p, st);
+    // split-K when position-tiles x oc-blocks leave the CUs under ~2 workgroups each: up to 512 of them
+    mc_plan_splitk(p, mode == 0 ? 128 : 64, cc, 384, 512, workspace, workspace_bytes);
+    if (mode == 0 && ks == 3) return launch_v2<0, 3, Conv3B>(p, st);
     if (mode == 0 && ks == 1) return launch_v2<0, 1, Conv1A>(p, st);
-    if (mode == 1 && ks == 3)
-        return c == 1 ? launch_v2<1, 3, UpB>(p, st) : c == 2 ? launch_v2<1, 3, UpC>(p, st) : launch_v2<1, 3, UpA>(p, st);
+    if (mode == 1 && ks == 3) return launch_v2<1, 3, UpB>(p, st);
     return -1;
 }

@@ -20,8 +20,8 @@
 // wave holds 32 channels x 16 blocks x 25 planes in 200 registers and two waves share a SIMD.  Workgroup = 4 waves =
 // 64 channels x 32 blocks (128 positions), 4 input channels per chunk, 46 080 B of LDS (52 224 B for 128 x 128 maps): TWO workgroups per CU, one wave of each
 // on every SIMD, so that one's barrier, patch transform, fragment reads, prologue and epilogue fall under the other's MFMAs
-// (the 8-wave / 64-block / 8-channel tile, SIS_UPFIR_WAVES=8, has both waves of a SIMD behind the same barrier: 5.22 -> 4.94 ms
-// on the three large layers).  Lane l of a wave: block l & 15, input channel (l >> 4) of the 4-deep MFMA step.
+// (an earlier 8-wave / 64-block / 8-channel tile had both waves of a SIMD behind the same barrier and was 5 % slower on the three
+// large layers).  Lane l of a wave: block l & 15, input channel (l >> 4) of the 4-deep MFMA step.
 //
 // The transposed convolution has H + 1 position rows and W + 1 position columns.  Two passes, one C call:
 //   interior: the (H/2) x (W/2) blocks of positions (0 .. H-1) x (0 .. W-1) per sample, all 25 products (this kernel): T rows
@@ -30,7 +30,7 @@
 // A block of the edge has zero padding for two of its three patch rows (columns), so 20 of its 25 products (24 in the corner)
 // would multiply zeros; numbering (H/2 + 1) x (W/2 + 1) blocks through this kernel, as it once did, also left every layer of
 // Generator(256) half a round of workgroups past a whole number of rounds ("Up-convolution").
-// Interior blocks are numbered row-major over (sample, block row, block column) and a workgroup takes 8 NW CONSECUTIVE blocks
+// Interior blocks are numbered row-major over (sample, block row, block column) and a workgroup takes 32 CONSECUTIVE blocks
 // (no tile classes; H W / 4 per sample: a multiple of 32 for every layer of the generator, no padding blocks).  Its input tile
 // is the run of image rows those blocks touch -- a 32-block tile of a 64 x 64 map is one block row, 3 image rows -- each staged
 // whole as [4 zeros | W pixels | 4 zeros] by LDS-DMA through a buffer descriptor whose out-of-range lanes write the zeros
@@ -46,9 +46,9 @@
 namespace {
 
 constexpr int UF_MBLK = 64;                           // output channels per workgroup
-// NW = waves per workgroup (8 or 4): NW input channels per chunk (one channel's DMA per wave) and 8 NW position blocks per
-// workgroup.  NW = 4 halves the tile and the chunk (46 - 52 KB of LDS): TWO workgroups share a CU, one wave of each per SIMD, and
-// one's barrier / transform / epilogue falls under the other's MFMAs.
+constexpr int UF_CC = 4;                              // input channels per chunk: one channel's DMA per wave
+constexpr int UF_NBLK = 32;                           // position blocks per workgroup
+constexpr int UF_THREADS = 256;
 constexpr int UF_PLANES = 16;
 constexpr int UF_WROW = UF_PLANES * UF_MBLK + 32;     // floats per channel row of the weight stage [8 plane pairs][64 co][2]:
                                                       // +32 puts the two channels a 32-lane group of a ds_read_b64 touches 32
@@ -65,12 +65,7 @@ struct UpFirParams {
     int xs;                        // floats per channel of the staged tile (multiple of 256)
 };
 
-// ABL: timing ablations for development builds (tools/bench_upfir.py, SIS_UPFIR_ABL): bit 0 no barrier in the chunk loop, bit 1 no
-// DMA in the loop, bit 2 no patch reads / transform in the loop, bit 3 no weight-fragment reads in the loop.  Any non-zero value
-// computes WRONG results; the shipped kernel is ABL = 0.
-template <int PIPE, int ABL = 0, int NW = 8>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2))) void modconv_upfir_kernel(const UpFirParams p) {
-    constexpr int UF_CC = NW, UF_NBLK = 8 * NW, UF_THREADS = 64 * NW;
+__global__ __launch_bounds__(UF_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void modconv_upfir_kernel(const UpFirParams p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* Wl = lds;                              // [2][CC][WROW]
     float* Xl = Wl + 2 * UF_CC * UF_WROW;         // [2][CC][xs]
@@ -143,211 +138,111 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     stage(0, 0);
     __syncthreads();   // vmcnt(0) + barrier: chunk 0 landed
 
-    if constexpr (PIPE == 4) {
-        // Chunks software-pipelined across the barrier (NW == 4, one MFMA step per chunk).  In the plain loop every chunk starts behind
-        // its barrier with 10 LDS reads and ~25 VALU of transform before its first MFMA.  Here the barrier of chunk c sits behind the
-        // request for its last fragment pair (pair 7, asked for in iteration 5): from there on nobody reads buffer c & 1 any more, chunk
-        // c + 1 has landed (its DMA was issued a whole chunk earlier) -- so the DMA of chunk c + 2 goes into the freed buffer and the
-        // transform of chunk c + 1 runs in slices between the 20 MFMAs of plane row 3, and the next chunk starts with MFMAs.
-        static_assert(NW == 4 && ABL == 0, "pipelined form: 4-wave workgroups, no ablations");
-        const int n_chunks = p.Cin / UF_CC;
-        if (n_chunks > 1) stage(UF_CC, 1);
-        __syncthreads();   // (chunk 1 landed as well: once per workgroup)
-        float tA[4][4], tB[4][4], cm0[4], raw[3][3], svn;
-        auto tr_read = [&](int c, int bufc) {   // patch and style of chunk c (clamped past the end: values unused)
-            const int cl = min(c, n_chunks - 1) * UF_CC + kq;
-            svn = Sl[soff + cl];
-            const float* xb = Xl + (bufc * UF_CC + kq) * p.xs + xoff;
+    // Chunks software-pipelined across the barrier (one MFMA step per chunk).  A plain loop starts every chunk behind
+    // its barrier with 10 LDS reads and ~25 VALU of transform before its first MFMA.  Here the barrier of chunk c sits behind the
+    // request for its last fragment pair (pair 7, asked for in iteration 5): from there on nobody reads buffer c & 1 any more, chunk
+    // c + 1 has landed (its DMA was issued a whole chunk earlier) -- so the DMA of chunk c + 2 goes into the freed buffer and the
+    // transform of chunk c + 1 runs in slices between the 20 MFMAs of plane row 3, and the next chunk starts with MFMAs.
+    const int n_chunks = p.Cin / UF_CC;
+    if (n_chunks > 1) stage(UF_CC, 1);
+    __syncthreads();   // (chunk 1 landed as well: once per workgroup)
+    float tA[4][4], tB[4][4], cm0[4], raw[3][3], svn;
+    auto tr_read = [&](int c, int bufc) {   // patch and style of chunk c (clamped past the end: values unused)
+        const int cl = min(c, n_chunks - 1) * UF_CC + kq;
+        svn = Sl[soff + cl];
+        const float* xb = Xl + (bufc * UF_CC + kq) * p.xs + xoff;
 #pragma unroll
-            for (int r = 0; r < 3; ++r)
+        for (int r = 0; r < 3; ++r)
 #pragma unroll
-                for (int j = 0; j < 3; ++j) raw[r][j] = xb[r * RW + j];
+            for (int j = 0; j < 3; ++j) raw[r][j] = xb[r * RW + j];
+    };
+    // column transform of patch row r: rows 1 and 2 ARE rows 1 and 3 of t, row 0 waits in cm0 for the row transform
+    auto tr_col = [&](int r, float (&t)[4][4]) {
+        const float d0 = raw[r][0] * svn, d1 = raw[r][1] * svn, d2 = raw[r][2] * svn;
+        float* o = r == 0 ? cm0 : (r == 1 ? t[1] : t[3]);
+        o[0] = d0 - d1; o[1] = d1; o[2] = d2 - d1; o[3] = d2;
+        // (pinned where it stands: the results are used in the NEXT chunk only, and the compiler otherwise sinks the arithmetic
+        // into that chunk's block, in front of its first MFMA)
+        asm volatile("" : "+v"(o[0]), "+v"(o[1]), "+v"(o[2]), "+v"(o[3]));
+    };
+    auto tr_row = [&](float (&t)[4][4]) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            t[0][j] = cm0[j] - t[1][j]; t[2][j] = t[3][j] - t[1][j];
+            asm volatile("" : "+v"(t[0][j]), "+v"(t[2][j]));
+        }
+    };
+    tr_read(0, 0);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) tr_col(r, tA);
+    tr_row(tA);
+    const int woff = kq * UF_WROW + (wm * 32 + l15) * 2;
+    // ring of three fragment pairs, carried from chunk to chunk: pair 0 of chunk c + 1 takes pair 6's slot once that is used up
+    sis_f32x2 ra[3][2];
+    ra[0][0] = *reinterpret_cast<const sis_f32x2*>(Wl + woff); ra[0][1] = *reinterpret_cast<const sis_f32x2*>(Wl + woff + 32);
+    auto chunk = [&](auto parity, int c, const float (&t)[4][4], float (&tn)[4][4]) {
+        constexpr int B = decltype(parity)::value;
+        const float* wb = Wl + B * UF_CC * UF_WROW + woff;
+        auto fetch = [&](int k) {
+            ra[k % 3][0] = *reinterpret_cast<const sis_f32x2*>(wb + k * 2 * UF_MBLK);
+            ra[k % 3][1] = *reinterpret_cast<const sis_f32x2*>(wb + k * 2 * UF_MBLK + 32);
         };
-        // column transform of patch row r: rows 1 and 2 ARE rows 1 and 3 of t, row 0 waits in cm0 for the row transform
-        auto tr_col = [&](int r, float (&t)[4][4]) {
-            const float d0 = raw[r][0] * svn, d1 = raw[r][1] * svn, d2 = raw[r][2] * svn;
-            float* o = r == 0 ? cm0 : (r == 1 ? t[1] : t[3]);
-            o[0] = d0 - d1; o[1] = d1; o[2] = d2 - d1; o[3] = d2;
-            // (pinned where it stands: the results are used in the NEXT chunk only, and the compiler otherwise sinks the arithmetic
-            // into that chunk's block, in front of its first MFMA)
-            asm volatile("" : "+v"(o[0]), "+v"(o[1]), "+v"(o[2]), "+v"(o[3]));
-        };
-        auto tr_row = [&](float (&t)[4][4]) {
+        fetch(1);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                t[0][j] = cm0[j] - t[1][j]; t[2][j] = t[3][j] - t[1][j];
-                asm volatile("" : "+v"(t[0][j]), "+v"(t[2][j]));
+        for (int k = 0; k < 8; ++k) {
+            if (k + 2 < 8) fetch(k + 2);
+            if (k == 7) {   // (behind the barrier: chunk c + 1 has landed)
+                ra[0][0] = *reinterpret_cast<const sis_f32x2*>(Wl + (B ^ 1) * UF_CC * UF_WROW + woff);
+                ra[0][1] = *reinterpret_cast<const sis_f32x2*>(Wl + (B ^ 1) * UF_CC * UF_WROW + woff + 32);
             }
-        };
-        tr_read(0, 0);
 #pragma unroll
-        for (int r = 0; r < 3; ++r) tr_col(r, tA);
-        tr_row(tA);
-        const int woff = kq * UF_WROW + (wm * 32 + l15) * 2;
-        // ring of three fragment pairs, carried from chunk to chunk: pair 0 of chunk c + 1 takes pair 6's slot once that is used up
-        sis_f32x2 ra[3][2];
-        ra[0][0] = *reinterpret_cast<const sis_f32x2*>(Wl + woff); ra[0][1] = *reinterpret_cast<const sis_f32x2*>(Wl + woff + 32);
-        auto chunk = [&](auto parity, int c, const float (&t)[4][4], float (&tn)[4][4]) {
-            constexpr int B = decltype(parity)::value;
-            const float* wb = Wl + B * UF_CC * UF_WROW + woff;
-            auto fetch = [&](int k) {
-                ra[k % 3][0] = *reinterpret_cast<const sis_f32x2*>(wb + k * 2 * UF_MBLK);
-                ra[k % 3][1] = *reinterpret_cast<const sis_f32x2*>(wb + k * 2 * UF_MBLK + 32);
-            };
-            fetch(1);
+            for (int e = 0; e < 2; ++e) {
+                const int i = 2 * k + e, u = i >> 2, v = i & 3;
+                const float a0 = ra[k % 3][0][e], a1 = ra[k % 3][1][e];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                if (k + 2 < 8) fetch(k + 2);
-                if (k == 7) {   // (behind the barrier: chunk c + 1 has landed)
-                    ra[0][0] = *reinterpret_cast<const sis_f32x2*>(Wl + (B ^ 1) * UF_CC * UF_WROW + woff);
-                    ra[0][1] = *reinterpret_cast<const sis_f32x2*>(Wl + (B ^ 1) * UF_CC * UF_WROW + woff + 32);
-                }
+                for (int pp = 0; pp < 2; ++pp)
 #pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const int i = 2 * k + e, u = i >> 2, v = i & 3;
-                    const float a0 = ra[k % 3][0][e], a1 = ra[k % 3][1][e];
-#pragma unroll
-                    for (int pp = 0; pp < 2; ++pp)
-#pragma unroll
-                        for (int qq = 0; qq < 2; ++qq) {
-                            if ((pp && u != 3) || (qq && v != 3)) continue;
-                            const int pi = u + pp, qi = v + qq;
-                            const int di = pi == 3 ? 1 : (pi == 4 ? 3 : pi), dj = qi == 3 ? 1 : (qi == 4 ? 3 : qi);
-                            acc[pi][qi][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, t[di][dj], acc[pi][qi][0], 0, 0, 0);
-                            acc[pi][qi][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, t[di][dj], acc[pi][qi][1], 0, 0, 0);
-                        }
-                    if (k >= 5) {   // side work of the chunk's tail, one piece behind each MFMA group
-                        if (k == 5 && e == 1) {
-                            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of chunk c + 1 (the compiler does not see them across the back edge)
-                            __syncthreads();
-                            if (c + 2 < n_chunks) stage((c + 2) * UF_CC, B);
-                            tr_read(c + 1, B ^ 1);
-                        }
-                        if (k == 6 && e == 0) { tr_col(0, tn); tr_col(1, tn); }
-                        if (k == 6 && e == 1) tr_col(2, tn);
-                        if (k == 7 && e == 0) tr_row(tn);
-                        __builtin_amdgcn_sched_barrier(0);
+                    for (int qq = 0; qq < 2; ++qq) {
+                        if ((pp && u != 3) || (qq && v != 3)) continue;
+                        const int pi = u + pp, qi = v + qq;
+                        const int di = pi == 3 ? 1 : (pi == 4 ? 3 : pi), dj = qi == 3 ? 1 : (qi == 4 ? 3 : qi);
+                        acc[pi][qi][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, t[di][dj], acc[pi][qi][0], 0, 0, 0);
+                        acc[pi][qi][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, t[di][dj], acc[pi][qi][1], 0, 0, 0);
                     }
-                }
-                if (k < 5) {
-                    if (k + 2 < 8) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    const int u = (2 * k) >> 2, vhi = ((2 * k) & 3) + 1;
-                    if (u == 3 && vhi == 3) __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);
-                    else if (u == 3) __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
-                    else if (vhi == 3) __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
-                    else __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+                if (k >= 5) {   // side work of the chunk's tail, one piece behind each MFMA group
+                    if (k == 5 && e == 1) {
+                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of chunk c + 1 (the compiler does not see them across the back edge)
+                        __syncthreads();
+                        if (c + 2 < n_chunks) stage((c + 2) * UF_CC, B);
+                        tr_read(c + 1, B ^ 1);
+                    }
+                    if (k == 6 && e == 0) { tr_col(0, tn); tr_col(1, tn); }
+                    if (k == 6 && e == 1) tr_col(2, tn);
+                    if (k == 7 && e == 0) tr_row(tn);
+                    __builtin_amdgcn_sched_barrier(0);
                 }
             }
-        };
-        for (int c = 0; c < n_chunks; c += 2) {
-            chunk(std::integral_constant<int, 0>(), c, tA, tB);
-            if (c + 1 < n_chunks) chunk(std::integral_constant<int, 1>(), c + 1, tB, tA);
+            if (k < 5) {
+                if (k + 2 < 8) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                const int u = (2 * k) >> 2, vhi = ((2 * k) & 3) + 1;
+                if (u == 3 && vhi == 3) __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);
+                else if (u == 3) __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+                else if (vhi == 3) __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
+                else __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+            }
         }
-    } else {
-    int buf = 0;
-    float t0[4][4] = {}, t1[4][4] = {};
-    // PIPE == 3: the SIMD partners (waves w and w + 4) run out of step inside a chunk -- waves 0-3 issue their DMA for the next
-    // chunk at its start, waves 4-7 between their two MFMA steps -- so that one partner's staging / transform phase falls under
-    // the other's MFMAs instead of both idling the matrix pipe behind the barrier (MI355X_MICROARCH.md, two waves per SIMD,
-    // item 9: split roles by wave number >= 4).
-    const bool late_dma = PIPE == 3 && wave >= 4;
-    for (int ci0 = 0; ci0 < p.Cin; ci0 += UF_CC, buf ^= 1) {
-        if (!(ABL & 2) && !late_dma && ci0 + UF_CC < p.Cin) stage(ci0 + UF_CC, buf ^ 1);
-        const float* Wb = Wl + buf * UF_CC * UF_WROW;
-        const float* Xb = Xl + buf * UF_CC * p.xs;
-        // Transform of one MFMA step (4 channels: this lane's is 4 ks + kq): raw 3 x 3 patch x style -> t[4][4]
-        auto transform = [&](int ks, float (&t)[4][4]) {
-            if constexpr (ABL & 4) {
-                if (ci0 != 0) return;   // (the first chunk's values stay in the registers)
-            }
-            const int cl = 4 * ks + kq;
-            const float sv = Sl[soff + ci0 + cl];
-            const float* xb = Xb + cl * p.xs + xoff;
-            float c[3][4];                                    // column transform of the three patch rows
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const float d0 = xb[r * RW] * sv, d1 = xb[r * RW + 1] * sv, d2 = xb[r * RW + 2] * sv;
-                c[r][0] = d0 - d1; c[r][1] = d1; c[r][2] = d2 - d1; c[r][3] = d2;
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {                     // row transform
-                t[0][j] = c[0][j] - c[1][j]; t[1][j] = c[1][j]; t[2][j] = c[2][j] - c[1][j]; t[3][j] = c[2][j];
-            }
-        };
-        // The 50 MFMAs of one step.  Planes (u, v) in order, one pair of A fragments each, used by every product (p, q) with
-        // pu[p] = u, pu[q] = v (plane row / column 3 serves the products 3 and 4).  PIPE >= 1: the fragments of plane i + 2 are
-        // requested before the MFMAs of plane i (a ring of three register pairs, pinned with sched_group_barrier: left to
-        // itself the compiler reads each pair right in front of its MFMAs and waits for it -- 32 exposed LDS latencies per chunk).
-        auto multiply = [&](int ks, const float (&t)[4][4]) {
-            // A fragments: one ds_read2_b64 per PAIR of planes (u, 2 h) / (u, 2 h + 1) delivers both planes for both channel tiles
-            const float* wb = Wb + (4 * ks + kq) * UF_WROW + (wm * 32 + l15) * 2;
-            sis_f32x2 ra[3][2];   // ring of three pairs x two channel tiles
-            auto fetch = [&](int k) {
-                if constexpr (ABL & 8) {
-                    ra[k % 3][0] = sis_f32x2{(float)(k + lane), (float)(k - lane)}; ra[k % 3][1] = sis_f32x2{(float)lane, (float)k};
-                } else {
-                    ra[k % 3][0] = *reinterpret_cast<const sis_f32x2*>(wb + k * 2 * UF_MBLK);
-                    ra[k % 3][1] = *reinterpret_cast<const sis_f32x2*>(wb + k * 2 * UF_MBLK + 32);
-                }
-            };
-            if constexpr (PIPE >= 1) { fetch(0); fetch(1); }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                if constexpr (PIPE >= 1) { if (k + 2 < 8) fetch(k + 2); }
-                else fetch(k);
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const int i = 2 * k + e, u = i >> 2, v = i & 3;
-                    const float a0 = ra[k % 3][0][e], a1 = ra[k % 3][1][e];
-#pragma unroll
-                    for (int pp = 0; pp < 2; ++pp)
-#pragma unroll
-                        for (int qq = 0; qq < 2; ++qq) {
-                            if ((pp && u != 3) || (qq && v != 3)) continue;
-                            const int pi = u + pp, qi = v + qq;               // product indices: u (or 4 for the second use of row 3)
-                            const int di = pi == 3 ? 1 : (pi == 4 ? 3 : pi), dj = qi == 3 ? 1 : (qi == 4 ? 3 : qi);
-                            acc[pi][qi][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, t[di][dj], acc[pi][qi][0], 0, 0, 0);
-                            acc[pi][qi][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, t[di][dj], acc[pi][qi][1], 0, 0, 0);
-                        }
-                }
-                if constexpr (PIPE >= 1) {
-                    if (k + 2 < 8) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);    // the read of pair k + 2 ...
-                    // ... then the MFMAs of pair k: planes (u, v) and (u, v + 1) with v even: 2 + 2, on plane row 3: 4 + 4,
-                    // and with plane column 3 in the pair twice as many for that plane
-                    const int u = (2 * k) >> 2, vhi = ((2 * k) & 3) + 1;
-                    if (u == 3 && vhi == 3) __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);
-                    else if (u == 3) __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
-                    else if (vhi == 3) __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
-                    else __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-                }
-            }
-        };
-        if constexpr (NW == 4) {     // one MFMA step per chunk
-            transform(0, t0);
-            multiply(0, t0);
-        } else if constexpr (PIPE == 2) {   // both steps' transforms first: the second one's loads and VALU go under the first step's MFMAs
-            transform(0, t0);
-            transform(1, t1);
-            multiply(0, t0);
-            multiply(1, t1);
-        } else {
-            transform(0, t0);
-            multiply(0, t0);
-            if (late_dma && ci0 + UF_CC < p.Cin) stage(ci0 + UF_CC, buf ^ 1);
-            transform(1, t1);
-            multiply(1, t1);
-        }
-        if constexpr (!(ABL & 1)) __syncthreads();   // next chunk's DMA retired (vmcnt 0) and everyone is done with this buffer
-    }
+    };
+    for (int c = 0; c < n_chunks; c += 2) {
+        chunk(std::integral_constant<int, 0>(), c, tA, tB);
+        if (c + 1 < n_chunks) chunk(std::integral_constant<int, 1>(), c + 1, tB, tA);
     }
 
     // ---- epilogue: output transform, demodulation, 16-byte stores of the block's 4 x 4 outputs per channel
-    // (PIPE == 4: the block's coordinates are worked out again from the lane number -- the loop has no register to carry them)
-    int eg = g;
-    if constexpr (PIPE == 4) { eg = g0 + wn * 16 + (int)(threadIdx.x & 15); asm volatile("" : "+v"(eg)); }
+    // (the block's coordinates are worked out again from the lane number -- the loop has no register to carry them)
+    int eg = g0 + wn * 16 + (int)(threadIdx.x & 15);
+    asm volatile("" : "+v"(eg));
     if (eg >= p.total_blocks) return;
-    int eb = b, ebh = bh, ebw = bw;
-    if constexpr (PIPE == 4) { eb = eg / p.bps; const int erem = eg % p.bps; ebh = erem / p.nbw; ebw = erem % p.nbw; }
+    const int eb = eg / p.bps, erem = eg % p.bps, ebh = erem / p.nbw, ebw = erem % p.nbw;
     const int OHW = p.OH * p.ORS;
     const float* db = p.dscale + (int64_t)eb * p.Cout;
     float* ob = p.out + (int64_t)eb * p.Cout * OHW + (int64_t)(4 * ebh) * p.ORS + 4 * ebw;
@@ -389,9 +284,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
 // (x0, x1, x2, s) of a 64-channel chunk are gathered once per workgroup into the LDS, one chunk ahead through registers, and every wave
 // reads its MFMA operand from there; weights by plain loads, a chunk ahead as well.  One barrier per chunk.  The 16-byte store at
 // column 2W also writes the pad columns 2W+1 .. 2W+3.
-#ifndef UF_EDGE_WAVES
-#define UF_EDGE_WAVES 8                               // (development builds: -DUF_EDGE_WAVES=4 = 64 output channels per edge workgroup everywhere)
-#endif
 constexpr int UE_KC = 64;                             // channels per chunk of the edge pass: 16 MFMA steps
 
 template <bool ROWK, int NWV>
@@ -558,9 +450,8 @@ __global__ __launch_bounds__(256) void upfir_prepack_kernel(float* __restrict__ 
     }
 }
 
-bool upfir_plan(UpFirParams& p, int batch, int cin, int cout, int h, int w, int row_stride, size_t* lds_bytes, int nw = 8) {
-    const int UF_CC = nw, UF_NBLK = 8 * nw;
-    static const int min_side = getenv("SIS_UPFIR_MIN_SIDE") ? atoi(getenv("SIS_UPFIR_MIN_SIDE")) : 16;   // (32: the 16 x 16 layer on the 4-phase kernel)
+bool upfir_plan(UpFirParams& p, int batch, int cin, int cout, int h, int w, int row_stride, size_t* lds_bytes) {
+    constexpr int min_side = 16;   // (smaller maps: the 4-phase kernel)
     if (batch <= 0 || h < min_side || w < min_side || (h & 1) || (w & 3) || cin % UF_CC || cout % UF_MBLK) return false;
     if ((row_stride & 3) || row_stride < 2 * w + 4) return false;
     if ((int64_t)batch * cin * h * w * 4 >= (1LL << 31) || (int64_t)cin * UF_PLANES * cout * 4 >= (1LL << 31)) return false;
@@ -589,17 +480,10 @@ bool upfir_plan(UpFirParams& p, int batch, int cin, int cout, int h, int w, int 
 
 }  // namespace
 
-// SIS_UPFIR_WAVES: 4 (default) = half tiles, two workgroups per CU; 8 = the one-workgroup-per-CU tile (A/B runs, same results)
-static int upfir_waves() {
-    static const int nw = getenv("SIS_UPFIR_WAVES") ? atoi(getenv("SIS_UPFIR_WAVES")) : 4;
-    return nw;
-}
-
 extern "C" int sis_modconv_up_fir_supported(int batch, int cin, int cout, int h, int w, int t_row_stride) {
     UpFirParams p;
     size_t lds;
-    const int nw = upfir_waves();
-    return (nw == 4 || nw == 8) && upfir_plan(p, batch, cin, cout, h, w, t_row_stride, &lds, nw) ? 1 : 0;
+    return upfir_plan(p, batch, cin, cout, h, w, t_row_stride, &lds) ? 1 : 0;
 }
 
 extern "C" int sis_modconv_up_fir_prepack(float* u, const float* w, int cout, int cin, void* stream) {
@@ -618,61 +502,23 @@ extern "C" int sis_modconv2d_up_fir(float* t, const float* x, const float* u, co
     SIS_REQUIRE((((uintptr_t)t | (uintptr_t)x | (uintptr_t)u) & 15) == 0, "sis_modconv2d_up_fir: pointers must be 16-byte aligned");
     UpFirParams p;
     size_t lds;
-    const int nw = upfir_waves();
-    SIS_REQUIRE(nw == 4 || nw == 8, "sis_modconv2d_up_fir: SIS_UPFIR_WAVES must be 4 or 8");
-    const int UF_NBLK = 8 * nw, UF_THREADS = 64 * nw;
-    SIS_REQUIRE(upfir_plan(p, batch, cin, cout, h, w, t_row_stride, &lds, nw),
+    SIS_REQUIRE(upfir_plan(p, batch, cin, cout, h, w, t_row_stride, &lds),
                 "sis_modconv2d_up_fir: %d x (%d -> %d) on %d x %d with row stride %d is not supported (sis_modconv_up_fir_supported)", batch,
                 cin, cout, h, w, t_row_stride);
     p.x = x; p.u = u; p.s = s; p.dscale = dscale; p.out = t;
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&modconv_upfir_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&modconv_upfir_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&modconv_upfir_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&modconv_upfir_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&modconv_upfir_kernel<1, 0, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&modconv_upfir_kernel<0, 0, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&modconv_upfir_kernel<4, 0, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&modconv_upfir_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
         if (e != hipSuccess) return sis_fail("sis_modconv2d_up_fir: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
         attr_set = true;
     }
     const int64_t grid = (int64_t)sis_cdiv(p.total_blocks, UF_NBLK) * (cout / UF_MBLK);
     SIS_REQUIRE(grid > 0 && grid < ((int64_t)1 << 31), "sis_modconv2d_up_fir: bad grid");
-    // chunk-loop form: 4 (4-wave workgroups only) = chunks pipelined across the barrier, 1 = fragments a pair ahead, 0 = plain; 2 / 3: 8-wave experiments
-    static const int pipe = getenv("SIS_UPFIR_PIPE") ? atoi(getenv("SIS_UPFIR_PIPE")) : 4;
-#ifdef SIS_ABLATIONS   // development builds only (tools/build_variant.sh WORK <tag> -DSIS_ABLATIONS): the shipped library has no wrong-result path
-    static const int abl = getenv("SIS_UPFIR_ABL") ? atoi(getenv("SIS_UPFIR_ABL")) : 0;      // timing ablations: WRONG results
-    if (abl) {
-        SIS_REQUIRE(nw == 8, "SIS_UPFIR_ABL: the ablations exist for SIS_UPFIR_WAVES=8 only");
-#define UF_ABL(A) hipLaunchKernelGGL((modconv_upfir_kernel<1, A>), dim3((unsigned)grid), dim3(UF_THREADS), lds, (hipStream_t)stream, p)
-        static bool abl_attr = false;
-        if (!abl_attr) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&modconv_upfir_kernel<1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&modconv_upfir_kernel<1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&modconv_upfir_kernel<1, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&modconv_upfir_kernel<1, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&modconv_upfir_kernel<1, 15>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            abl_attr = true;
-        }
-        if (abl == 1) UF_ABL(1); else if (abl == 2) UF_ABL(2); else if (abl == 4) UF_ABL(4); else if (abl == 8) UF_ABL(8); else UF_ABL(15);
-#undef UF_ABL
-        SIS_CHECK_LAUNCH("modconv_upfir_kernel<ablation>");
-        sis_kernel_name = "modconv_upfir_kernel";
-        return 0;
-    }
-#endif
-    if (nw == 4 && pipe == 4) hipLaunchKernelGGL((modconv_upfir_kernel<4, 0, 4>), dim3((unsigned)grid), dim3(UF_THREADS), lds, (hipStream_t)stream, p);
-    else if (nw == 4 && pipe == 0) hipLaunchKernelGGL((modconv_upfir_kernel<0, 0, 4>), dim3((unsigned)grid), dim3(UF_THREADS), lds, (hipStream_t)stream, p);
-    else if (nw == 4) hipLaunchKernelGGL((modconv_upfir_kernel<1, 0, 4>), dim3((unsigned)grid), dim3(UF_THREADS), lds, (hipStream_t)stream, p);
-    else if (pipe == 0) hipLaunchKernelGGL(modconv_upfir_kernel<0>, dim3((unsigned)grid), dim3(UF_THREADS), lds, (hipStream_t)stream, p);
-    else if (pipe == 2) hipLaunchKernelGGL(modconv_upfir_kernel<2>, dim3((unsigned)grid), dim3(UF_THREADS), lds, (hipStream_t)stream, p);
-    else if (pipe == 3) hipLaunchKernelGGL(modconv_upfir_kernel<3>, dim3((unsigned)grid), dim3(UF_THREADS), lds, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(modconv_upfir_kernel<1>, dim3((unsigned)grid), dim3(UF_THREADS), lds, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(modconv_upfir_kernel, dim3((unsigned)grid), dim3(UF_THREADS), lds, (hipStream_t)stream, p);
     SIS_CHECK_LAUNCH("modconv_upfir_kernel");
     // edge pass: T row 2H and T column 2W (and the pad columns), disjoint from the interior's outputs
     const int n_row_tiles = sis_cdiv(batch * (w / 2 + 1), 16), n_tiles = n_row_tiles + sis_cdiv(batch * (h / 2), 16);
-    if (cout % 128 == 0 && UF_EDGE_WAVES == 8) hipLaunchKernelGGL(modconv_upfir_edge_kernel<8>, dim3((unsigned)(n_tiles * (cout / 128))), dim3(512), 0, (hipStream_t)stream, p, n_row_tiles);
+    if (cout % 128 == 0) hipLaunchKernelGGL(modconv_upfir_edge_kernel<8>, dim3((unsigned)(n_tiles * (cout / 128))), dim3(512), 0, (hipStream_t)stream, p, n_row_tiles);
     else hipLaunchKernelGGL(modconv_upfir_edge_kernel<4>, dim3((unsigned)(n_tiles * (cout / 64))), dim3(256), 0, (hipStream_t)stream, p, n_row_tiles);
     SIS_CHECK_LAUNCH("modconv_upfir_edge_kernel");
     sis_kernel_name = "modconv_upfir_kernel";

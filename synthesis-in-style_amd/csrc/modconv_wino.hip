@@ -989,30 +989,16 @@ extern "C" int sis_conv3x3_prepack_multi(const void* table, int n_layers, int to
     return 0;
 }
 
-void modconv_splitk_finish_launch(const ConvParams& p, hipStream_t st);
-
 // Returns 0 / 1 like the other launchers, -1 when the shape is not eligible (odd sizes, unaligned, tiny Cin).
 int modconv_wino_launch(ConvParams& p, hipStream_t st, void* workspace, int64_t workspace_bytes, bool plan_only) {
     if (p.H % 2 || p.W % 4 || p.Cin % WCC != 0 || !p.cout_vec4 || (((uintptr_t)p.x | (uintptr_t)p.wpk | (uintptr_t)p.out) & 15))
         return -1;
     if (p.fuse && p.noise && (((uintptr_t)p.noise & 3) != 0)) return -1;
     const TileClass& tc = p.cls[0];
-    if (p.ncls != 1 || tc.th_log2 < 1 || tc.tw_log2 < 2 || tc.xt > WNTHR * 4) return -1;  // xt: padded-row tile, see mc_add_class ext
-    // split-K plan (same rule as the direct kernel, 64-channel blocks)
-    p.ksplit = 1; p.kchunk = p.Cin; p.slab = nullptr;
+    if (p.ncls != 1 || tc.th_log2 < 1 || tc.tw_log2 < 2 || tc.xt > WNTHR * 4) return -1;  // xt: padded-row tile, see mc_wino_tiles
+    // split-K: same rule as the direct kernel; this kernel's workgroups are lighter, so it starts below 256 and aims at 384
+    mc_plan_splitk(p, WMBLK, WCC, 256, 384, workspace, workspace_bytes);
     const int64_t blocks = (int64_t)p.npos_tiles * sis_cdiv(p.Cout, WMBLK);
-    if (blocks < 256 && p.Cin >= 4 * WCC && workspace) {
-        int want = (int)((384 + blocks - 1) / blocks);
-        const int max_split = p.Cin / (2 * WCC);
-        if (want > max_split) want = max_split;
-        const int64_t out_bytes = (int64_t)p.B * p.Cout * p.OH * p.ORS * 4;
-        if ((int64_t)want * out_bytes > workspace_bytes) want = (int)(workspace_bytes / out_bytes);
-        if (want >= 2) {
-            p.kchunk = sis_cdiv(sis_cdiv(p.Cin, want), WCC) * WCC;
-            p.ksplit = sis_cdiv(p.Cin, p.kchunk);
-            p.slab = (float*)workspace;
-        }
-    }
     const size_t lds = (size_t)(2 * WCC * 16 * WMBLK + 2 * WCC * tc.xt + (p.s ? p.nb_max * p.Cin : 0)) * sizeof(float);
     const size_t lds2 = lds + (size_t)(2 * 16 * WCC * WTILES + p.nb_max * WMBLK + WMBLK + WTILES * 4) * sizeof(float);
     if (lds > 160 * 1024) return -1;
@@ -1024,21 +1010,18 @@ int modconv_wino_launch(ConvParams& p, hipStream_t st, void* workspace, int64_t 
         if (e != hipSuccess) return sis_fail("modconv: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
         attr_set = true;
     }
-    static const bool pipelined = !(getenv("SIS_WINO_PIPE") && getenv("SIS_WINO_PIPE")[0] == '0');
-    if (pipelined && lds2 <= 160 * 1024 && tc.xt >= 256) {
+    // The pipelined kernel takes every tile that has a full 64 patches and whose second LDS image fits; the first kernel the rest.
+    if (lds2 <= 160 * 1024 && tc.xt >= 256) {
         sis_kernel_name = "modconv_wino2_kernel";
-        // pixel tiles per workgroup: as many as keep >= 1024 workgroups (4 per CU) in flight
-        static const int tpw_cap = getenv("SIS_WINO_TPW") ? atoi(getenv("SIS_WINO_TPW")) : 16;
+        // pixel tiles per workgroup: as many (up to 16) as keep >= 1024 workgroups (4 per CU) in flight
         int tpw = 1;
-        static const int min_wg = getenv("SIS_WINO_MINWG") ? atoi(getenv("SIS_WINO_MINWG")) : 1024;
         // (the tile-to-tile pipeline stages the next tile from the last two chunks and keeps the buffer parity: an even number of
         // chunks per tile, otherwise one tile per workgroup)
-        while (p.kchunk % (2 * WCC) == 0 && tpw * 2 <= tpw_cap && p.npos_tiles % (tpw * 2) == 0 && blocks / (tpw * 2) >= min_wg) tpw *= 2;
-        // all co-blocks of a pixel tile on one XCD when the whole transformed weight tensor stays L2-resident there
-        static const double swz_mb = getenv("SIS_WINO_XCD_MB") ? atof(getenv("SIS_WINO_XCD_MB")) : 5.0;
+        while (p.kchunk % (2 * WCC) == 0 && tpw * 2 <= 16 && p.npos_tiles % (tpw * 2) == 0 && blocks / (tpw * 2) >= 1024) tpw *= 2;
+        // all co-blocks of a pixel tile on one XCD when the whole transformed weight tensor (<= 5 MB) stays L2-resident there
         const int64_t grid = blocks / tpw;
         const int n_co_h = (p.Cout + WMBLK - 1) / WMBLK;
-        const int xcd_group = (double)p.Cin * p.Cout * 16 * sizeof(float) <= swz_mb * 1048576.0 && n_co_h > 1 && grid % (8 * n_co_h) == 0;
+        const int xcd_group = (double)p.Cin * p.Cout * 16 * sizeof(float) <= 5.0 * 1048576.0 && n_co_h > 1 && grid % (8 * n_co_h) == 0;
         typedef void (*kern_t)(const ConvParams, const int, const int, const int);
         static const kern_t table[4][2] = {{modconv_wino2_kernel<1, false>, modconv_wino2_kernel<1, true>},
                                            {modconv_wino2_kernel<2, false>, modconv_wino2_kernel<2, true>},
@@ -1059,8 +1042,7 @@ int modconv_wino_launch(ConvParams& p, hipStream_t st, void* workspace, int64_t 
         hipLaunchKernelGGL(modconv_wino_kernel, dim3((unsigned)blocks, p.ksplit), dim3(WNTHR), lds, st, p, tc.xt);
     }
     SIS_CHECK_LAUNCH("modconv_wino_kernel");
-    if (p.ksplit > 1) modconv_splitk_finish_launch(p, st);
-    return 0;
+    return p.ksplit > 1 ? modconv_splitk_finish_launch(p, st) : 0;
 }
 
 // Winograd F(2x4,3x3) form of the same layers: kernel, prepack and C entries

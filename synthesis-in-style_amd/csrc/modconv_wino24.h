@@ -395,7 +395,9 @@ static int wino24_plan(ConvParams& p, int cin, int cout, int h, int w) {
     if (cin <= 0 || cout <= 0 || h <= 0 || w <= 0) return -1;
     if (cin % 8 || cout % WMBLK || h % 2 || w % 4) return -1;
     if ((int64_t)cin * h * w * 4 >= ((int64_t)1 << 31) || (int64_t)cin * cout * 96 >= ((int64_t)1 << 31)) return -1;  // 32-bit DMA offsets
-    p.slab = nullptr; p.ksplit = 1; p.kchunk = cin; p.npos_tiles = 0; p.ncls = 0; p.nb_max = 0;
+    p.Cin = cin;
+    mc_reset_splitk(p);
+    mc_reset_tiles(p);
     mc_add_class(p, 512, 2, 1, 0, h, 0, w, 64, 1);
     const TileClass& tc = p.cls[0];
     if (tc.nb != 1 || tc.th_log2 + tc.tw_log2 != 9 || tc.tw_log2 < 5) return -1;
@@ -417,16 +419,13 @@ extern "C" int sis_modconv2d_wino24(float* out, const float* x, const float* u24
     SIS_REQUIRE(out && x && u24 && s && dscale, "sis_modconv2d_wino24: null pointer");
     SIS_REQUIRE(batch > 0, "sis_modconv2d_wino24: non-positive size");
     if (noise) SIS_REQUIRE(noise_weight, "sis_modconv2d_wino24: noise given without noise_weight");
-    ConvParams p;
+    ConvParams p = mc_params(out, x, u24, s, dscale, noise, noise_batch_stride, noise_weight, bias, batch, cin, cout, h, w, h, w, w,
+                             fuse_act != 0);
     const int lds = wino24_plan(p, cin, cout, h, w);
     SIS_REQUIRE(lds > 0, "sis_modconv2d_wino24: shape %dx%d, %d -> %d not eligible (sis_modconv_wino24_eligible)", h, w, cin, cout);
     SIS_REQUIRE((int64_t)batch * (cin > cout ? cin : cout) * h * w < ((int64_t)1 << 31), "sis_modconv2d_wino24: tensor too large");
     SIS_REQUIRE(((((uintptr_t)x | (uintptr_t)u24 | (uintptr_t)out) & 15) == 0) && (!noise || ((uintptr_t)noise & 3) == 0),
                 "sis_modconv2d_wino24: pointers must be 16-byte aligned");
-    p.x = x; p.wpk = u24; p.s = s; p.dscale = dscale; p.noise = noise; p.noise_w = noise_weight; p.bias = bias;
-    p.out = out; p.noise_bstride = noise_batch_stride;
-    p.B = batch; p.Cin = cin; p.Cout = cout; p.H = h; p.W = w; p.OH = h; p.OW = w; p.ORS = w; p.fuse = fuse_act != 0;
-    p.cout_vec4 = 1;
     const TileClass& tc = p.cls[0];
     const int64_t tiles = (int64_t)batch * tc.nth * tc.ntw;  // one-sample tiles
     p.npos_tiles = (int)tiles;

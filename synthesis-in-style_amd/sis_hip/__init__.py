@@ -968,7 +968,6 @@ def modconv2d(x, wpk, s, dscale, ksize, noise=None, noise_weight=None, bias=None
                    "sis_modconv2d_wino24")
         return out
     ws = _workspace(x.device)
-    wino = wino_u is not None and ksize == 3 and h % 2 == 0 and w % 2 == 0 and cin % 8 == 0 and cout % 4 == 0
     with torch.cuda.device(x.device):
         _check(_launch(None,
                        2.0 * batch * cout * cin * ksize * ksize * h * w,

@@ -97,7 +97,7 @@ def _modconv_operands(t, gen, b, cin, cout, sdim):
     return style, weight, mod_w, mod_b, wpk, s, ds
 
 
-@case("modconv2d", ["modconv_mfma.hip", "modconv_mfma2.hip", "modconv_wino.hip", "gen_small_ops.hip"],
+@case("modconv2d", ["modconv_entries.hip", "modconv_mfma.hip", "modconv_mfma2.hip", "modconv_wino.hip", "gen_small_ops.hip"],
       *[(b, cin, cout, h, w, fuse, wino) for (b, cin, cout, h, w) in [(3, 24, 136, 16, 16), (5, 64, 128, 4, 4)]
         for fuse in (False, True) for wino in (False, True)], (2, 6, 6, 5, 6, False, False), (2, 6, 6, 5, 6, True, False))
 def _modconv2d(t, b, cin, cout, h, w, fuse, wino):
@@ -140,7 +140,7 @@ def _up_reference(x, style, weight, mod_w, mod_b, noise, nw, bias):
     return taps, t_ref, ref, ref_act
 
 
-@case("modconv2d_up", ["modconv_mfma.hip", "modconv_mfma2.hip", "upfirdn2d.hip"], (3, 24, 72, 8, 8, False), (3, 24, 72, 8, 8, True),
+@case("modconv2d_up", ["modconv_entries.hip", "modconv_mfma.hip", "modconv_mfma2.hip", "upfirdn2d.hip"], (3, 24, 72, 8, 8, False), (3, 24, 72, 8, 8, True),
       (2, 6, 12, 5, 6, False), (2, 6, 12, 5, 6, True))
 def _modconv2d_up(t, b, cin, cout, h, w, padded):
     """test_modconv_up_vs_oracle: the 4-phase transposed convolution, then blur_noise_act reading the buffer it wrote (with
@@ -246,7 +246,7 @@ def _fused_bias_act(t, shape):
 # =================================================================================================== plain fp32 convolutions
 # references and bounds: tests/test_hip_conv_gpu.py, tests/test_conv1x1_f32_gpu.py
 
-@case("conv3x3", ["modconv_mfma.hip", "modconv_wino.hip"], (5, 8, 8, 2, 4, 1), (9, 40, 72, 4, 8, 1), (1, 16, 64, 2, 128, 1), (1, 8, 16, 16, 24, 2))
+@case("conv3x3", ["modconv_entries.hip", "modconv_wino.hip"], (5, 8, 8, 2, 4, 1), (9, 40, 72, 4, 8, 1), (1, 16, 64, 2, 128, 1), (1, 8, 16, 16, 24, 2))
 def _conv3x3(t, batch, cin, cout, h, w, dil):
     """test_forward_and_data_gradient (2e-5 of the range), the kernel called directly: forward image and adjoint image."""
     import sis_hip
