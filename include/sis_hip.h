@@ -147,6 +147,18 @@ int sis_modconv2d_wino24(float* out, const float* x, const float* u24, const flo
                          const float* noise, int64_t noise_batch_stride, const float* noise_weight, const float* bias,
                          int batch, int cin, int cout, int h, int w, int fuse_act, int tiles_per_wg, void* stream);
 
+/* sis_modconv2d_wino24 that also leaves the following ToRGB's channel sum, in blocks of 64 output channels:
+ * rgb_part[cb][b][c][y][x] = sum_{co in [64 cb, 64 cb + 64)} rgb_scale * rgb_w[c][co] * rgb_s[b][co] * out[b][co][y][x], c = 0..2,
+ * a [cout / 64][B][3][H][W] buffer (16-byte aligned) that is written in full.  out is what sis_modconv2d_wino24 writes, bit for
+ * bit; a sample's sums do not depend on the batch or on tiles_per_wg.  sis_rgb_finish completes the ToRGB layer:
+ * out[b][c] = sum_cb part[cb][b][c] (cb ascending) + bias[c] + upsample(skip)[b][c], skip / taps / pads as in sis_to_rgb. */
+int sis_modconv2d_wino24_rgb(float* out, float* rgb_part, const float* x, const float* u24, const float* s, const float* dscale,
+                             const float* noise, int64_t noise_batch_stride, const float* noise_weight, const float* bias,
+                             const float* rgb_w, const float* rgb_s, float rgb_scale, int batch, int cin, int cout, int h, int w,
+                             int fuse_act, int tiles_per_wg, void* stream);
+int sis_rgb_finish(float* out, const float* part, const float* bias, const float* skip, const float* taps, int batch, int blocks,
+                   int cout, int h, int width, int kh, int kw, int pad0, int pad1, void* stream);
+
 /* Modulated transposed convolution, stride 2, no padding, ks = 3: model.py:251-261 up to (not
  * including) the Blur: t[b,co,p,q] = dscale[b,co] * sum_{ci, 2h+kh=p, 2w+kw=q} wpk[ci][kh*3+kw][co]
  * * s[b,ci] * x[b,ci,h,w];  t is [B, Cout, 2H+1, t_row_stride] with the first 2W+1 floats of every row

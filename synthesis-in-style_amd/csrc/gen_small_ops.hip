@@ -331,6 +331,70 @@ __device__ __forceinline__ float skip_up2(const float* __restrict__ sp, const fl
     return v;
 }
 
+// Upsampled skip image, taps <= 4 x 4 (two per dimension after the polyphase split): per output channel the 4 * VEC skip
+// values and tap weights are requested together with clamped indices, then masked and added in skip_up2's order (the
+// per-tap `continue`s of skip_up2 made every tap a dependent round trip: 24 per lane, as long as the channel loop itself).
+template <int VEC>
+struct SkipTaps {
+    int s_off[VEC][4], t_off[VEC][4];
+    unsigned ok;
+};
+
+template <int VEC>
+__device__ __forceinline__ SkipTaps<VEC> skip_taps(const RgbParams& p, int pix) {
+    SkipTaps<VEC> k;
+    k.ok = 0;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+        const int y = (pix + v) / p.w, xx = (pix + v) % p.w;
+        const int mid_x = xx + 1 - p.pad0, mid_y = y + 1 - p.pad0;
+        const int ix0 = (mid_x >= 0) ? mid_x / 2 : -((1 - mid_x) / 2);
+        const int iy0 = (mid_y >= 0) ? mid_y / 2 : -((1 - mid_y) / 2);
+        const int kx0 = (ix0 + 1) * 2 - mid_x - 1, ky0 = (iy0 + 1) * 2 - mid_y - 1;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int iy = iy0 + (t >> 1), ix = ix0 + (t & 1), fy = ky0 + 2 * (t >> 1), fx = kx0 + 2 * (t & 1);
+            const bool ok = iy >= 0 && iy < p.sh && ix >= 0 && ix < p.sw && fy < p.kh && fx < p.kw;
+            k.ok |= (ok ? 1u : 0u) << (v * 4 + t);
+            k.s_off[v][t] = min(max(iy, 0), p.sh - 1) * p.sw + min(max(ix, 0), p.sw - 1);
+            k.t_off[v][t] = (p.kh - 1 - min(fy, p.kh - 1)) * p.kw + (p.kw - 1 - min(fx, p.kw - 1));
+        }
+    }
+    return k;
+}
+
+// The end of a ToRGB output: a[v] (the channel sum of VEC consecutive pixels from pix on, colour c of sample b) + bias + upsampled
+// skip, stored to o.  skip_fast: k holds skip_taps(p, pix).  Shared by to_rgb_kernel and rgb_finish_kernel.
+template <int VEC>
+__device__ __forceinline__ void rgb_bias_skip_store(float* __restrict__ o, const float (&a_in)[VEC], float bb, const float* __restrict__ sp,
+                                                    const float* __restrict__ taps, const RgbParams& p, bool skip_fast,
+                                                    const SkipTaps<VEC>& k, int pix) {
+    float r[VEC];
+    float sv[VEC][4], tv[VEC][4];
+    if (skip_fast) {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) { sv[v][t] = sp[k.s_off[v][t]]; tv[v][t] = taps[k.t_off[v][t]]; }
+    }
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+        float a = a_in[v] + bb;
+        if (skip_fast) {
+            float u = 0.f;
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                if ((k.ok >> (v * 4 + t)) & 1u) u += sv[v][t] * tv[v][t];
+            a += u;
+        } else if (sp) {
+            a += skip_up2(sp, taps, p, (pix + v) / p.w, (pix + v) % p.w);
+        }
+        r[v] = a;
+    }
+    if (VEC == 4) *reinterpret_cast<float4*>(o) = make_float4(r[0], r[1], r[2], r[3]);
+    else o[0] = r[0];
+}
+
 // One workgroup = one sample x one group of 64*VEC pixels; its 4 waves each take every 4th input channel
 // (4x the loads in flight: the low-resolution layers have only B x 1 pixel groups and were latency-bound with
 // one wave walking all 512 channels), partial sums meet in LDS, wave 0 adds bias + upsampled skip and stores.
@@ -399,64 +463,59 @@ __global__ __launch_bounds__(256) void to_rgb_kernel(float* __restrict__ out, co
     }
     __syncthreads();
     if (wave != 0 || !live) return;
-    // Upsampled skip image, taps <= 4 x 4 (two per dimension after the polyphase split): per output channel the 4 * VEC skip
-    // values and tap weights are requested together with clamped indices, then masked and added in skip_up2's order (the
-    // per-tap `continue`s of skip_up2 made every tap a dependent round trip: 24 per lane, as long as the channel loop itself).
     const bool skip_fast = skip && p.kh <= 4 && p.kw <= 4;
-    int s_off[VEC][4], t_off[VEC][4];
-    unsigned s_ok = 0;
-    if (skip_fast) {
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) {
-            const int y = (pix + v) / p.w, xx = (pix + v) % p.w;
-            const int mid_x = xx + 1 - p.pad0, mid_y = y + 1 - p.pad0;
-            const int ix0 = (mid_x >= 0) ? mid_x / 2 : -((1 - mid_x) / 2);
-            const int iy0 = (mid_y >= 0) ? mid_y / 2 : -((1 - mid_y) / 2);
-            const int kx0 = (ix0 + 1) * 2 - mid_x - 1, ky0 = (iy0 + 1) * 2 - mid_y - 1;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int iy = iy0 + (t >> 1), ix = ix0 + (t & 1), fy = ky0 + 2 * (t >> 1), fx = kx0 + 2 * (t & 1);
-                const bool ok = iy >= 0 && iy < p.sh && ix >= 0 && ix < p.sw && fy < p.kh && fx < p.kw;
-                s_ok |= (ok ? 1u : 0u) << (v * 4 + t);
-                s_off[v][t] = min(max(iy, 0), p.sh - 1) * p.sw + min(max(ix, 0), p.sw - 1);
-                t_off[v][t] = (p.kh - 1 - min(fy, p.kh - 1)) * p.kw + (p.kw - 1 - min(fx, p.kw - 1));
-            }
-        }
-    }
+    SkipTaps<VEC> k;
+    if (skip_fast) k = skip_taps<VEC>(p, pix);
 #pragma unroll
     for (int c = 0; c < RGB_MAXC; ++c) {
         if (c >= p.cout) continue;
-        const float bb = bias ? bias[c] : 0.f;
-        float* o = out + ((int64_t)b * p.cout + c) * hw + pix;
-        float r[VEC];
-        float sv[VEC][4], tv[VEC][4];
-        if (skip_fast) {
-            const float* sp = skip + ((int64_t)b * p.cout + c) * p.sh * p.sw;
-#pragma unroll
-            for (int v = 0; v < VEC; ++v)
-#pragma unroll
-                for (int t = 0; t < 4; ++t) { sv[v][t] = sp[s_off[v][t]]; tv[v][t] = taps[t_off[v][t]]; }
-        }
+        float a[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
-            float a = acc[c][v];
+            a[v] = acc[c][v];
 #pragma unroll
-            for (int ww = 0; ww < 3; ++ww) a += part[((ww * RGB_MAXC + c) * VEC + v) * 64 + lane];
-            a += bb;
-            if (skip_fast) {
-                float u = 0.f;
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-                    if ((s_ok >> (v * 4 + t)) & 1u) u += sv[v][t] * tv[v][t];
-                a += u;
-            } else if (skip) {
-                const int y = (pix + v) / p.w, xx = (pix + v) % p.w;
-                a += skip_up2(skip + ((int64_t)b * p.cout + c) * p.sh * p.sw, taps, p, y, xx);
-            }
-            r[v] = a;
+            for (int ww = 0; ww < 3; ++ww) a[v] += part[((ww * RGB_MAXC + c) * VEC + v) * 64 + lane];
         }
-        if (VEC == 4) *reinterpret_cast<float4*>(o) = make_float4(r[0], r[1], r[2], r[3]);
-        else o[0] = r[0];
+        rgb_bias_skip_store<VEC>(out + ((int64_t)b * p.cout + c) * hw + pix, a, bias ? bias[c] : 0.f,
+                                 skip ? skip + ((int64_t)b * p.cout + c) * p.sh * p.sw : nullptr, taps, p, skip_fast, k, pix);
+    }
+}
+
+// The ToRGB of a layer whose convolution left the channel sum in blocks (modconv_wino24_kernel<true>): out[b][c] = sum over the
+// p.cin blocks cb (ascending) of part[cb][b][c] + bias[c] + upsampled skip.  4 pixels per lane (h * w % 4 == 0), 3 colours each.
+__global__ __launch_bounds__(256) void rgb_finish_kernel(float* __restrict__ out, const float* __restrict__ part,
+                                                         const float* __restrict__ bias, const float* __restrict__ skip,
+                                                         const float* __restrict__ taps, RgbParams p) {
+    const int hw = p.h * p.w;
+    const int groups = (hw + 1023) / 1024;
+    const int b = blockIdx.x / groups;
+    const int pix = ((blockIdx.x % groups) * 256 + threadIdx.x) * 4;
+    if (pix >= hw) return;
+    const int64_t blk = (int64_t)p.batch * p.cout * hw;
+    const float* pp = part + (int64_t)b * p.cout * hw + pix;
+    float a[RGB_MAXC][4];
+#pragma unroll
+    for (int c = 0; c < RGB_MAXC; ++c)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) a[c][v] = 0.f;
+#pragma unroll 2
+    for (int cb = 0; cb < p.cin; ++cb) {  // the colours of a block are requested together
+        float4 u[RGB_MAXC];
+#pragma unroll
+        for (int c = 0; c < RGB_MAXC; ++c)
+            if (c < p.cout) u[c] = *reinterpret_cast<const float4*>(pp + cb * blk + (int64_t)c * hw);
+#pragma unroll
+        for (int c = 0; c < RGB_MAXC; ++c)
+            if (c < p.cout) { a[c][0] += u[c].x; a[c][1] += u[c].y; a[c][2] += u[c].z; a[c][3] += u[c].w; }
+    }
+    const bool skip_fast = skip && p.kh <= 4 && p.kw <= 4;
+    SkipTaps<4> k;
+    if (skip_fast) k = skip_taps<4>(p, pix);
+#pragma unroll
+    for (int c = 0; c < RGB_MAXC; ++c) {
+        if (c >= p.cout) continue;
+        rgb_bias_skip_store<4>(out + ((int64_t)b * p.cout + c) * hw + pix, a[c], bias ? bias[c] : 0.f,
+                               skip ? skip + ((int64_t)b * p.cout + c) * p.sh * p.sw : nullptr, taps, p, skip_fast, k, pix);
     }
 }
 
@@ -583,5 +642,30 @@ extern "C" int sis_to_rgb(float* out, const float* x, const float* w, const floa
                            taps, p);
     }
     SIS_CHECK_LAUNCH("sis_to_rgb");
+    return 0;
+}
+
+extern "C" int sis_rgb_finish(float* out, const float* part, const float* bias, const float* skip, const float* taps, int batch,
+                              int blocks, int cout, int h, int wd, int kh, int kw, int pad0, int pad1, void* stream) {
+    if (batch <= 0 || h <= 0 || wd <= 0) return 0;
+    SIS_REQUIRE(out && part, "sis_rgb_finish: null pointer");
+    SIS_REQUIRE(cout >= 1 && cout <= RGB_MAXC && blocks >= 1, "sis_rgb_finish: cout %d outside 1..%d or no blocks", cout, RGB_MAXC);
+    SIS_REQUIRE((int64_t)h * wd % 4 == 0 && (((uintptr_t)part | (uintptr_t)out) & 15) == 0,
+                "sis_rgb_finish: needs h * w %% 4 == 0 and 16-byte aligned pointers");
+    SIS_REQUIRE((int64_t)batch * cout * h * wd < ((int64_t)1 << 31), "sis_rgb_finish: tensor too large");
+    RgbParams p;
+    p.batch = batch; p.cin = blocks; p.cout = cout; p.h = h; p.w = wd; p.kh = kh; p.kw = kw; p.pad0 = pad0;
+    p.sh = 0; p.sw = 0; p.scale = 1.f;
+    if (skip) {
+        SIS_REQUIRE(taps && kh >= 1 && kw >= 1, "sis_rgb_finish: skip given without taps");
+        SIS_REQUIRE(h % 2 == 0 && wd % 2 == 0, "sis_rgb_finish: skip path needs even output size");
+        p.sh = h / 2; p.sw = wd / 2;
+        SIS_REQUIRE(sis_upfirdn2d_out_size(p.sh, 2, 1, pad0, pad1, kh) == h &&
+                        sis_upfirdn2d_out_size(p.sw, 2, 1, pad0, pad1, kw) == wd,
+                    "sis_rgb_finish: upsampled skip would not match the %dx%d output", h, wd);
+    }
+    hipLaunchKernelGGL(rgb_finish_kernel, dim3(batch * sis_cdiv(h * wd, 1024)), dim3(256), 0, (hipStream_t)stream, out, part, bias,
+                       skip, taps, p);
+    SIS_CHECK_LAUNCH("sis_rgb_finish");
     return 0;
 }

@@ -18,6 +18,10 @@
 //
 // Workgroup = 8 waves = (co half) x (tile half) x q = 64 co x 64 tiles (512 pixels: 8 x 64 or 16 x 32), 4-channel
 // chunks: U and V 24 KB each per buffer, double-buffered, plus the raw input tile 2 x 11.25 KB: 121 KB of LDS.
+//
+// modconv_wino24_kernel<true> also forms the channel sum of the ToRGB layer that follows, per 64-channel block, from the values
+// it stores (3 FMAs per finished value; the eight lanes that hold a pixel's 64 channels meet through the exchange area in one
+// fixed order): that layer then reads 3 x Cout / 64 planes (rgb_finish_kernel, gen_small_ops.hip) instead of the activation.
 
 namespace {
 
@@ -84,7 +88,20 @@ __device__ unsigned int sis_wino24_trace_tile[TR_NWG][8][16][8];
 #define W24_TRACE(slot) do {} while (0)
 #endif
 
-__global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvParams p, const int tiles_per_wg, const int xcd_group) {
+// ToRGB operands of the instantiation that also emits RGB partial sums (RGB = true; the other one takes an empty struct).
+struct W24Rgb {
+    const float* w;   // [3][Cout]  ToRGB weight
+    const float* s;   // [B][Cout]  ToRGB style
+    float* part;      // [Cout / 64][B][3][H][W]  partial sums of the workgroup's channel block
+    float scale;
+};
+struct W24NoRgb {};
+
+// RGB: a workgroup additionally writes part[o0 / 64][b][c][y][x] = sum over its 64 channels of wr[b][c][co] * out[b][co][y][x],
+// wr = scale * w[c][co] * s[b][co] (ToRGB's modulated weight, no demodulation), from the values it stores to out.
+template <bool RGB>
+__global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvParams p, const int tiles_per_wg, const int xcd_group,
+                                                                  const std::conditional_t<RGB, W24Rgb, W24NoRgb> rgb) {
     constexpr int CC = W24_CC, UF = W24_UF, VF = W24_VF, XT = W24_XT;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* Ul = lds;                  // [2][UF]
@@ -94,6 +111,7 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvPara
     float* Dl = Sl + p.Cin;           // [WMBLK]   scale * demodulation
     float* Bl = Dl + WMBLK;           // [WMBLK]   bias
     float* Nl = Bl + WMBLK;           // [WTILES][2][4] noise_weight * noise of the tile's pixels
+    [[maybe_unused]] float* Wl = Nl + WTILES * 8;  // [3][WMBLK] RGB: ToRGB weight of the tile's sample and channel block
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, half = lane >> 5;
@@ -224,6 +242,12 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvPara
                 Dl[tp] = p.dscale[(int64_t)T.b * p.Cout + o0 + tp];
                 Bl[tp] = (p.fuse && p.bias) ? p.bias[o0 + tp] : 0.f;
             }
+            if constexpr (RGB) {
+                if (tp < 3 * WMBLK) {
+                    const int co = o0 + (tp & (WMBLK - 1));
+                    Wl[tp] = rgb.scale * rgb.w[(tp / WMBLK) * p.Cout + co] * rgb.s[(int64_t)T.b * p.Cout + co];
+                }
+            }
             {
                 const int tt_ = tp >> 3, e = tp & 7;
                 const int yy = T.h0 + 2 * (tt_ >> txs) + (e >> 2), xx = T.w0 + 4 * (tt_ & ((1 << txs) - 1)) + (e & 3);
@@ -339,10 +363,20 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvPara
                 float* obase = p.out + ((int64_t)T.b * p.Cout + o0 + cl0) * HW + oh * p.W + ow;
                 const float* xin = xch + (1 - Q) * 48 * 64 + lane;
                 const sis_f32x4 nz0 = lds_ld4(Nl + t * 8), nz1 = lds_ld4(Nl + t * 8 + 4);
+                [[maybe_unused]] float pr[3][2][4];  // RGB: this lane's 8 channels (ascending) of its 2 x 4 pixels
+                if constexpr (RGB) {
+#pragma unroll
+                    for (int e = 0; e < 24; ++e) pr[e >> 3][(e >> 2) & 1][e & 3] = 0.f;
+                }
 #pragma unroll
                 for (int jr = 0; jr < 8; ++jr) {
                     const int ro = (jr & 3) + 8 * (jr >> 2);
                     const float dd = Dl[cl0 + ro], bb = Bl[cl0 + ro];
+                    [[maybe_unused]] float wc[3];
+                    if constexpr (RGB) {
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) wc[c] = Wl[c * WMBLK + cl0 + ro];
+                    }
                     float theirs[2][3];
 #pragma unroll
                     for (int e = 0; e < 6; ++e) theirs[e / 3][e % 3] = xin[(jr * 6 + e) * 64];
@@ -363,6 +397,39 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvPara
                             o[x] = fmaxf(val, val * slope) * gain;  // = (val > 0 ? val : 0.2 val) * sqrt(2) when the tail is on
                         }
                         *reinterpret_cast<sis_f32x4*>(obase + (int64_t)ro * HW + r * p.W) = sis_f32x4{o[0], o[1], o[2], o[3]};
+                        if constexpr (RGB) {
+#pragma unroll
+                            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                                for (int x = 0; x < 4; ++x) pr[c][r][x] = fmaf(wc[c], o[x], pr[c][r][x]);
+                        }
+                    }
+                }
+                if constexpr (RGB) {
+                    // The partner's half of the exchange area was read by this wave alone and is behind its last read (a wave's
+                    // LDS accesses keep their order): the lane's 24 sums go there as [colour][row][lane][4 pixels].
+                    float* pw = xch + (1 - Q) * 48 * 64 + lane * 4;
+#pragma unroll
+                    for (int e = 0; e < 6; ++e)
+                        *reinterpret_cast<sis_f32x4*>(pw + e * 256) = sis_f32x4{pr[e >> 1][e & 1][0], pr[e >> 1][e & 1][1], pr[e >> 1][e & 1][2], pr[e >> 1][e & 1][3]};
+                }
+            }
+            if constexpr (RGB) {
+                // A pixel's 64 channels sit in eight lanes: (co half wm) x (column half Q) x (lane half), 8 channels each.  Wave
+                // 2 c + r adds them for colour c and pixel row r of the 64 tiles, in the fixed order wm, Q, lane half (each
+                // ascending), and stores one float4 per tile.  The next tile's first barrier stands between these reads and the
+                // DMA that reuses the area.
+                __syncthreads();
+                if (wave < 6) {
+                    const int oh2 = T.h0 + 2 * (lane >> txs), ow2 = T.w0 + 4 * (lane & ((1 << txs) - 1));
+                    if (oh2 < p.H && ow2 < p.W) {
+                        const float* ps = lds + (lane >> 5) * (2 * 48 * 64) + (wave * 64 + (lane & 31)) * 4;
+                        sis_f32x4 a = lds_ld4(ps + 48 * 64);  // wm = 0, Q = 0 (in its partner's half), lanes 0..31
+#pragma unroll
+                        for (int src = 1; src < 8; ++src)
+                            a += lds_ld4(ps + (src >> 2) * (4 * 48 * 64) + (1 - ((src >> 1) & 1)) * (48 * 64) + (src & 1) * 128);
+                        float* pd = rgb.part + ((((int64_t)(o0 / WMBLK) * p.B + T.b) * 3 + (wave >> 1)) * p.H + oh2 + (wave & 1)) * p.W + ow2;
+                        *reinterpret_cast<sis_f32x4*>(pd) = a;
                     }
                 }
             }
@@ -391,7 +458,7 @@ extern "C" int sis_modconv_prepack_wino24(float* u, const float* w, int cout, in
 
 // The F(2x4,3x3) kernel takes a layer by (Cin, Cout, H, W) alone: 64-channel output blocks, 8-channel input steps, and a
 // map that one-sample tiles of 512 pixels (8 x 64 or 16 x 32) cover -- W > 16, H * W >= 512 after rounding up to powers of two.
-static int wino24_plan(ConvParams& p, int cin, int cout, int h, int w) {
+static int wino24_plan(ConvParams& p, int cin, int cout, int h, int w, bool rgb = false) {
     if (cin <= 0 || cout <= 0 || h <= 0 || w <= 0) return -1;
     if (cin % 8 || cout % WMBLK || h % 2 || w % 4) return -1;
     if ((int64_t)cin * h * w * 4 >= ((int64_t)1 << 31) || (int64_t)cin * cout * 96 >= ((int64_t)1 << 31)) return -1;  // 32-bit DMA offsets
@@ -402,7 +469,7 @@ static int wino24_plan(ConvParams& p, int cin, int cout, int h, int w) {
     const TileClass& tc = p.cls[0];
     if (tc.nb != 1 || tc.th_log2 + tc.tw_log2 != 9 || tc.tw_log2 < 5) return -1;
     if (((1 << tc.th_log2) + 2) * ((1 << tc.tw_log2) + 8) != W24_XT) return -1;
-    const size_t lds = (size_t)(2 * W24_UF + 2 * W24_VF + 2 * W24_CC * W24_XT + cin + 2 * WMBLK + WTILES * 8) * sizeof(float);
+    const size_t lds = (size_t)(2 * W24_UF + 2 * W24_VF + 2 * W24_CC * W24_XT + cin + (rgb ? 5 : 2) * WMBLK + WTILES * 8) * sizeof(float);
     if (lds > 160 * 1024) return -1;
     return (int)lds;
 }
@@ -412,45 +479,70 @@ extern "C" int sis_modconv_wino24_eligible(int cin, int cout, int h, int w) {
     return wino24_plan(p, cin, cout, h, w) > 0 ? 1 : 0;
 }
 
-extern "C" int sis_modconv2d_wino24(float* out, const float* x, const float* u24, const float* s, const float* dscale,
-                                    const float* noise, int64_t noise_batch_stride, const float* noise_weight, const float* bias,
-                                    int batch, int cin, int cout, int h, int w, int fuse_act, int tiles_per_wg, void* stream) {
-    if (batch == 0) return 0;
-    SIS_REQUIRE(out && x && u24 && s && dscale, "sis_modconv2d_wino24: null pointer");
-    SIS_REQUIRE(batch > 0, "sis_modconv2d_wino24: non-positive size");
-    if (noise) SIS_REQUIRE(noise_weight, "sis_modconv2d_wino24: noise given without noise_weight");
+// Both entries below: out as sis_modconv2d_wino24 documents it; rgb (or null) selects the instantiation with the RGB partial sums.
+static int wino24_launch(const char* name, float* out, const float* x, const float* u24, const float* s, const float* dscale,
+                         const float* noise, int64_t noise_batch_stride, const float* noise_weight, const float* bias, int batch,
+                         int cin, int cout, int h, int w, int fuse_act, int tiles_per_wg, const W24Rgb* rgb, void* stream) {
+    SIS_REQUIRE(out && x && u24 && s && dscale, "%s: null pointer", name);
+    SIS_REQUIRE(batch > 0, "%s: non-positive size", name);
+    if (noise) SIS_REQUIRE(noise_weight, "%s: noise given without noise_weight", name);
     ConvParams p = mc_params(out, x, u24, s, dscale, noise, noise_batch_stride, noise_weight, bias, batch, cin, cout, h, w, h, w, w,
                              fuse_act != 0);
-    const int lds = wino24_plan(p, cin, cout, h, w);
-    SIS_REQUIRE(lds > 0, "sis_modconv2d_wino24: shape %dx%d, %d -> %d not eligible (sis_modconv_wino24_eligible)", h, w, cin, cout);
-    SIS_REQUIRE((int64_t)batch * (cin > cout ? cin : cout) * h * w < ((int64_t)1 << 31), "sis_modconv2d_wino24: tensor too large");
+    const int lds = wino24_plan(p, cin, cout, h, w, rgb != nullptr);
+    SIS_REQUIRE(lds > 0, "%s: shape %dx%d, %d -> %d not eligible (sis_modconv_wino24_eligible)", name, h, w, cin, cout);
+    SIS_REQUIRE((int64_t)batch * (cin > cout ? cin : cout) * h * w < ((int64_t)1 << 31), "%s: tensor too large", name);
     SIS_REQUIRE(((((uintptr_t)x | (uintptr_t)u24 | (uintptr_t)out) & 15) == 0) && (!noise || ((uintptr_t)noise & 3) == 0),
-                "sis_modconv2d_wino24: pointers must be 16-byte aligned");
+                "%s: pointers must be 16-byte aligned", name);
     const TileClass& tc = p.cls[0];
     const int64_t tiles = (int64_t)batch * tc.nth * tc.ntw;  // one-sample tiles
     p.npos_tiles = (int)tiles;
     const int n_co = cout / WMBLK;
     const int64_t blocks = tiles * n_co;
-    SIS_REQUIRE(blocks < ((int64_t)1 << 31), "sis_modconv2d_wino24: bad grid");
+    SIS_REQUIRE(blocks < ((int64_t)1 << 31), "%s: bad grid", name);
     // pixel tiles per workgroup: as many as keep >= 1024 workgroups in flight (scheduling only: every tile is computed the same
     // way whichever workgroup walks it); tiles_per_wg > 0 is the tests' override
     int tpw = 1;
     if (tiles_per_wg > 0) {
-        SIS_REQUIRE(tiles % tiles_per_wg == 0, "sis_modconv2d_wino24: %d tiles per workgroup do not divide %lld tiles", tiles_per_wg, (long long)tiles);
+        SIS_REQUIRE(tiles % tiles_per_wg == 0, "%s: %d tiles per workgroup do not divide %lld tiles", name, tiles_per_wg, (long long)tiles);
         tpw = tiles_per_wg;
     } else {
         while (tpw * 2 <= 16 && tiles % (tpw * 2) == 0 && blocks / (tpw * 2) >= 1024) tpw *= 2;
     }
     const int64_t grid = blocks / tpw;
     const int xcd_group = (double)cin * cout * 24 * sizeof(float) <= 5.0 * 1048576.0 && n_co > 1 && grid % (8 * n_co) == 0;
-    static bool have_attr = false;
-    if (!have_attr) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&modconv_wino24_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    static bool have_attr[2] = {false, false};
+    const void* fn = rgb ? reinterpret_cast<const void*>(&modconv_wino24_kernel<true>) : reinterpret_cast<const void*>(&modconv_wino24_kernel<false>);
+    if (!have_attr[rgb != nullptr]) {
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return sis_fail("modconv: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-        have_attr = true;
+        have_attr[rgb != nullptr] = true;
     }
-    sis_kernel_name = "modconv_wino24_kernel";
-    hipLaunchKernelGGL(modconv_wino24_kernel, dim3((unsigned)grid), dim3(WNTHR), (size_t)lds, (hipStream_t)stream, p, tpw, xcd_group);
-    SIS_CHECK_LAUNCH("modconv_wino24_kernel");
+    sis_kernel_name = "modconv_wino24_kernel";  // both instantiations: one kernel to the per-kernel records
+    if (rgb) {
+        hipLaunchKernelGGL(modconv_wino24_kernel<true>, dim3((unsigned)grid), dim3(WNTHR), (size_t)lds, (hipStream_t)stream, p, tpw, xcd_group, *rgb);
+    } else {
+        hipLaunchKernelGGL(modconv_wino24_kernel<false>, dim3((unsigned)grid), dim3(WNTHR), (size_t)lds, (hipStream_t)stream, p, tpw, xcd_group, W24NoRgb{});
+    }
+    SIS_CHECK_LAUNCH(name);
     return 0;
+}
+
+extern "C" int sis_modconv2d_wino24(float* out, const float* x, const float* u24, const float* s, const float* dscale,
+                                    const float* noise, int64_t noise_batch_stride, const float* noise_weight, const float* bias,
+                                    int batch, int cin, int cout, int h, int w, int fuse_act, int tiles_per_wg, void* stream) {
+    if (batch == 0) return 0;
+    return wino24_launch("sis_modconv2d_wino24", out, x, u24, s, dscale, noise, noise_batch_stride, noise_weight, bias, batch, cin, cout,
+                         h, w, fuse_act, tiles_per_wg, nullptr, stream);
+}
+
+extern "C" int sis_modconv2d_wino24_rgb(float* out, float* rgb_part, const float* x, const float* u24, const float* s, const float* dscale,
+                                        const float* noise, int64_t noise_batch_stride, const float* noise_weight, const float* bias,
+                                        const float* rgb_w, const float* rgb_s, float rgb_scale, int batch, int cin, int cout, int h,
+                                        int w, int fuse_act, int tiles_per_wg, void* stream) {
+    if (batch == 0) return 0;
+    SIS_REQUIRE(rgb_part && rgb_w && rgb_s, "sis_modconv2d_wino24_rgb: null pointer");
+    SIS_REQUIRE(((uintptr_t)rgb_part & 15) == 0, "sis_modconv2d_wino24_rgb: rgb_part must be 16-byte aligned");
+    const W24Rgb rgb = {rgb_w, rgb_s, rgb_part, rgb_scale};
+    return wino24_launch("sis_modconv2d_wino24_rgb", out, x, u24, s, dscale, noise, noise_batch_stride, noise_weight, bias, batch, cin,
+                         cout, h, w, fuse_act, tiles_per_wg, &rgb, stream);
 }

@@ -166,9 +166,7 @@ class ModulatedConv2d(nn.Module):
             # and a layer holds no planes it never runs on.  SIS_WINOGRAD=0 selects the direct kernel everywhere,
             # SIS_WINO24=0 F(2x2,3x3) wherever a Winograd kernel runs (bisecting / A-B runs); both are read here, per pack.
             self._wino = self._wino24 = None
-            self._wino_on = (self.kernel_size == 3 and not self.upsample and not self.downsample and self.in_channel % 8 == 0
-                             and self.out_channel % 4 == 0 and os.environ.get("SIS_WINOGRAD", "1") != "0")
-            self._wino24_on = self._wino_on and os.environ.get("SIS_WINO24", "1") != "0"
+            self._wino_on, self._wino24_on = self._winograd_switches()
             # up-convolutions keep the 16 transformed planes of the fast-FIR kernel (25 instead of 36 multiplies per 2 x 2
             # input positions, csrc/modconv_upfir.hip); the launch falls back to the 4-phase kernel below 32 x 32
             self._fir = None
@@ -176,6 +174,16 @@ class ModulatedConv2d(nn.Module):
                 self._fir = sis_hip.modconv_prepack_up_fir(w.detach())
             self._pack_key = key
         return self._pack
+
+    def _winograd_switches(self):
+        wino = (self.kernel_size == 3 and not self.upsample and not self.downsample and self.in_channel % 8 == 0
+                and self.out_channel % 4 == 0 and os.environ.get("SIS_WINOGRAD", "1") != "0")
+        return wino, wino and os.environ.get("SIS_WINO24", "1") != "0"
+
+    def wino24_takes(self, h, w):
+        """Whether an h x w map of this layer runs on the F(2x4,3x3) kernel (the switches as the current pack read them)."""
+        on = self._wino24_on if self._pack_key is not None else self._winograd_switches()[1]
+        return bool(on and sis_hip.modconv_wino24_eligible(self.in_channel, self.out_channel, h, w))
 
     def wino_weights(self):
         self.packed_weights()
@@ -187,7 +195,7 @@ class ModulatedConv2d(nn.Module):
         """The keyword of sis_hip.modconv2d that carries this layer's transformed weights for an h x w map: the F(2x4,3x3) planes
         where that kernel takes (Cin, Cout, h, w) -- the batch plays no part -- and the F(2x2,3x3) planes (or None) otherwise."""
         self.packed_weights()
-        if self._wino24_on and sis_hip.modconv_wino24_eligible(self.in_channel, self.out_channel, h, w):
+        if self.wino24_takes(h, w):
             if self._wino24 is None:
                 self._wino24 = sis_hip.modconv_prepack_wino24(self.weight.detach())
             return {"wino24_u": self._wino24}
@@ -307,9 +315,10 @@ class StyledConv(nn.Module):
         wpk, s, dscale = conv.modulate(style)
         return self.forward_s(input, wpk, s, dscale, noise)
 
-    def forward_s(self, input, wpk, s, dscale, noise=None, out=None):
+    def forward_s(self, input, wpk, s, dscale, noise=None, out=None, rgb=None):
         """Fused layer given the already computed style vector ``s`` [B,Cin] and epilogue factors [B,Cout].  ``out`` (stride-1
-        layers): result tensor to write into."""
+        layers): result tensor to write into.  ``rgb`` (layers that ``conv.wino24_takes``): ``ToRGB.fused_operands`` of the
+        ToRGB that follows; the convolution leaves its channel sum for ``ToRGB.finish_s``."""
         conv, act = self.conv, self.activate
         b, _, h, w = input.shape
         if conv.upsample:
@@ -325,7 +334,7 @@ class StyledConv(nn.Module):
         if noise is None:
             noise = input.new_empty(b, 1, h, w).normal_()
         return sis_hip.modconv2d(input, wpk, s, dscale, conv.kernel_size, noise, self.noise.weight, act.bias,
-                                 fuse_act=True, out=out, **conv.winograd_operand(h, w))
+                                 fuse_act=True, out=out, rgb=rgb, **conv.winograd_operand(h, w))
 
 
 class ToRGB(nn.Module):
@@ -353,6 +362,22 @@ class ToRGB(nn.Module):
         if up.factor != 2:
             return sis_hip.to_rgb(input, conv.weight, s, self.bias, conv.scale) + up(skip)
         return sis_hip.to_rgb(input, conv.weight, s, self.bias, conv.scale, skip, up.kernel, up.pad, out=out)
+
+    # ---- the form whose channel sum the convolution in front has already formed (sis_hip.modconv2d(..., rgb=)) ----
+    def fused_operands(self, s, batch, h, w):
+        """The ``rgb=`` operand of ``StyledConv.forward_s``.  The partial-sum buffer belongs to this layer and is reused from call
+        to call (as the prepacked planes of a convolution): it is rebuilt when the batch or the map changes."""
+        conv = self.conv
+        key = (s.device,) + sis_hip.rgb_part_shape(batch, conv.in_channel, h, w)
+        if getattr(self, '_part_key', None) != key:
+            self._part = torch.empty(key[1:], dtype=torch.float32, device=s.device)
+            self._part_key = key
+        return conv.weight, s, conv.scale, self._part
+
+    def finish_s(self, skip, out=None):
+        """The image from the partial sums that the convolution given ``fused_operands`` has left."""
+        up = self.upsample
+        return sis_hip.rgb_finish(self._part, self.bias, skip, up.kernel, up.pad, out=out)
 
 
 def truncate_styles(style, truncation, truncation_latent):
@@ -513,11 +538,24 @@ class Generator(nn.Module):
             return 1
         return parts
 
+    @staticmethod
+    def _rgb_fused(conv, rgb, h, w, skip, parts=1):
+        """Whether a resolution's second convolution also forms the channel sum of its ToRGB (``ToRGB.fused_operands``), which
+        then only adds the channel blocks, the bias and the skip image instead of reading the activation again: wherever the
+        F(2x4,3x3) kernel takes the convolution (32^2 and up in the 256^2 generator).  At the last resolution that pass was
+        exposed on the main stream; the hidden ones no longer share HBM and CUs with the up-convolutions beside them
+        (profiles/wino24_rgb_epilogue.txt).  The batch-part form (``_tail``) keeps the separate ToRGB."""
+        if parts > 1 or skip is None or rgb.upsample.factor != 2 or rgb.conv.out_channel != 3:
+            return False
+        return conv.conv.wino24_takes(h, w)
+
     def _tail(self, x, conv, rgb, s_conv, d_conv, s_rgb, noise, skip, main, side):
         """The last StyledConv and its ToRGB by batch parts.  The final ToRGB has no later convolution to hide behind (196 us of
         a 14.9 ms step at B = 32: an HBM-bound pass over the 1 GB activation with the matrix cores idle), so the batch is cut
         in parts: while the convolution of part k + 1 runs, the side stream converts part k; only the last part's ToRGB is
-        exposed.  Results are written into batch slices of ONE activation tensor and ONE image: same values, same layout."""
+        exposed.  Results are written into batch slices of ONE activation tensor and ONE image: same values, same layout.
+        (Off by default; by default that exposed pass is gone instead: the last convolution forms the channel sum in its
+        epilogue, ``_rgb_fused``, and a finish launch over 3 x (Cout / 64 + 1) planes is what stays on the main stream.)"""
         parts = self._tail_parts(x, rgb, skip)
         b, _, h, w = x.shape
         n = b // parts
@@ -577,19 +615,21 @@ class Generator(nn.Module):
             # HBM-bound passes overlap the MFMA-bound convolutions of the next resolution.
             main, side = torch.cuda.current_stream(latent.device), self._rgb_stream(latent.device)
 
-            def rgb_branch(layer, x, style, prev, last=False):
+            def rgb_branch(layer, x, style, prev, last=False, fused=False):
+                # fused: the convolution that wrote x has left the layer's channel sum (ToRGB.fused_operands)
+                run = (lambda: layer.finish_s(prev)) if fused else (lambda: layer.forward_s(x, style, prev))
                 if side is None:
-                    return layer.forward_s(x, style, prev)
+                    return run()
                 if last:  # nothing left to overlap it with: on the main stream, behind the side chain (no fork / join gap)
                     main.wait_event(side.record_event())
                     if prev is not None:
                         prev.record_stream(main)  # allocated on the side stream, read here
-                    return layer.forward_s(x, style, prev)
+                    return run()
                 ready = main.record_event()
                 x.record_stream(side)
                 with torch.cuda.stream(side):
                     side.wait_event(ready)
-                    return layer.forward_s(x, style, prev)
+                    return run()
 
             out = self.conv1.forward_s(out, self.conv1.conv.packed_weights()[0], s[0], d[0], noise[0])
             tap(1, out)
@@ -604,9 +644,11 @@ class Generator(nn.Module):
                     out, skip = self._tail(out, conv, rgb, s[j + 1], d[j + 1], s[j + 2], noise[2 + 2 * r], skip, main, side)
                     tap(i + 2, out)
                     continue
-                out = conv.forward_s(out, conv.conv.packed_weights()[0], s[j + 1], d[j + 1], noise[2 + 2 * r])
+                fused = self._rgb_fused(conv, rgb, out.shape[2], out.shape[3], skip, self._tail_parts(out, rgb, skip) if last else 1)
+                operands = rgb.fused_operands(s[j + 2], out.shape[0], out.shape[2], out.shape[3]) if fused else None
+                out = conv.forward_s(out, conv.conv.packed_weights()[0], s[j + 1], d[j + 1], noise[2 + 2 * r], rgb=operands)
                 tap(i + 2, out)
-                skip = rgb_branch(rgb, out, s[j + 2], skip, last=last)
+                skip = rgb_branch(rgb, out, s[j + 2], skip, last=last, fused=fused)
             if side is not None and self.log_size == 2:  # 4 x 4 generator: to_rgb1 is the only (side-stream) ToRGB
                 main.wait_event(side.record_event())
                 skip.record_stream(main)

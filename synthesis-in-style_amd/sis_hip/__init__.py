@@ -50,6 +50,8 @@ _SIGNATURES = {
     "sis_modconv_prepack_wino24": ([_vp, _vp, _i, _i, _vp], _i),
     "sis_modconv_wino24_eligible": ([_i] * 4, _i),
     "sis_modconv2d_wino24": ([_vp] * 6 + [_i64, _vp, _vp] + [_i] * 7 + [_vp], _i),
+    "sis_modconv2d_wino24_rgb": ([_vp] * 7 + [_i64, _vp, _vp, _vp, _vp, _f] + [_i] * 7 + [_vp], _i),
+    "sis_rgb_finish": ([_vp] * 5 + [_i] * 9 + [_vp], _i),
     "sis_last_kernel": ([], ctypes.c_char_p),
     "sis_conv3x3_prepack": ([_vp, _vp, _i, _i, _i, _vp], _i),
     "sis_conv3x3_prepack_both": ([_vp, _vp, _vp, _i, _i, _vp], _i),
@@ -946,15 +948,42 @@ def _out_or_new(out, shape, device, what):
     return out
 
 
+def rgb_part_shape(batch, cout, h, w):
+    """Shape of the partial-sum buffer that ``modconv2d(..., rgb=)`` fills and ``rgb_finish`` reads."""
+    return (cout // 64, batch, 3, h, w)
+
+
 def modconv2d(x, wpk, s, dscale, ksize, noise=None, noise_weight=None, bias=None, fuse_act=False, wino_u=None, out=None,
-              wino24_u=None, wino24_tiles_per_wg=0):
+              wino24_u=None, wino24_tiles_per_wg=0, rgb=None):
     """``wino24_u`` (modconv_prepack_wino24): the layer runs on the F(2x4,3x3) kernel where modconv_wino24_eligible says so,
-    whatever the batch; other shapes take the path they took without it.  ``wino24_tiles_per_wg``: tests only."""
+    whatever the batch; other shapes take the path they took without it.  ``wino24_tiles_per_wg``: tests only.
+
+    ``rgb`` = (weight [3 * Cout], s_rgb [B, Cout], scale, part): the F(2x4,3x3) kernel also leaves the following ToRGB's channel
+    sum in ``part`` (``rgb_part_shape``), in blocks of 64 channels, for ``rgb_finish``; an error where that kernel does not take
+    the layer."""
     x = _f32(x, "input")
     batch, cin, h, w = x.shape
     cout = wpk.shape[2]
     noise, nbs = _noise_args(noise, batch, h, w)
     out = _out_or_new(out, (batch, cout, h, w), x.device, "modconv2d")
+    if rgb is not None:
+        if wino24_u is None or ksize != 3 or batch <= 0 or not modconv_wino24_eligible(cin, cout, h, w):
+            raise RuntimeError(f"modconv2d: rgb= needs the F(2x4,3x3) kernel, which does not take {cin} -> {cout} at {h}x{w}")
+        rgb_w, rgb_s, rgb_scale, part = rgb
+        rgb_w, rgb_s = _f32(rgb_w, "rgb weight"), _f32(rgb_s, "rgb style")
+        if rgb_w.numel() != 3 * cout or tuple(rgb_s.shape) != (batch, cout):
+            raise RuntimeError(f"modconv2d: rgb weight {tuple(rgb_w.shape)} / style {tuple(rgb_s.shape)} do not fit 3 x {cout} channels")
+        _out_or_new(part, rgb_part_shape(batch, cout, h, w), x.device, "modconv2d rgb part")
+        with torch.cuda.device(x.device):
+            _check(_launch(None,
+                           0.75 * 2.0 * batch * cout * cin * 9 * h * w,
+                           4.0 * (x.numel() + out.numel() + wino24_u.numel() + part.numel()),
+                           lambda: lib().sis_modconv2d_wino24_rgb(_ptr(out), _ptr(part), _ptr(x), _ptr(wino24_u), _ptr(s), _ptr(dscale),
+                                                                  _ptr(noise), nbs, _ptr(noise_weight), _ptr(bias), _ptr(rgb_w),
+                                                                  _ptr(rgb_s), float(rgb_scale), batch, cin, cout, h, w,
+                                                                  int(bool(fuse_act)), int(wino24_tiles_per_wg), _stream())),
+                   "sis_modconv2d_wino24_rgb")
+        return out
     if wino24_u is not None and ksize == 3 and batch > 0 and modconv_wino24_eligible(cin, cout, h, w):
         with torch.cuda.device(x.device):
             # FLOPs recorded as direct form x 3/4: bench.py prices every kernel whose name contains "wino" at 16/36 of the
@@ -1055,6 +1084,24 @@ def to_rgb(x, weight, s, bias, scale, skip=None, taps=None, pad=(0, 0), out=None
                        lambda: lib().sis_to_rgb(_ptr(out), _ptr(x), _ptr(w), _ptr(s), _ptr(bias), _ptr(skip),
                                                 _ptr(taps), batch, cin, cout, h, wd, kh, kw, pad[0], pad[1],
                                                 float(scale), _stream())), "sis_to_rgb")
+    return out
+
+
+def rgb_finish(part, bias, skip=None, taps=None, pad=(0, 0), out=None):
+    """The ToRGB image from the channel-block sums ``part`` [Cout / 64, B, 3, H, W] of ``modconv2d(..., rgb=)``:
+    sum over the blocks + bias + upsampled skip (as ``to_rgb``)."""
+    part = _f32(part, "part")
+    blocks, batch, cout, h, wd = part.shape
+    kh = kw = 0
+    if skip is not None:
+        skip = _f32(skip, "skip")
+        taps = _f32(taps, "kernel")
+        kh, kw = taps.shape
+    out = _out_or_new(out, (batch, cout, h, wd), part.device, "rgb_finish")
+    with torch.cuda.device(part.device):
+        _check(_launch("rgb_finish_kernel", 0.0, 4.0 * (part.numel() + out.numel() + (skip.numel() if skip is not None else 0)),
+                       lambda: lib().sis_rgb_finish(_ptr(out), _ptr(part), _ptr(bias), _ptr(skip), _ptr(taps), batch, blocks, cout,
+                                                    h, wd, kh, kw, pad[0], pad[1], _stream())), "sis_rgb_finish")
     return out
 
 

@@ -2,7 +2,8 @@
 usage: python tools/bench_layers.py [batch] [reps] [layer, e.g. conv64]   -> one line per layer: ms, TFLOP/s
 SIS_WINOGRAD=0: direct kernel; SIS_WINO24=0: F(2x2,3x3) where F(2x4,3x3) would run (the generator's own switches).
 SIS_LAYER_LAUNCHES=1: per-launch times instead (median, min, max), the form the per-layer selection rule of DESIGN 3.2 reads.
-SIS_WINO24_TPW=n: n tiles per workgroup on the F(2x4,3x3) layers instead of the launcher's choice."""
+SIS_WINO24_TPW=n: n tiles per workgroup on the F(2x4,3x3) layers instead of the launcher's choice.
+SIS_WINO24_RGB=1: the F(2x4,3x3) layers also form the ToRGB channel sum (modconv_wino24_kernel<true>)."""
 import os
 import sys
 
@@ -40,6 +41,9 @@ for kind, cin, cout, h in layers:
     bias = torch.zeros(cout, device=dev)
     if kind == "conv" and WINO24 and sis_hip.modconv_wino24_eligible(cin, cout, h, h):
         kw = {"wino24_u": sis_hip.modconv_prepack_wino24(w), "wino24_tiles_per_wg": int(os.environ.get("SIS_WINO24_TPW", "0"))}
+        if os.environ.get("SIS_WINO24_RGB", "0") == "1":
+            kw["rgb"] = (torch.randn(3, cout, device=dev), 1 + 0.1 * torch.randn(B, cout, device=dev), 1 / cout ** 0.5,
+                         torch.empty(sis_hip.rgb_part_shape(B, cout, h, h), device=dev))
     else:
         kw = {"wino_u": sis_hip.modconv_prepack_wino(w) if (WINO and kind == "conv") else None}
     f = (lambda: sis_hip.modconv2d(x, wpk, s, ds, 3, noise, nw, bias, fuse_act=True, **kw)) if kind == "conv" else \
