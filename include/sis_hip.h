@@ -989,6 +989,40 @@ int sis_png_encode_pairs(uint8_t* out, int* sizes, const uint8_t* image, const u
                          int label_width, int64_t out_stride, uint32_t ihdr_crc, void* workspace, int64_t workspace_bytes,
                          void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Reconstruction metrics and the denoising loader (csrc/eval_ops.h).  No host sync, no atomics, every sum in a
+ * fixed order: bit-reproducible and capturable.
+ * sis_psnr_ssim_tile: the tile edge of the SSIM kernel (tests size a shape around it).
+ * sis_psnr_ssim_workspace_bytes: bytes of device workspace of one sis_psnr_ssim call (tile partials, partial minima).
+ * sis_psnr_ssim (evaluation/psnr_ssim.py:14-39, PSNRSSIMEvaluator.unnormalize / psnr / ssim of every sample of a batch; the
+ *   reference calls kornia once per image at batch size 1): image, target float32 [batch][channels][height][width] ->
+ *   psnr[b] = 10 log10(max_val^2 / mse_b), the POSITIVE metric (kornia.psnr_loss changed sign between versions; what is reported
+ *   is the metric), +inf where mse_b == 0; ssim[b] = mean over the sample of clamp(s, 0, 1), the value of the reference's
+ *   (1 - 2 ssim_loss(..., reduction='none')).mean() with ssim_loss = clamp(1 - s, 0, 1) / 2; and, where ssim_map is not null,
+ *   ssim_map [batch][channels][height][width] = the unclamped s.  s = (2 mu_x mu_y + C1)(2 sigma_xy + C2) / ((mu_x^2 + mu_y^2 +
+ *   C1)(sigma_x^2 + sigma_y^2 + C2)), mu = the image filtered with the normalised separable Gaussian of `window` taps and sigma
+ *   1.5 under reflect padding that does not repeat the edge, sigma_x^2 = G(x^2) - mu_x^2, sigma_xy = G(xy) - mu_x mu_y,
+ *   C1 = (0.01 max_val)^2, C2 = (0.03 max_val)^2.  mode 0: per sample, a tensor whose minimum is < 0 is first mapped by
+ *   x <- (clamp(x, -1, 1) + 1) / 2 (pytorch_training's clamp_and_unnormalize), image and target decided independently, as
+ *   `unnormalize` does at batch size 1; mode 1: both always; mode 2: neither.  Moments and sums are accumulated in double.
+ *   window odd in 3..11, height and width > window / 2, batch <= 65535, a sample < 2^31 elements; workspace 8-byte aligned.
+ * sis_autoencoder_batch (data/autoencoder_dataset.py:21-36 __getitem__, :44-54 iaa.AdditiveGaussianNoise, :59-67 the grey
+ *   conversion, with the DataLoader's collate): images uint8 [n_images][3][size][size] resident on the device, ids int32 [batch],
+ *   per-sample scale float [batch], per_channel int32 [batch], seed uint32 [batch], grey int32 [batch] (all device) ->
+ *   output_image = (p / 255 - 0.5) / 0.5, bit-equal to sis_gan_image_batch, and input_image = the same map of
+ *   q = clip(rint(p + scale * z), 0, 255) (half to even), z a standard normal by Box-Muller from a counter hash of (seed,
+ *   component, pixel) (bit recipe: DESIGN.md §15), one z per pixel shared by the three channels unless per_channel; with grey,
+ *   after the noise, all three channels become (19595 R + 38470 G + 7471 B + 32768) >> 16 (PIL's convert('L').convert('RGB')).
+ *   Both outputs float32 [batch][3][size][size], written in one launch.  scale == 0 reproduces p.  An id outside 0 .. n_images - 1
+ *   yields NaN samples and reads nothing.  16-byte stores when size * size % 4 == 0. */
+int sis_psnr_ssim_tile(void);
+int64_t sis_psnr_ssim_workspace_bytes(int batch, int channels, int height, int width);
+int sis_psnr_ssim(float* psnr, float* ssim, float* ssim_map, const float* image, const float* target, int batch, int channels,
+                  int height, int width, int window, float max_val, int mode, void* workspace, int64_t workspace_bytes, void* stream);
+int sis_autoencoder_batch(float* input_image, float* output_image, const uint8_t* images, const int* ids, const float* scale,
+                          const int* per_channel, const uint32_t* seed, const int* grey, int64_t n_images, int batch, int size,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

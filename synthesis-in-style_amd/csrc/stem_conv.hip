@@ -285,3 +285,7 @@ extern "C" int sis_stem_conv_wgrad(void* dw, int dw_dtype, const void* x, int x_
 // GAN training from an image list: the loader's batch gather, and the phase split / weight composition that run a discriminator
 // downsampling layer on the Winograd kernels (train_stylegan_2.py, networks/hip_conv.py down_conv3x3)
 #include "gan_train_ops.h"
+
+// reconstruction metrics (PSNR / SSIM of a batch) and the denoising autoencoder loader's batch (evaluation/psnr_ssim.py,
+// data/autoencoder_dataset.py); after gan_train_ops.h, whose gan_norm it uses
+#include "eval_ops.h"

@@ -212,6 +212,10 @@ _SIGNATURES = {
     "sis_png_capacity": ([_i, _i], _i64),
     "sis_png_encode_pairs_workspace_bytes": ([_i, _i], _i64),
     "sis_png_encode_pairs": ([_vp] * 4 + [_i] * 4 + [_i64, ctypes.c_uint32, _vp, _i64, _vp], _i),
+    "sis_psnr_ssim_tile": ([], _i),
+    "sis_psnr_ssim_workspace_bytes": ([_i] * 4, _i64),
+    "sis_psnr_ssim": ([_vp] * 5 + [_i] * 5 + [_f, _i, _vp, _i64, _vp], _i),
+    "sis_autoencoder_batch": ([_vp] * 8 + [_i64, _i, _i, _vp], _i),
 }
 
 
@@ -3368,3 +3372,77 @@ def png_encode_pairs(image_u8, label_u8=None, out=None):
                                                           png_ihdr_crc(w + wl, h), _ptr(ws), ws.numel() * 4, _stream())),
                "sis_png_encode_pairs")
     return out, sizes
+
+
+# ------------------------------------------------------------------------------ reconstruction metrics (csrc/eval_ops.h)
+
+UNNORMALIZE_AUTO, UNNORMALIZE_ALWAYS, UNNORMALIZE_NEVER = 0, 1, 2
+
+
+def psnr_ssim_tile():
+    """Tile edge of the SSIM kernel."""
+    return int(lib().sis_psnr_ssim_tile())
+
+
+def psnr_ssim(image, target, window=5, max_val=1.0, unnormalize=UNNORMALIZE_AUTO, return_map=False):
+    """float32 [B, C, H, W] image and target -> (psnr [B], ssim [B]) device tensors, with ``return_map`` also the unclamped SSIM
+    map [B, C, H, W]: the reference's ``PSNRSSIMEvaluator`` applied to every sample on its own (DESIGN.md §15 states the
+    definitions).  ``psnr`` is the positive metric 10 log10(max_val^2 / mse) (+inf for equal samples), ``ssim`` the mean of
+    clamp(s, 0, 1).  ``unnormalize``: 0 decides per sample and tensor by ``min < 0`` as the reference does, 1 maps both tensors
+    by (clamp(x, -1, 1) + 1) / 2, 2 leaves both.  Three launches on the current stream, no host sync."""
+    require_device(image, "image")
+    require_device(target, "target")
+    if image.dtype != torch.float32 or target.dtype != torch.float32 or image.dim() != 4 or image.shape != target.shape \
+            or image.device != target.device or image.numel() == 0:
+        raise RuntimeError(f"psnr_ssim: float32 [B, C, H, W] image and target of one shape on one device are needed, got "
+                           f"{image.dtype} {tuple(image.shape)} and {target.dtype} {tuple(target.shape)}")
+    window, mode = int(window), int(unnormalize)
+    b, c, h, w = image.shape
+    if window % 2 != 1 or not 3 <= window <= 11 or h <= window // 2 or w <= window // 2:
+        raise RuntimeError(f"psnr_ssim: window {window} must be odd in 3..11 and H, W = {h}, {w} larger than window // 2")
+    if mode not in (UNNORMALIZE_AUTO, UNNORMALIZE_ALWAYS, UNNORMALIZE_NEVER):
+        raise RuntimeError(f"psnr_ssim: unnormalize {unnormalize} is not 0 (by the minimum), 1 (always) or 2 (never)")
+    image, target = image.contiguous(), target.contiguous()
+    psnr = torch.empty((b,), dtype=torch.float32, device=image.device)
+    ssim = torch.empty((b,), dtype=torch.float32, device=image.device)
+    smap = torch.empty((b, c, h, w), dtype=torch.float32, device=image.device) if return_map else None
+    ws_bytes = int(lib().sis_psnr_ssim_workspace_bytes(b, c, h, w))
+    ws = torch.empty((ws_bytes // 8,), dtype=torch.float64, device=image.device)
+    n = image.numel()
+    reads = (3.0 if mode == UNNORMALIZE_AUTO else 2.0) * 4.0 * n
+    taps = 2.0 * window * 5 * 2   # row + column pass of five moments, one FMA per tap
+    with torch.cuda.device(image.device):
+        _check(_launch("psnr_ssim_tile_kernel", (taps + 40.0) * n, reads + (4.0 * n if return_map else 0.0),
+                       lambda: lib().sis_psnr_ssim(_ptr(psnr), _ptr(ssim), _ptr(smap), _ptr(image), _ptr(target), b, c, h, w, window,
+                                                   float(max_val), mode, _ptr(ws), ws_bytes, _stream())), "sis_psnr_ssim")
+    return (psnr, ssim, smap) if return_map else (psnr, ssim)
+
+
+def autoencoder_batch(images, ids, scale, per_channel, seed, grey):
+    """Resident uint8 [N, 3, S, S], int32 ids [B] and the per-sample noise parameters (device tensors [B]: float32 ``scale``,
+    int32 ``per_channel``, int32 ``seed`` -- its 32 bits are the seed word --, int32 ``grey``) -> (input_image, output_image),
+    float32 [B, 3, S, S]: the reference's (Denoising / BlackAndWhiteDenoising)AutoencoderDataset batch in one launch.
+    ``output_image`` equals ``gan_image_batch``; ``input_image`` is the same map of clip(rint(p + scale * z), 0, 255), grey
+    after the noise where asked.  The caller keeps the ids inside 0 .. N - 1 (an id outside yields NaN samples)."""
+    require_device(images, "images")
+    require_device(ids, "ids")
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[1] != 3 or images.shape[2] != images.shape[3]:
+        raise RuntimeError(f"autoencoder_batch: uint8 [N, 3, S, S] images are needed, got {images.dtype} {tuple(images.shape)}")
+    if ids.dtype != torch.int32 or ids.dim() != 1 or ids.numel() == 0 or ids.device != images.device:
+        raise RuntimeError("autoencoder_batch: int32 [B] ids on the images' device are needed")
+    for t, name, dtype in ((scale, "scale", torch.float32), (per_channel, "per_channel", torch.int32), (seed, "seed", torch.int32),
+                           (grey, "grey", torch.int32)):
+        require_device(t, name)
+        if t.dtype != dtype or tuple(t.shape) != tuple(ids.shape) or t.device != images.device:
+            raise RuntimeError(f"autoencoder_batch: {name} must be a {dtype} [B] tensor on the images' device, got {t.dtype} {tuple(t.shape)}")
+    images, ids = images.contiguous(), ids.contiguous()
+    scale, per_channel, seed, grey = scale.contiguous(), per_channel.contiguous(), seed.contiguous(), grey.contiguous()
+    n, _, size, _ = images.shape
+    b = ids.numel()
+    inp = torch.empty((b, 3, size, size), dtype=torch.float32, device=images.device)
+    out = torch.empty((b, 3, size, size), dtype=torch.float32, device=images.device)
+    with torch.cuda.device(images.device):
+        _check(_launch("autoencoder_batch_kernel", 0.0, 9.0 * out.numel(),
+                       lambda: lib().sis_autoencoder_batch(_ptr(inp), _ptr(out), _ptr(images), _ptr(ids), _ptr(scale), _ptr(per_channel),
+                                                           _ptr(seed), _ptr(grey), n, b, size, _stream())), "sis_autoencoder_batch")
+    return inp, out
