@@ -1023,6 +1023,31 @@ int sis_autoencoder_batch(float* input_image, float* output_image, const uint8_t
                           const int* per_channel, const uint32_t* seed, const int* grey, int64_t n_images, int batch, int size,
                           void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Dataset ground truth: per-image class listing and COCO annotations (csrc/coco_gt.h; the reference's
+ * segmentation/evaluation/coco_gt.py:38-92 and create_dataset_for_segmentation.py:151-206).  Integers only, fixed launch
+ * sequence, no host sync, the same bytes on every run.  Stated in DESIGN.md §16 and tested against an independent restatement;
+ * NOT pinned against OpenCV's findContours or pycocotools.
+ * sis_label_regions_workspace_bytes (coco_gt.py:38-92): bytes of device workspace of one call; 0 for a size < 1 or p > 1024.
+ * sis_label_regions (coco_gt.py:38-92 extract_rle / determine_classes_in_image / build_annotations_for_image;
+ *   create_dataset_for_segmentation.py:151-206 the has_<class> keys and coco_gt.json): label uint8 [batch][p][p][3] (device),
+ *   colours uint8 [classes][3] on the HOST (the annotated classes' colours).  Per plane (b, k): M = (label[b] == colours[k]) on
+ *   all three bytes; the regions are the 8-connected components of everything the 4-connected background of M cannot reach
+ *   from outside the plane (outermost contours, holes filled), in ascending order of root = the smallest y * p + x of the
+ *   region.  regions [batch][classes][max_regions][8] int32 = root, x0, y0, w, h (tight box), area (pixels), run_offset,
+ *   run_count; a region whose pixels all lie on one horizontal, vertical or diagonal line has run_count 0 and no runs.
+ *   runs [batch][classes][max_runs] int32: from run_offset, the region's COCO uncompressed RLE over the whole plane in
+ *   column-major order (position x * p + y; the first count is the number of leading zeros; the counts sum to p * p).
+ *   has [batch][classes] uint8: 1 iff the plane has a region with runs.  region_count, run_total [batch][classes] int32: the true
+ *   numbers, also above the capacities; rows and counts beyond max_regions / max_runs are not stored.  runs == NULL: no counts
+ *   are emitted and max_runs is ignored (run_offset, run_count and run_total are still filled); regions == NULL: no rows are
+ *   stored and max_regions is ignored.  1 <= classes <= 8, p <= 1024, batch * classes <= 65535; workspace 4-byte aligned.
+ *   Declines with an error code and launches nothing otherwise. */
+int64_t sis_label_regions_workspace_bytes(int batch, int classes, int p);
+int sis_label_regions(uint8_t* has, int32_t* region_count, int32_t* regions, int32_t* run_total, int32_t* runs, const uint8_t* label,
+                      const uint8_t* colours, int classes, int batch, int p, int max_regions, int max_runs, void* workspace,
+                      int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

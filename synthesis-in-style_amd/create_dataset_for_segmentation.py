@@ -7,7 +7,17 @@ layers on the device (FactorCatalog.predict) -> uint8 images on the device -> si
 in the reference's directory layout ``<id // 100000>/<id // 1000>/<id>.png`` (save_image, :84-90).
 
 Without a ``segmenter_type`` the label half of the PNG is the raw cluster-id map of ``label_layer``
-(id * 255 // (K-1) grey levels).  Not reproduced: COCO ground truth (``coco_gt.json``), the per-image class listing, debug images.
+(id * 255 // (K-1) grey levels).  Not reproduced: debug images.
+
+``--ground-truth`` (opt-in; needs ``class_to_color_map`` in the config; without it every output is what it was): the
+reference's ground truth (:151-206).  In the loop the label image of every batch goes through ``sis_hip.label_regions`` in
+listing mode on the label side stream (csrc/coco_gt.h), and when the batch is flushed the ``has_<class>`` truth
+values of the written images are appended, one JSON line per image, to ``class_listing.rank<r>.jsonl`` below the save
+directory.  The split then carries these keys in every entry of ``train.json`` / ``val.json`` (files the sidecars do not cover
+are listed from their PNGs) and writes ``coco_gt.json`` for the validation images in ``val.json`` order: one annotation per
+outermost contour of a class, holes filled, with RLE, area and bbox (segmentation/evaluation/coco_gt.py).
+``--only-create-train-val-split --ground-truth`` does the same on a finished directory, with or without sidecars, which is
+also the way after a run on several ranks.  ``scripts/balance_segmentation_train_gt.py`` consumes the keys.
 
 Train / validation split (the reference's :180-202): after a normal run with ``--save-to`` (rank 0), or alone behind
 ``--only-create-train-val-split``, the PNGs below the save directory are shuffled with ``random.seed(config['seed'])`` and
@@ -56,10 +66,19 @@ import torch
 import sis_hip  # noqa: F401  (fails loudly at import when libsis_hip.so is missing: there is no CPU path)
 from networks import get_stylegan2_generator
 from segmentation.gan_local_edit.factor_catalog import FactorCatalog
-from utils.dataset_creation import encode_pairs_on_device, label_and_encode, seeded_latents, shard_range
+from utils.dataset_creation import encode_pairs_on_device, label_and_encode, list_classes_on_device, seeded_latents, shard_range
 
 PNG_ENCODERS = ("pil", "device")
 MAX_PNG_WRITERS = 8
+CLASS_LISTING = "class_listing.rank{rank}.jsonl"
+
+
+def ground_truth_creator(creation_config, image_root):
+    """The COCOGtCreator of ``--ground-truth`` (the reference's :185)."""
+    from segmentation.evaluation.coco_gt import COCOGtCreator
+    if 'class_to_color_map' not in creation_config:
+        raise ValueError('--ground-truth needs "class_to_color_map" in the config file')
+    return COCOGtCreator(creation_config['class_to_color_map'], image_root=Path(image_root))
 
 
 def png_writer_count(requested) -> int:
@@ -178,6 +197,11 @@ def build_dataset(args, creation_config, rank=0, world_size=1):
     on_device = encoder == 'device' and save_dir is not None
     writers = PngWriterPool(getattr(args, 'png_writers', None)) if on_device else None
     name_format = f"{{id:0{max(4, len(str(args.num_images)))}d}}.png"
+    listing = None   # --ground-truth: (creator, the open sidecar) of this rank
+    if getattr(args, 'ground_truth', False) and save_dir is not None:
+        creator = ground_truth_creator(creation_config, save_dir)
+        save_dir.mkdir(exist_ok=True, parents=True)
+        listing = (creator, (save_dir / CLASS_LISTING.format(rank=rank)).open('w'))
     torch.random.manual_seed(creation_config.get('seed', 1))
     done = 0
 
@@ -198,7 +222,7 @@ def build_dataset(args, creation_config, rank=0, world_size=1):
 
     def flush(job):
         """Host side of a finished batch: wait for its label pass, then encode / write the files."""
-        first_id, pixels, labels, ready, files = job
+        first_id, pixels, labels, ready, files, listed = job
         if ready is not None:
             ready.synchronize()
         keep = None
@@ -207,6 +231,14 @@ def build_dataset(args, creation_config, rank=0, world_size=1):
             dropped.extend(first_id + int(i) for i in numpy.nonzero(~keep)[0])
         if save_dir is None:
             return
+        if listed is not None:   # its copy was issued on the label stream before the event(s) this function waits for
+            if ready is None:
+                listed[1].synchronize()
+            creator, sidecar = listing
+            for idx, row in enumerate(listed[0].numpy()):
+                if keep is None or keep[idx]:
+                    name = str(image_path(first_id + idx, save_dir, name_format).relative_to(save_dir))
+                    sidecar.write(json.dumps({"file_name": name, **creator.classes_from_has(row)}) + "\n")
         if files is not None:   # encoded on the device: the host only writes buffer[i, :sizes[i]]
             buffer, sizes, encoded = files
             encoded.synchronize()
@@ -255,8 +287,14 @@ def build_dataset(args, creation_config, rank=0, world_size=1):
             extra = {} if cluster_segmenter is None else {"cluster_segmenter": cluster_segmenter}
             pixels, labels, ready = label_and_encode(image, acts, catalogs, dataset_gan, **extra)
             # device encoder: label image, PNG files and their copy to pinned memory follow the label pass on its stream
-            files = encode_pairs_on_device(pixels, lambda: label_image_on_device(pixels, labels), ready) if on_device else None
-            job = (a, pixels, labels, ready, files)
+            label_image, listed = (lambda: label_image_on_device(pixels, labels)), None
+            if listing is not None:   # the class listing follows the label image on the same stream; the label image is built once
+                lab, has, listed_event = list_classes_on_device(pixels, label_image, listing[0].colours, ready)
+                label_image, listed = (lambda: lab), (has, listed_event)
+                if ready is not None:
+                    ready = listed_event   # later on the same stream: flush waits once, as before
+            files = encode_pairs_on_device(pixels, label_image, ready) if on_device else None
+            job = (a, pixels, labels, ready, files, listed)
             if pending is not None:
                 flush(pending)
             pending = job
@@ -270,37 +308,68 @@ def build_dataset(args, creation_config, rank=0, world_size=1):
     finally:
         if writers is not None:
             writers.close()   # drained here: before the caller writes the split files, and on every way out
+        if listing is not None:
+            listing[1].close()
     torch.cuda.synchronize()
     args.dropped_image_ids = dropped   # the labeller's drop decisions of this rank (empty without a cluster-based labeller)
     return done, (lo, hi)
 
 
-def create_train_val_split(image_save_base_dir: Path, seed: int):
-    """train.json / val.json below ``image_save_base_dir``: seeded shuffle of its PNGs, the first 90 % train, the rest validation."""
+def read_class_listings(image_save_base_dir: Path) -> dict:
+    """file name -> its ``has_<class>`` keys, from the sidecars the ranks of a ``--ground-truth`` run left."""
+    listed = {}
+    for sidecar in sorted(Path(image_save_base_dir).glob(CLASS_LISTING.format(rank='*'))):
+        with sidecar.open() as f:
+            for line in f:
+                if line.strip():
+                    entry = json.loads(line)
+                    listed[entry.pop("file_name")] = entry
+    return listed
+
+
+def create_train_val_split(image_save_base_dir: Path, seed: int, ground_truth=None):
+    """train.json / val.json below ``image_save_base_dir``: seeded shuffle of its PNGs, the first 90 % train, the rest validation.
+    ``ground_truth`` (a COCOGtCreator rooted at the directory): every entry also carries the image's ``has_<class>`` keys -- from
+    the sidecars of the run where they cover the file, from its PNG otherwise -- and ``coco_gt.json`` is written for the
+    validation images in ``val.json`` order (the reference's :180-206)."""
     image_save_base_dir = Path(image_save_base_dir)
     generated_images = sorted(image_save_base_dir.glob('**/*.png'))
     random.seed(seed)
     random.shuffle(generated_images)
     n_train = len(generated_images) * 9 // 10   # nine tenths train, the rest validation (floor, as int(0.9 n))
     parts = {'train.json': generated_images[:n_train], 'val.json': generated_images[n_train:]}
+    classes = {}
+    if ground_truth is not None:
+        keys = {f"has_{name}" for _, name, _ in ground_truth.annotated}
+        classes = {name: entry for name, entry in read_class_listings(image_save_base_dir).items() if set(entry) == keys}
+        missing = [path for path in generated_images if str(path.relative_to(image_save_base_dir)) not in classes]
+        for path, entry in zip(missing, ground_truth.determine_classes_in_images(missing)):
+            classes[str(path.relative_to(image_save_base_dir))] = entry
     for name, paths in parts.items():
         with (image_save_base_dir / name).open('w') as f:
-            json.dump([{"file_name": str(path.relative_to(image_save_base_dir))} for path in paths], f)
+            json.dump([{"file_name": str(path.relative_to(image_save_base_dir)), **classes.get(str(path.relative_to(image_save_base_dir)), {})}
+                       for path in paths], f)
+    if ground_truth is not None:
+        with (image_save_base_dir / 'coco_gt.json').open('w') as f:
+            json.dump(ground_truth.create_coco_gt_from_image_paths(parts['val.json']), f)
     return len(parts['train.json']), len(parts['val.json'])
 
 
 def main(args):
     creation_config = json.load(open(args.config)) if args.config else {}
     rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))
+    with_gt = {}
+    if getattr(args, 'ground_truth', False) and args.save_to:
+        with_gt = {"ground_truth": ground_truth_creator(creation_config, args.save_to)}
     if getattr(args, 'only_create_train_val_split', False):
         if not args.save_to:
             raise ValueError('--only-create-train-val-split needs --save-to (the directory that holds the PNG pairs)')
-        n_train, n_val = create_train_val_split(Path(args.save_to), creation_config.get('seed', 1))
+        n_train, n_val = create_train_val_split(Path(args.save_to), creation_config.get('seed', 1), **with_gt)
         print(f"split: {n_train} training and {n_val} validation images", flush=True)
         return
     done, (lo, hi) = build_dataset(args, creation_config, rank, world)
     if args.save_to and world == 1:
-        create_train_val_split(Path(args.save_to), creation_config.get('seed', 1))
+        create_train_val_split(Path(args.save_to), creation_config.get('seed', 1), **with_gt)
     elif args.save_to and rank == 0:   # no collective in this tool: the other ranks may still be writing
         print("several ranks: train.json / val.json are NOT written; run --only-create-train-val-split once all ranks are done",
               flush=True)
@@ -329,6 +398,8 @@ def build_parser():
                         "and the host only writes them")
     parser.add_argument("--png-writers", type=png_writer_count, default=4, help="file-writer threads of --png-encoder device "
                         "(clamped to 1..8)")
+    parser.add_argument("--ground-truth", action='store_true', default=False, help="also write the has_<class> keys of train.json / "
+                        "val.json and coco_gt.json for the validation images (needs class_to_color_map in the config)")
     parser.add_argument("-ssd", "--semantic-segmentation-base-dir", type=Path, help="directory that holds catalogs/ and "
                         "merged_classes_K.json, as create_semantic_segmentation.py and the annotation step leave it")
     return parser

@@ -184,3 +184,5 @@ extern "C" int sis_remove_small_contours(float* out, const float* pred, void* wo
     SIS_CHECK_LAUNCH("contour_apply_kernel");
     return 0;
 }
+
+#include "coco_gt.h"   // the dataset's ground truth: region tables and COCO run lengths on the same labelling kernels

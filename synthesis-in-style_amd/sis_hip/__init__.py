@@ -216,6 +216,8 @@ _SIGNATURES = {
     "sis_psnr_ssim_workspace_bytes": ([_i] * 4, _i64),
     "sis_psnr_ssim": ([_vp] * 5 + [_i] * 5 + [_f, _i, _vp, _i64, _vp], _i),
     "sis_autoencoder_batch": ([_vp] * 8 + [_i64, _i, _i, _vp], _i),
+    "sis_label_regions_workspace_bytes": ([_i, _i, _i], _i64),
+    "sis_label_regions": ([_vp] * 7 + [_i] * 5 + [_vp, _i64, _vp], _i),
 }
 
 
@@ -3446,3 +3448,57 @@ def autoencoder_batch(images, ids, scale, per_channel, seed, grey):
                        lambda: lib().sis_autoencoder_batch(_ptr(inp), _ptr(out), _ptr(images), _ptr(ids), _ptr(scale), _ptr(per_channel),
                                                            _ptr(seed), _ptr(grey), n, b, size, _stream())), "sis_autoencoder_batch")
     return inp, out
+
+
+# ------------------------------------------------------------------------------ dataset ground truth (csrc/coco_gt.h)
+
+LabelRegions = collections.namedtuple("LabelRegions", "has region_count regions run_total runs")
+LABEL_REGIONS_MAX_CLASSES = 8
+
+
+def label_regions_capacity(p):
+    """(max_regions, max_runs) of the worst cases (DESIGN.md §16.1): an aligned 2x2 block holds pixels of one region at most;
+    p*p + 1 counts and one more per region."""
+    regions = ((int(p) + 1) // 2) ** 2
+    return regions, int(p) * int(p) + 1 + regions
+
+
+def label_regions(label, colours, runs=True, max_regions=None, max_runs=None):
+    """uint8 [B, p, p, 3] label images (device) and the annotated classes' colours (host, [K][3] integers) -> a ``LabelRegions``
+    of device tensors: ``has`` uint8 [B, K], ``region_count`` and ``run_total`` int32 [B, K] (the true numbers),
+    ``regions`` int32 [B, K, max_regions, 8] with rows (root, x0, y0, w, h, area, run_offset, run_count) in ascending root order,
+    ``runs`` int32 [B, K, max_runs]: COCO's uncompressed column-major run lengths of every region that is not a straight
+    stroke, region after region.  ``runs=False`` is the listing mode (``runs`` is None, the table is still complete);
+    ``max_regions=0`` stores no rows (``regions`` is None).  The capacities default to what no plane can exceed.  Fixed launch
+    sequence on the current stream, no host sync."""
+    require_device(label, "label")
+    if label.dtype != torch.uint8 or label.dim() != 4 or label.shape[3] != 3 or label.shape[1] != label.shape[2] or label.shape[0] < 1 \
+            or label.shape[1] < 1:
+        raise RuntimeError(f"label_regions: uint8 [B, p, p, 3] label images are needed, got {label.dtype} {tuple(label.shape)}")
+    flat = [int(v) for colour in colours for v in colour]
+    k = len(flat) // 3
+    if k < 1 or k > LABEL_REGIONS_MAX_CLASSES or len(flat) != 3 * k or any(len(colour) != 3 for colour in colours) \
+            or any(not 0 <= v <= 255 for v in flat):
+        raise RuntimeError(f"label_regions: 1..{LABEL_REGIONS_MAX_CLASSES} colours of three bytes are needed, got {colours!r}")
+    label = label.contiguous()
+    b, p = label.shape[0], label.shape[1]
+    worst_regions, worst_runs = label_regions_capacity(p)
+    max_regions = worst_regions if max_regions is None else int(max_regions)
+    max_runs = worst_runs if max_runs is None else int(max_runs)
+    if max_regions < 0 or max_runs < 0:
+        raise RuntimeError("label_regions: negative capacity")
+    dev = label.device
+    has = torch.empty((b, k), dtype=torch.uint8, device=dev)
+    region_count = torch.empty((b, k), dtype=torch.int32, device=dev)
+    run_total = torch.empty((b, k), dtype=torch.int32, device=dev)
+    regions = torch.empty((b, k, max_regions, 8), dtype=torch.int32, device=dev) if max_regions > 0 else None
+    counts = torch.empty((b, k, max_runs), dtype=torch.int32, device=dev) if runs else None
+    ws_bytes = int(lib().sis_label_regions_workspace_bytes(b, k, p))
+    ws = torch.empty(((max(ws_bytes, 4) + 3) // 4,), dtype=torch.int32, device=dev)
+    c_colours = (ctypes.c_uint8 * (3 * k))(*flat)
+    with torch.cuda.device(dev):
+        _check(_launch("gt_stats_kernel", 0.0, 3.0 * label.numel() + 30.0 * b * k * p * p,
+                       lambda: lib().sis_label_regions(_ptr(has), _ptr(region_count), _ptr(regions), _ptr(run_total), _ptr(counts),
+                                                       _ptr(label), c_colours, k, b, p, max_regions, max_runs, _ptr(ws),
+                                                       ws.numel() * 4, _stream())), "sis_label_regions")
+    return LabelRegions(has, region_count, regions, run_total, counts)

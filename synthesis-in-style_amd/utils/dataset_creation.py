@@ -125,3 +125,21 @@ def encode_pairs_on_device(pixels: torch.Tensor, label_image, ready: Optional[to
         host_buffer.copy_(buffer, non_blocking=True)
         host_sizes.copy_(sizes, non_blocking=True)
         return host_buffer, host_sizes, stream.record_event()
+
+
+def list_classes_on_device(pixels: torch.Tensor, label_image, colours, ready: Optional[torch.cuda.Event] = None):
+    """Which annotated classes every label image holds (the reference's determine_classes_in_image,
+    segmentation/evaluation/coco_gt.py:51-65): ``sis_hip.label_regions`` in listing mode on the uint8 [B, p, p, 3] label images
+    that the callable ``label_image`` builds on the device, and its ``has`` bytes copied to PINNED host memory.  Issued like
+    ``encode_pairs_on_device``: with ``ready`` (the event ``label_and_encode`` returned) on the label side stream, behind the
+    label pass; without one on the current stream.  Returns (label images, has uint8 [B, K] host, event): synchronise on the
+    event before reading ``has``; the event also stands for the label pass before it."""
+    device = pixels.device
+    side = _LABEL_STREAMS.get(device) if ready is not None else None
+    stream = side if side is not None else torch.cuda.current_stream(device)
+    with torch.cuda.stream(stream):
+        labels = label_image()
+        has = sis_hip.label_regions(labels, colours, runs=False, max_regions=0).has
+        host_has = torch.empty(has.shape, dtype=torch.uint8, pin_memory=True)
+        host_has.copy_(has, non_blocking=True)
+        return labels, host_has, stream.record_event()
