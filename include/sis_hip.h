@@ -159,6 +159,29 @@ int sis_modconv2d_wino24_rgb(float* out, float* rgb_part, const float* x, const 
 int sis_rgb_finish(float* out, const float* part, const float* bias, const float* skip, const float* taps, int batch, int blocks,
                    int cout, int h, int width, int kh, int kw, int pad0, int pad1, void* stream);
 
+/* The same stride-1 3x3 layers with bf16 operands on the bf16 matrix cores (csrc/modconv_bf16.h; opt-in, the default route is
+ * fp32): model.py:272-276 (+ :287-292, fused_act.py:85-86 when fuse_act != 0) with both operands rounded,
+ *   y[b,co,h,w] = dscale[b,co] * sum_{ci,kh,kw} bf16(w[co,ci,kh,kw]) * bf16(fl32(s[b,ci] * x[b,ci,h+kh-1,w+kw-1]))
+ *   fuse_act:  y = lrelu_{0.2}(y + noise_weight[0]*noise[nb,0,h,w] + bias[co]) * sqrt(2)      (as sis_modconv2d, in fp32)
+ * Both conversions round to nearest even; the style product is formed in fp32 and rounded once; the weight is the raw
+ * parameter rounded once (the conv scale stays in dscale); accumulation, dscale, noise, bias and the tail are fp32; x and out
+ * are fp32.  No atomics, no split-K: a sample's result depends on neither the batch nor the launch plan.
+ * sis_modconv_bf16_eligible (model.py:272-276, :287-292) depends on (cin, cout, h, w) only, never on the batch: cin % 8 == 0
+ * (a last half-empty chunk of 16 channels is padded with zeros), cin <= 1024, cout % 64 == 0, w % 4 == 0 (16-byte row loads),
+ * w >= 32 and h * w >= 256 (one whole tile of 256 pixels: 4 x 64, or 8 x 32 on maps up to 32 wide; h itself is free) and fewer than 2^31
+ * elements per sample on either side.
+ * sis_modconv_bf16_packed_elems (model.py:272-276, :287-292): bf16 elements of the packed weight image of a cin -> cout layer
+ * (-1: no such layer); sis_modconv_prepack_bf16 (model.py:272-276, :287-292) writes it from w [cout][cin][3][3], once per
+ * checkpoint: [cout tile of 128 (cout >= 128) or 64][chunk of 16 channels][tap][row][swizzled 8-channel unit][8], private to
+ * the kernel.  sis_modconv2d_bf16 (model.py:272-276, :287-292): the operands of sis_modconv2d_wino24 with that image in place
+ * of u24; x and packed 16-byte aligned. */
+int sis_modconv_bf16_eligible(int cin, int cout, int h, int w);
+int64_t sis_modconv_bf16_packed_elems(int cin, int cout);
+int sis_modconv_prepack_bf16(void* packed, const float* w, int cout, int cin, void* stream);
+int sis_modconv2d_bf16(float* out, const float* x, const void* packed, const float* s, const float* dscale,
+                       const float* noise, int64_t noise_batch_stride, const float* noise_weight, const float* bias,
+                       int batch, int cin, int cout, int h, int w, int fuse_act, void* stream);
+
 /* Modulated transposed convolution, stride 2, no padding, ks = 3: model.py:251-261 up to (not
  * including) the Blur: t[b,co,p,q] = dscale[b,co] * sum_{ci, 2h+kh=p, 2w+kw=q} wpk[ci][kh*3+kw][co]
  * * s[b,ci] * x[b,ci,h,w];  t is [B, Cout, 2H+1, t_row_stride] with the first 2W+1 floats of every row

@@ -141,6 +141,26 @@ def load_generator(checkpoint, size, latent_size, n_mlp, channel_multiplier, dev
     return g.to(device).eval()
 
 
+GENERATOR_PRECISIONS = ("fp32", "bf16")
+
+
+def add_generator_precision_argument(parser):
+    parser.add_argument("--generator-precision", choices=GENERATOR_PRECISIONS, default="fp32",
+                        help="fp32: every generator layer on the fp32 kernels (the parity contract); bf16: the stride-1 3x3 "
+                             "layers round their operands to bf16 and accumulate in fp32 (faster, images differ slightly)")
+
+
+def apply_generator_precision(g, args):
+    """--generator-precision on a loaded generator; one line names the mode.  (Callers without the flag: nothing changes.)"""
+    precision = getattr(args, 'generator_precision', None)
+    if precision is None:
+        return g
+    g.set_matrix_precision(precision)
+    what = "stride-1 3x3 layers with bf16 operands, fp32 accumulation" if precision == "bf16" else "all layers fp32"
+    print(f"generator precision: {precision} ({what})", flush=True)
+    return g
+
+
 def dataset_gan_segmenter(g, classifier_path, creation_config, mean_latent, device):
     """The reference's get_dataset_gan_params + get_dataset_segmenter (:28-81): one probe forward (B = 1, before the
     dataset's seed is set) gives the activation layout, i.e. the feature size and one bilinear upsampler per layer."""
@@ -180,6 +200,7 @@ def build_dataset(args, creation_config, rank=0, world_size=1):
     torch.cuda.set_device(device)
     g = load_generator(args.checkpoint, creation_config.get('image_size', 256), creation_config.get('latent_size', 512),
                        creation_config.get('n_mlp', 8), creation_config.get('channel_multiplier', 2), device)
+    apply_generator_precision(g, args)
     catalogs = {}
     for layer, path in creation_config.get('catalogs', {}).items():  # {"13": "centres_13.npy", ...}
         catalogs[int(layer)] = FactorCatalog(cluster_centers=numpy.load(path))
@@ -402,6 +423,7 @@ def build_parser():
                         "val.json and coco_gt.json for the validation images (needs class_to_color_map in the config)")
     parser.add_argument("-ssd", "--semantic-segmentation-base-dir", type=Path, help="directory that holds catalogs/ and "
                         "merged_classes_K.json, as create_semantic_segmentation.py and the annotation step leave it")
+    add_generator_precision_argument(parser)
     return parser
 
 

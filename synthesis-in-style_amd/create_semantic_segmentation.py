@@ -28,7 +28,7 @@ import numpy
 import torch
 
 import sis_hip
-from create_dataset_for_segmentation import load_generator
+from create_dataset_for_segmentation import add_generator_precision_argument, apply_generator_precision, load_generator
 from segmentation.gan_local_edit.spherical_kmeans import MiniBatchSphericalKMeans
 from utils.dataset_creation import seeded_latents
 
@@ -177,6 +177,7 @@ def main(args):
         torch.cuda.set_device(device)
         dest = prepare_output_dir(args)
         g = load_generator(args.checkpoint, args.image_size, args.latent_size, args.n_mlp, args.channel_multiplier, device)
+        apply_generator_precision(g, args)
         activations, images = get_activations(args, g, device)
     if not activations:
         raise ValueError("no activation layer is left after --strip-activations-from")
@@ -212,6 +213,7 @@ def build_parser():
     parser.add_argument("--channel-multiplier", type=int, default=2)
     parser.add_argument("--seed", type=int, default=1, help="seed of the latent stream")
     parser.add_argument("--random-state", type=int, default=0, help="seed of the fit plans")
+    add_generator_precision_argument(parser)
     return parser
 
 

@@ -634,3 +634,6 @@ extern "C" int sis_weight_std_bwd_multi(const void* table, const void* const* gr
     }
     return 0;
 }
+
+// The generator's opt-in bf16 modulated convolution: same tiles, staging and weight image, fp32 activations in and out.
+#include "modconv_bf16.h"

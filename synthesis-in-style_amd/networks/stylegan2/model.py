@@ -123,6 +123,9 @@ class EqualLinear(nn.Module):
         return f'{self.__class__.__name__}({self.weight.shape[1]}, {self.weight.shape[0]})'
 
 
+MATRIX_PRECISIONS = ("fp32", "bf16")
+
+
 class ModulatedConv2d(nn.Module):
     def __init__(self, in_channel, out_channel, kernel_size, style_dim, demodulate=True, upsample=False,
                  downsample=False, blur_kernel=[1, 3, 3, 1]):
@@ -148,6 +151,7 @@ class ModulatedConv2d(nn.Module):
         self.modulation = EqualLinear(style_dim, in_channel, bias_init=1)
         self._pack = None
         self._pack_key = None
+        self.matrix_precision = None   # None: SIS_GEN_PRECISION decides (default fp32); see set_matrix_precision
 
     def __repr__(self):
         return (f'{self.__class__.__name__}({self.in_channel}, {self.out_channel}, {self.kernel_size}, '
@@ -167,6 +171,11 @@ class ModulatedConv2d(nn.Module):
             # SIS_WINO24=0 F(2x2,3x3) wherever a Winograd kernel runs (bisecting / A-B runs); both are read here, per pack.
             self._wino = self._wino24 = None
             self._wino_on, self._wino24_on = self._winograd_switches()
+            # the opt-in bf16 matrix-core route of the same layers (csrc/modconv_bf16.h): SIS_GEN_PRECISION=bf16, or
+            # Generator.set_matrix_precision; read here, per pack, like the Winograd switches.  Its weight image is packed at
+            # first use too.  The default, fp32, leaves every layer on the path it had.
+            self._bf16 = None
+            self._bf16_on = self._bf16_switch()
             # up-convolutions keep the 16 transformed planes of the fast-FIR kernel (25 instead of 36 multiplies per 2 x 2
             # input positions, csrc/modconv_upfir.hip); the launch falls back to the 4-phase kernel below 32 x 32
             self._fir = None
@@ -180,8 +189,33 @@ class ModulatedConv2d(nn.Module):
                 and self.out_channel % 4 == 0 and os.environ.get("SIS_WINOGRAD", "1") != "0")
         return wino, wino and os.environ.get("SIS_WINO24", "1") != "0"
 
+    def _bf16_switch(self):
+        p = self.matrix_precision if self.matrix_precision is not None else os.environ.get("SIS_GEN_PRECISION", "fp32")
+        if p not in MATRIX_PRECISIONS:
+            raise ValueError(f"SIS_GEN_PRECISION / set_matrix_precision: {p!r} is not one of {MATRIX_PRECISIONS}")
+        return p == "bf16" and self.kernel_size == 3 and not self.upsample and not self.downsample
+
+    def set_matrix_precision(self, precision):
+        """"fp32" / "bf16" for this layer's inference route, None: as SIS_GEN_PRECISION says.  The switch of a live pack is read
+        again and its bf16 image dropped; the fp32 operands (wpk, wsq) do not depend on the precision and stay, so that a
+        modulation plan that holds their addresses stays valid."""
+        if precision is not None and precision not in MATRIX_PRECISIONS:
+            raise ValueError(f"set_matrix_precision: {precision!r} is not one of {MATRIX_PRECISIONS}")
+        self.matrix_precision = precision
+        if self._pack_key is not None:
+            self._bf16 = None
+            self._bf16_on = self._bf16_switch()
+
+    def bf16_takes(self, h, w):
+        """Whether an h x w map of this layer runs with bf16 operands (the switch as the current pack read it)."""
+        on = self._bf16_on if self._pack_key is not None else self._bf16_switch()
+        return bool(on and sis_hip.modconv_bf16_eligible(self.in_channel, self.out_channel, h, w))
+
     def wino24_takes(self, h, w):
-        """Whether an h x w map of this layer runs on the F(2x4,3x3) kernel (the switches as the current pack read them)."""
+        """Whether an h x w map of this layer runs on the F(2x4,3x3) kernel (the switches as the current pack read them); not
+        where the layer runs with bf16 operands, so its ToRGB is then the separate sis_to_rgb pass."""
+        if self.bf16_takes(h, w):
+            return False
         on = self._wino24_on if self._pack_key is not None else self._winograd_switches()[1]
         return bool(on and sis_hip.modconv_wino24_eligible(self.in_channel, self.out_channel, h, w))
 
@@ -195,6 +229,10 @@ class ModulatedConv2d(nn.Module):
         """The keyword of sis_hip.modconv2d that carries this layer's transformed weights for an h x w map: the F(2x4,3x3) planes
         where that kernel takes (Cin, Cout, h, w) -- the batch plays no part -- and the F(2x2,3x3) planes (or None) otherwise."""
         self.packed_weights()
+        if self.bf16_takes(h, w):
+            if self._bf16 is None:
+                self._bf16 = sis_hip.modconv_prepack_bf16(self.weight.detach())
+            return {"bf16_w": self._bf16}
         if self.wino24_takes(h, w):
             if self._wino24 is None:
                 self._wino24 = sis_hip.modconv_prepack_wino24(self.weight.detach())
@@ -446,6 +484,17 @@ class Generator(nn.Module):
         cm = channel_multiplier
         return {4: 512, 8: 512, 16: 512, 32: 512, 64: 256 * cm, 128: 128 * cm, 256: 64 * cm, 512: 32 * cm,
                 1024: 16 * cm}
+
+    def set_matrix_precision(self, precision):
+        """"fp32" (the default route, bit for bit) or "bf16": the stride-1 3x3 layers that sis_hip.modconv_bf16_eligible takes
+        run their inference route with bf16 operands and fp32 accumulation; None: as SIS_GEN_PRECISION says.
+        Set on every modulated convolution; their packs are dropped and rebuilt at the next forward."""
+        for m in self.modules():
+            if isinstance(m, ModulatedConv2d):
+                m.set_matrix_precision(precision)
+                m._pack = m._pack_key = None
+        self._plan_key = None   # the modulation plan holds addresses inside the dropped packs
+        return self
 
     def make_noise(self) -> typing.List[torch.Tensor]:
         device = self.input.input.device

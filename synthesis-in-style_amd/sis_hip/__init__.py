@@ -52,6 +52,10 @@ _SIGNATURES = {
     "sis_modconv2d_wino24": ([_vp] * 6 + [_i64, _vp, _vp] + [_i] * 7 + [_vp], _i),
     "sis_modconv2d_wino24_rgb": ([_vp] * 7 + [_i64, _vp, _vp, _vp, _vp, _f] + [_i] * 7 + [_vp], _i),
     "sis_rgb_finish": ([_vp] * 5 + [_i] * 9 + [_vp], _i),
+    "sis_modconv_bf16_eligible": ([_i] * 4, _i),
+    "sis_modconv_bf16_packed_elems": ([_i] * 2, _i64),
+    "sis_modconv_prepack_bf16": ([_vp, _vp, _i, _i, _vp], _i),
+    "sis_modconv2d_bf16": ([_vp] * 6 + [_i64, _vp, _vp] + [_i] * 6 + [_vp], _i),
     "sis_last_kernel": ([], ctypes.c_char_p),
     "sis_conv3x3_prepack": ([_vp, _vp, _i, _i, _i, _vp], _i),
     "sis_conv3x3_prepack_both": ([_vp, _vp, _vp, _i, _i, _vp], _i),
@@ -567,6 +571,30 @@ def modconv_wino24_eligible(cin, cout, h, w):
     return bool(lib().sis_modconv_wino24_eligible(int(cin), int(cout), int(h), int(w)))
 
 
+BF16_KERNEL = "modconv_bf16_kernel"
+
+
+def modconv_bf16_eligible(cin, cout, h, w):
+    """True when the bf16 matrix-core kernel takes a stride-1 3x3 layer of this shape; the batch size plays no part."""
+    return bool(lib().sis_modconv_bf16_eligible(int(cin), int(cout), int(h), int(w)))
+
+
+def modconv_prepack_bf16(weight):
+    """[1, Cout, Cin, 3, 3] -> the bf16 weight image of the bf16 modulated convolution (the raw parameter rounded once to
+    nearest even, in the kernel's private tile order), a flat bfloat16 tensor."""
+    w = _f32(weight, "weight")
+    _, cout, cin, k, _ = w.shape
+    if k != 3:
+        raise RuntimeError("the bf16 modulated convolution is for 3x3 kernels")
+    n = lib().sis_modconv_bf16_packed_elems(cin, cout)
+    if n <= 0:
+        raise RuntimeError(f"modconv_prepack_bf16: no bf16 weight image for {cin} -> {cout} channels")
+    packed = torch.empty((n,), dtype=torch.bfloat16, device=w.device)
+    with torch.cuda.device(w.device):
+        _check(lib().sis_modconv_prepack_bf16(_ptr(packed), _ptr(w), cout, cin, _stream()), "sis_modconv_prepack_bf16")
+    return packed
+
+
 def conv3x3_supported(x, weight, dilation=1):
     """True when the plain Winograd path takes this layer in both directions (forward and data gradient): 3x3
     kernel, float32 NCHW; a dilation d is run as d*d independent convolutions of the stride-d sub-images, so the
@@ -960,8 +988,11 @@ def rgb_part_shape(batch, cout, h, w):
 
 
 def modconv2d(x, wpk, s, dscale, ksize, noise=None, noise_weight=None, bias=None, fuse_act=False, wino_u=None, out=None,
-              wino24_u=None, wino24_tiles_per_wg=0, rgb=None):
-    """``wino24_u`` (modconv_prepack_wino24): the layer runs on the F(2x4,3x3) kernel where modconv_wino24_eligible says so,
+              wino24_u=None, wino24_tiles_per_wg=0, rgb=None, bf16_w=None):
+    """``bf16_w`` (modconv_prepack_bf16): the layer runs with bf16 operands on the bf16 matrix cores where modconv_bf16_eligible
+    says so, whatever the batch (not together with ``rgb``); other shapes take the path they took without it.
+
+    ``wino24_u`` (modconv_prepack_wino24): the layer runs on the F(2x4,3x3) kernel where modconv_wino24_eligible says so,
     whatever the batch; other shapes take the path they took without it.  ``wino24_tiles_per_wg``: tests only.
 
     ``rgb`` = (weight [3 * Cout], s_rgb [B, Cout], scale, part): the F(2x4,3x3) kernel also leaves the following ToRGB's channel
@@ -989,6 +1020,18 @@ def modconv2d(x, wpk, s, dscale, ksize, noise=None, noise_weight=None, bias=None
                                                                   _ptr(rgb_s), float(rgb_scale), batch, cin, cout, h, w,
                                                                   int(bool(fuse_act)), int(wino24_tiles_per_wg), _stream())),
                    "sis_modconv2d_wino24_rgb")
+        return out
+    if bf16_w is not None and rgb is None and ksize == 3 and batch > 0 and modconv_bf16_eligible(cin, cout, h, w):
+        if bf16_w.dtype != torch.bfloat16 or bf16_w.numel() != lib().sis_modconv_bf16_packed_elems(cin, cout) or not bf16_w.is_contiguous():
+            raise RuntimeError(f"modconv2d: bf16_w is not the modconv_prepack_bf16 image of a {cin} -> {cout} layer")
+        with torch.cuda.device(x.device):
+            _check(_launch(None,
+                           2.0 * batch * cout * cin * 9 * h * w,
+                           4.0 * (x.numel() + out.numel()) + 2.0 * bf16_w.numel(),
+                           lambda: lib().sis_modconv2d_bf16(_ptr(out), _ptr(x), _ptr(bf16_w), _ptr(s), _ptr(dscale), _ptr(noise),
+                                                            nbs, _ptr(noise_weight), _ptr(bias), batch, cin, cout, h, w,
+                                                            int(bool(fuse_act)), _stream())),
+                   "sis_modconv2d_bf16")
         return out
     if wino24_u is not None and ksize == 3 and batch > 0 and modconv_wino24_eligible(cin, cout, h, w):
         with torch.cuda.device(x.device):
