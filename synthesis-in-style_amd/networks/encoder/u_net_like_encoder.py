@@ -17,7 +17,8 @@ Two formulations, the same up to rounding:
   on ``sis_conv3x3`` (Winograd) and ``sis_bn_act_fwd``; each block's ``relu(bn2(.) + identity)`` with its noise head and its
   pool partials on ``sis_enc_block_tail``; all latent heads of an encode in one ``sis_enc_latent_heads`` launch.  A layer
   whose shape a kernel declines runs its ATen formulation and is counted by ``sis_hip.library_call``.  Packed weights and
-  folded vectors are built once and rebuilt when a parameter's or buffer's ``_version`` (or storage) changes.
+  folded vectors are built once and rebuilt when a parameter's or buffer's stamp (``sis_hip.weight_stamp``: storage, ``_version``,
+  the counter of writes autograd cannot see) has moved.
 """
 import math
 import os
@@ -173,7 +174,7 @@ class UNetLikeEncoder(nn.Module):
     def _state_key(self):
         if self._hip_tensors is None:   # the module tree is walked once, not per forward
             self._hip_tensors = list(self.parameters()) + list(self.buffers())
-        return tuple((t.data_ptr(), t._version) for t in self._hip_tensors)
+        return tuple(sis_hip.weight_stamp(t) for t in self._hip_tensors)
 
     def _packs(self):
         """Per block: folded BatchNorms and the Winograd images of the stride-1 layers; rebuilt when a tensor changed.  The

@@ -159,9 +159,10 @@ class ModulatedConv2d(nn.Module):
 
     # ---- MI355X path -----------------------------------------------------------------------
     def packed_weights(self):
-        """(wpk [Cin, k*k, Cout], wsq [Cout, Cin]); rebuilt when the parameter changes."""
+        """(wpk [Cin, k*k, Cout], wsq [Cout, Cin]); rebuilt when the parameter's stamp (sis_hip.weight_stamp: storage, autograd's
+        version counter, the counter of writes autograd cannot see) has moved."""
         w = self.weight
-        key = (w.data_ptr(), w._version, w.device)
+        key = sis_hip.weight_stamp(w) + (w.device,)
         if self._pack_key != key:
             self._pack = sis_hip.modconv_prepack(w.detach())
             # stride-1 3x3 layers also keep a Winograd transform of the weights: the 24 planes of F(2x4,3x3) (3x fewer MFMA
@@ -528,8 +529,10 @@ class Generator(nn.Module):
 
     def _modulation_plan(self, batch, device):
         seq = self._layer_sequence()
-        key = (batch, device) + tuple((m.conv.weight.data_ptr(), m.conv.weight._version, m.conv.modulation.weight.data_ptr(),
-                                       m.conv.modulation.bias.data_ptr()) for m, _ in seq)
+        # the rows hold addresses, no values: of the modulation parameters and, for the styled convolutions, of wsq inside the
+        # layer's pack -- so the key is those addresses, with each pack brought up to date first (a rebuilt pack moves wsq)
+        key = (batch, device) + tuple((m.conv.modulation.weight.data_ptr(), m.conv.modulation.bias.data_ptr(),
+                                       m.conv.packed_weights()[1].data_ptr() if isinstance(m, StyledConv) else 0) for m, _ in seq)
         if getattr(self, '_plan_key', None) == key:
             return self._plan
         mod_rows, dem_rows, s_off, d_off, mblocks, dblocks = [], [], 0, 0, 0, 0

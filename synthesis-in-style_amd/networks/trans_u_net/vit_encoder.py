@@ -93,7 +93,8 @@ class _Bf16Shadow:
     Who keeps it current: ``FusedSGD`` when the copy is registered there (``bind``): the optimizer launch that updates the
     fp32 master weights writes the rounded values into the copy as well.  Otherwise (plain ``torch.optim`` steps,
     ``load_state_dict``, a FusedSGD the copy was never registered with) the copy is refreshed here whenever a parameter's
-    ``_version`` -- or the raw-update counter FusedSGD bumps, since its kernel writes bypass ``_version`` -- has moved."""
+    stamp (``sis_hip.weight_stamp``: ``_version``, or the raw-update counter the fused optimizers bump, since their kernel writes
+    bypass ``_version``) has moved."""
 
     def __init__(self, params):
         self.params = list(params)
@@ -103,8 +104,8 @@ class _Bf16Shadow:
 
     def _key(self):
         if self.bound is not None and self.bound is self.buf:
-            return tuple(p._version for p in self.params)  # raw optimizer updates are mirrored into the copy by the optimizer
-        return tuple((p._version, getattr(p, '_sis_raw_updates', 0)) for p in self.params)
+            return tuple(sis_hip.weight_stamp(p, raw=False) for p in self.params)  # raw optimizer updates are mirrored into the copy by the optimizer
+        return tuple(sis_hip.weight_stamp(p) for p in self.params)
 
     def tensor(self):
         first = self.params[0]

@@ -297,6 +297,35 @@ def library_calls(reset=False):
 _own_kernels = None
 
 
+# ---------------------------------------------------------------------------------------------------- weight stamps
+# State derived from a parameter (packed weight images, folded BatchNorms, bf16 copies, tables that hold addresses inside
+# them) is current while the parameter's stamp has not moved.  ``_version`` moves with every write autograd
+# sees; a write it cannot see (a kernel of this library given ``data_ptr()``, a ``.data`` idiom) is reported by
+# ``mark_written``, which the fused optimizers call for their device steps.
+RAW_UPDATES = "_sis_raw_updates"
+
+
+def weight_stamp(t, raw=True):
+    """(data_ptr, _version, raw-update counter) of a tensor: equal stamps mean the same storage, not written in between by
+    anything that moves ``_version`` or calls ``mark_written``.  ``raw=False`` leaves the counter out (a copy that the raw
+    writer itself keeps current)."""
+    return (t.data_ptr(), t._version, getattr(t, RAW_UPDATES, 0) if raw else 0)
+
+
+def mark_written(*targets):
+    """Tell the modules that cache state derived from these tensors that their values were changed by a write autograd
+    cannot see (``p.data.mul_()``, ``_foreach`` ops on ``.data`` lists, a kernel handed ``p.data_ptr()``, a NumPy view).
+    ``targets``: tensors, modules (all their parameters and buffers) or iterables of either.  The mark lives on the tensor
+    OBJECT: pass the parameter itself, not ``p.data`` or ``p.detach()``, which are new objects."""
+    for target in targets:
+        if isinstance(target, torch.Tensor):
+            setattr(target, RAW_UPDATES, getattr(target, RAW_UPDATES, 0) + 1)
+        elif isinstance(target, torch.nn.Module):
+            mark_written(*target.parameters(), *target.buffers())
+        else:
+            mark_written(*target)
+
+
 # ---------------------------------------------------------------------------------------------------- side streams
 # HIP maps streams onto a handful of hardware queues (4 on this stack), and two streams on ONE queue run their kernels one after
 # the other.  Which pool stream lands beside the default stream's queue depends on what else created streams first: after an RCCL
@@ -537,8 +566,8 @@ def modconv_prepack(weight):
     wpk = torch.empty((cin, k * k, cout), dtype=torch.float32, device=w.device)
     wsq = torch.empty((cout, cin), dtype=torch.float32, device=w.device)
     with torch.cuda.device(w.device):
-        _check(lib().sis_modconv_prepack(_ptr(wpk), _ptr(wsq), _ptr(w), cout, cin, k, _stream()),
-               "sis_modconv_prepack")
+        _check(_launch("modconv_prepack", 0.0, 4.0 * (w.numel() + wpk.numel() + wsq.numel()),
+                       lambda: lib().sis_modconv_prepack(_ptr(wpk), _ptr(wsq), _ptr(w), cout, cin, k, _stream())), "sis_modconv_prepack")
     return wpk, wsq
 
 
@@ -550,7 +579,8 @@ def modconv_prepack_wino(weight):
         raise RuntimeError("the Winograd transform is for 3x3 kernels")
     u = torch.empty((cin, 16, cout), dtype=torch.float32, device=w.device)
     with torch.cuda.device(w.device):
-        _check(lib().sis_modconv_prepack_wino(_ptr(u), _ptr(w), cout, cin, _stream()), "sis_modconv_prepack_wino")
+        _check(_launch("modconv_prepack_wino", 0.0, 4.0 * (w.numel() + u.numel()),
+                       lambda: lib().sis_modconv_prepack_wino(_ptr(u), _ptr(w), cout, cin, _stream())), "sis_modconv_prepack_wino")
     return u
 
 
@@ -562,7 +592,8 @@ def modconv_prepack_wino24(weight):
         raise RuntimeError("the Winograd transform is for 3x3 kernels")
     u = torch.empty((cin, 2, 3, cout, 4), dtype=torch.float32, device=w.device)
     with torch.cuda.device(w.device):
-        _check(lib().sis_modconv_prepack_wino24(_ptr(u), _ptr(w), cout, cin, _stream()), "sis_modconv_prepack_wino24")
+        _check(_launch("modconv_prepack_wino24", 0.0, 4.0 * (w.numel() + u.numel()),
+                       lambda: lib().sis_modconv_prepack_wino24(_ptr(u), _ptr(w), cout, cin, _stream())), "sis_modconv_prepack_wino24")
     return u
 
 
@@ -591,7 +622,8 @@ def modconv_prepack_bf16(weight):
         raise RuntimeError(f"modconv_prepack_bf16: no bf16 weight image for {cin} -> {cout} channels")
     packed = torch.empty((n,), dtype=torch.bfloat16, device=w.device)
     with torch.cuda.device(w.device):
-        _check(lib().sis_modconv_prepack_bf16(_ptr(packed), _ptr(w), cout, cin, _stream()), "sis_modconv_prepack_bf16")
+        _check(_launch("modconv_prepack_bf16", 0.0, 4.0 * w.numel() + 2.0 * packed.numel(),
+                       lambda: lib().sis_modconv_prepack_bf16(_ptr(packed), _ptr(w), cout, cin, _stream())), "sis_modconv_prepack_bf16")
     return packed
 
 
@@ -1068,7 +1100,8 @@ def modconv_prepack_up_fir(weight):
     cout, cin = w.shape[0], w.shape[1]
     u = torch.empty((cin, 8, cout, 2), dtype=torch.float32, device=w.device)
     with torch.cuda.device(w.device):
-        _check(lib().sis_modconv_up_fir_prepack(_ptr(u), _ptr(w), cout, cin, _stream()), "sis_modconv_up_fir_prepack")
+        _check(_launch("modconv_up_fir_prepack", 0.0, 4.0 * (w.numel() + u.numel()),
+                       lambda: lib().sis_modconv_up_fir_prepack(_ptr(u), _ptr(w), cout, cin, _stream())), "sis_modconv_up_fir_prepack")
     return u
 
 
@@ -3133,7 +3166,8 @@ def enc_conv3x3_s2_pack(weight, shortcut_weight=None):
     packed = torch.empty((cin, taps, -(-cout // 64) * 64), dtype=torch.float32, device=w.device)
     assert packed.numel() == lib().sis_enc_conv3x3_s2_packed_floats(cin, cout, int(wd is not None))
     with torch.cuda.device(w.device):
-        _check(lib().sis_enc_conv3x3_s2_pack(_ptr(packed), _ptr(w), _ptr(wd), cin, cout, _stream()), "sis_enc_conv3x3_s2_pack")
+        _check(_launch("enc_conv3x3_s2_prepack", 0.0, 4.0 * (w.numel() + packed.numel()),
+                       lambda: lib().sis_enc_conv3x3_s2_pack(_ptr(packed), _ptr(w), _ptr(wd), cin, cout, _stream())), "sis_enc_conv3x3_s2_pack")
     return packed
 
 

@@ -170,8 +170,9 @@ class GradientClipAdam(Optimizer):
             raise RuntimeError("GradientClipAdam: capture needs one eager step() and a push_hyper() call first")
         if not capturing:
             self.push_hyper()
-        for _, p in entries:
-            p._sis_raw_updates = getattr(p, '_sis_raw_updates', 0) + 1
+        # the update below bypasses torch's version counter: modules that keep state derived from a parameter (packed weight
+        # images, folded BatchNorms, bf16 copies) watch this mark next to ``_version`` (sis_hip.weight_stamp)
+        sis_hip.mark_written(p for _, p in entries)
         grad_key = tuple(p.grad.data_ptr() for _, p in entries)
         if grad_key != self._grad_key or capturing:
             self._upload(entries, capturing)

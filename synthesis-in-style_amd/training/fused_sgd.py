@@ -156,10 +156,9 @@ class FusedSGD(Optimizer):
         capturing = self._on_gpu and torch.cuda.is_current_stream_capturing()
         if capturing and (fresh or self._hyper is None or self._capture_host is None):
             raise RuntimeError("FusedSGD: capture needs one eager step() and a push_hyper() call first")
-        for _, p, _, _ in entries:
-            # the update below bypasses torch's version counter: modules caching derived tensors (bf16 shadows that are
-            # NOT registered here) watch this counter next to ``param._version``
-            p._sis_raw_updates = getattr(p, '_sis_raw_updates', 0) + 1
+        # the update below bypasses torch's version counter: modules caching derived tensors (packed weight images, bf16
+        # shadows that are NOT registered here) watch this mark next to ``param._version`` (sis_hip.weight_stamp)
+        sis_hip.mark_written(p for _, p, _, _ in entries)
         grad_key = tuple(g.data_ptr() for _, _, g, _ in entries) + tuple(p.data_ptr() for _, p, _, _ in entries)
         if grad_key != self._grad_key or capturing:
             self._upload(entries, capturing)

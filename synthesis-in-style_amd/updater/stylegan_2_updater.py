@@ -61,9 +61,11 @@ class Stylegan2Updater(Updater):
         source = dict(trained_model.named_parameters())
         names = [k for k, _ in self.g_ema.named_parameters()]
         with torch.no_grad():
-            averaged = [p.data for _, p in self.g_ema.named_parameters()]
+            # on the parameters themselves, not their ``.data``: the same arithmetic, and each write moves the parameter's
+            # ``_version``, which is how g_ema's packed weight images learn that they are stale (sis_hip.weight_stamp)
+            averaged = [p for _, p in self.g_ema.named_parameters()]
             torch._foreach_mul_(averaged, decay)
-            torch._foreach_add_(averaged, [source[k].data for k in names], alpha=1 - decay)
+            torch._foreach_add_(averaged, [source[k].detach() for k in names], alpha=1 - decay)
 
     # ---- latents and per-layer noise --------------------------------------------------------
     def make_noise(self, batch_size: int, n_noise: int) -> Tuple[torch.Tensor, ...]:
