@@ -29,6 +29,7 @@ twice differentiable for the path-length regulariser), with ``upfirdn2d`` / ``fu
 the HIP kernels through their autograd Functions.  The discriminator half of the reference file lives
 in ``discriminator.py`` and is re-exported here.  CPU tensors are rejected with ``RuntimeError`` like the reference's extension does.
 """
+import collections
 import math
 import os
 import random
@@ -124,6 +125,13 @@ class EqualLinear(nn.Module):
 
 
 MATRIX_PRECISIONS = ("fp32", "bf16")
+# How a stride-1 3x3 layer runs an h x w map in inference (ModulatedConv2d.route), in order of precedence: bf16 operands on the
+# bf16 matrix cores (opt-in), Winograd F(2x4,3x3), Winograd F(2x2,3x3), the direct kernel.  Everything else is "direct".
+ROUTES = ("bf16", "wino24", "wino", "direct")
+# weight image of a route (and of the fast-FIR up-convolution): the keyword that carries it into sis_hip and what packs it
+_IMAGES = {"bf16": ("bf16_w", "modconv_prepack_bf16"), "wino24": ("wino24_u", "modconv_prepack_wino24"),
+           "wino": ("wino_u", "modconv_prepack_wino"), "up_fir": ("fir_u", "modconv_prepack_up_fir")}
+_Switches = collections.namedtuple("_Switches", ROUTES[:3])   # whether the layer may take each route at all
 
 
 class ModulatedConv2d(nn.Module):
@@ -151,6 +159,7 @@ class ModulatedConv2d(nn.Module):
         self.modulation = EqualLinear(style_dim, in_channel, bias_init=1)
         self._pack = None
         self._pack_key = None
+        self._images = {}
         self.matrix_precision = None   # None: SIS_GEN_PRECISION decides (default fp32); see set_matrix_precision
 
     def __repr__(self):
@@ -165,36 +174,25 @@ class ModulatedConv2d(nn.Module):
         key = sis_hip.weight_stamp(w) + (w.device,)
         if self._pack_key != key:
             self._pack = sis_hip.modconv_prepack(w.detach())
-            # stride-1 3x3 layers also keep a Winograd transform of the weights: the 24 planes of F(2x4,3x3) (3x fewer MFMA
-            # FLOPs) for the map sizes that kernel takes, the 16 planes of F(2x2,3x3) (2.25x fewer) for the others.  Which of the
-            # two a layer needs depends on the map it is called with, so each is packed at its first use (winograd_operand)
-            # and a layer holds no planes it never runs on.  SIS_WINOGRAD=0 selects the direct kernel everywhere,
-            # SIS_WINO24=0 F(2x2,3x3) wherever a Winograd kernel runs (bisecting / A-B runs); both are read here, per pack.
-            self._wino = self._wino24 = None
-            self._wino_on, self._wino24_on = self._winograd_switches()
-            # the opt-in bf16 matrix-core route of the same layers (csrc/modconv_bf16.h): SIS_GEN_PRECISION=bf16, or
-            # Generator.set_matrix_precision; read here, per pack, like the Winograd switches.  Its weight image is packed at
-            # first use too.  The default, fp32, leaves every layer on the path it had.
-            self._bf16 = None
-            self._bf16_on = self._bf16_switch()
-            # up-convolutions keep the 16 transformed planes of the fast-FIR kernel (25 instead of 36 multiplies per 2 x 2
-            # input positions, csrc/modconv_upfir.hip); the launch falls back to the 4-phase kernel below 32 x 32
-            self._fir = None
-            if self.kernel_size == 3 and self.upsample and self.in_channel % 8 == 0 and self.out_channel % 64 == 0:
-                self._fir = sis_hip.modconv_prepack_up_fir(w.detach())
+            # The other images of the weights (_IMAGES) are packed at first use (operand), so a layer holds none it never runs
+            # on: which route a stride-1 3x3 layer takes depends on the map it is called with.  The switches are read here, per
+            # pack, and held with it.
+            self._images = {}
+            self._switches = self._read_switches()
             self._pack_key = key
         return self._pack
 
-    def _winograd_switches(self):
-        wino = (self.kernel_size == 3 and not self.upsample and not self.downsample and self.in_channel % 8 == 0
-                and self.out_channel % 4 == 0 and os.environ.get("SIS_WINOGRAD", "1") != "0")
-        return wino, wino and os.environ.get("SIS_WINO24", "1") != "0"
-
-    def _bf16_switch(self):
+    def _read_switches(self):
+        """SIS_GEN_PRECISION=bf16 (or set_matrix_precision) opts the stride-1 3x3 layers into the bf16 matrix-core route
+        (csrc/modconv_bf16.h); the default, fp32, leaves every layer on the path it had.  SIS_WINOGRAD=0 selects the direct
+        kernel everywhere, SIS_WINO24=0 F(2x2,3x3) wherever a Winograd kernel runs (bisecting / A-B runs)."""
         p = self.matrix_precision if self.matrix_precision is not None else os.environ.get("SIS_GEN_PRECISION", "fp32")
         if p not in MATRIX_PRECISIONS:
             raise ValueError(f"SIS_GEN_PRECISION / set_matrix_precision: {p!r} is not one of {MATRIX_PRECISIONS}")
-        return p == "bf16" and self.kernel_size == 3 and not self.upsample and not self.downsample
+        stride1 = self.kernel_size == 3 and not self.upsample and not self.downsample
+        wino = (stride1 and self.in_channel % 8 == 0 and self.out_channel % 4 == 0
+                and os.environ.get("SIS_WINOGRAD", "1") != "0")
+        return _Switches(bf16=stride1 and p == "bf16", wino24=wino and os.environ.get("SIS_WINO24", "1") != "0", wino=wino)
 
     def set_matrix_precision(self, precision):
         """"fp32" / "bf16" for this layer's inference route, None: as SIS_GEN_PRECISION says.  The switch of a live pack is read
@@ -204,45 +202,49 @@ class ModulatedConv2d(nn.Module):
             raise ValueError(f"set_matrix_precision: {precision!r} is not one of {MATRIX_PRECISIONS}")
         self.matrix_precision = precision
         if self._pack_key is not None:
-            self._bf16 = None
-            self._bf16_on = self._bf16_switch()
+            self._images.pop("bf16", None)
+            self._switches = self._switches._replace(bf16=self._read_switches().bf16)
+
+    def route(self, h, w):
+        """The one of ROUTES an h x w map of this layer runs on: the switches as the current pack read them (afresh where there
+        is no pack), then the library's own eligibility answers -- the batch plays no part."""
+        on = self._switches if self._pack_key is not None else self._read_switches()
+        if on.bf16 and sis_hip.modconv_bf16_eligible(self.in_channel, self.out_channel, h, w):
+            return "bf16"
+        if on.wino24 and sis_hip.modconv_wino24_eligible(self.in_channel, self.out_channel, h, w):
+            return "wino24"
+        return "wino" if on.wino else "direct"
 
     def bf16_takes(self, h, w):
-        """Whether an h x w map of this layer runs with bf16 operands (the switch as the current pack read it)."""
-        on = self._bf16_on if self._pack_key is not None else self._bf16_switch()
-        return bool(on and sis_hip.modconv_bf16_eligible(self.in_channel, self.out_channel, h, w))
+        """Whether an h x w map of this layer runs with bf16 operands."""
+        return self.route(h, w) == "bf16"
 
     def wino24_takes(self, h, w):
-        """Whether an h x w map of this layer runs on the F(2x4,3x3) kernel (the switches as the current pack read them); not
-        where the layer runs with bf16 operands, so its ToRGB is then the separate sis_to_rgb pass."""
-        if self.bf16_takes(h, w):
-            return False
-        on = self._wino24_on if self._pack_key is not None else self._winograd_switches()[1]
-        return bool(on and sis_hip.modconv_wino24_eligible(self.in_channel, self.out_channel, h, w))
+        """Whether an h x w map of this layer runs on the F(2x4,3x3) kernel; not where it runs with bf16 operands, so its ToRGB
+        is then the separate sis_to_rgb pass."""
+        return self.route(h, w) == "wino24"
 
-    def wino_weights(self):
+    def _image(self, name):
         self.packed_weights()
-        if self._wino is None and self._wino_on:
-            self._wino = sis_hip.modconv_prepack_wino(self.weight.detach())
-        return self._wino
+        if name not in self._images:
+            self._images[name] = getattr(sis_hip, _IMAGES[name][1])(self.weight.detach())
+        return self._images[name]
+
+    def operand(self, route):
+        """The keyword of sis_hip.modconv2d that carries the weights in the form ``route`` runs on, packed at first use; none
+        for "direct"."""
+        return {} if route == "direct" else {_IMAGES[route][0]: self._image(route)}
 
     def winograd_operand(self, h, w):
-        """The keyword of sis_hip.modconv2d that carries this layer's transformed weights for an h x w map: the F(2x4,3x3) planes
-        where that kernel takes (Cin, Cout, h, w) -- the batch plays no part -- and the F(2x2,3x3) planes (or None) otherwise."""
-        self.packed_weights()
-        if self.bf16_takes(h, w):
-            if self._bf16 is None:
-                self._bf16 = sis_hip.modconv_prepack_bf16(self.weight.detach())
-            return {"bf16_w": self._bf16}
-        if self.wino24_takes(h, w):
-            if self._wino24 is None:
-                self._wino24 = sis_hip.modconv_prepack_wino24(self.weight.detach())
-            return {"wino24_u": self._wino24}
-        return {"wino_u": self.wino_weights()}
+        """``operand`` of the route an h x w map runs on."""
+        return self.operand(self.route(h, w))
 
     def fir_weights(self):
-        self.packed_weights()
-        return self._fir
+        """The "up_fir" image: the 16 transformed planes of the fast-FIR up-convolution (25 instead of 36 multiplies per 2 x 2
+        input positions, csrc/modconv_upfir.hip), None where that kernel does not take the layer."""
+        if self.kernel_size == 3 and self.upsample and self.in_channel % 8 == 0 and self.out_channel % 64 == 0:
+            return self._image("up_fir")
+        return None
 
     def hip_supported(self):
         return (not self.downsample) and (self.kernel_size == 3 or (self.kernel_size == 1 and not self.upsample))
@@ -354,10 +356,10 @@ class StyledConv(nn.Module):
         wpk, s, dscale = conv.modulate(style)
         return self.forward_s(input, wpk, s, dscale, noise)
 
-    def forward_s(self, input, wpk, s, dscale, noise=None, out=None, rgb=None):
-        """Fused layer given the already computed style vector ``s`` [B,Cin] and epilogue factors [B,Cout].  ``out`` (stride-1
-        layers): result tensor to write into.  ``rgb`` (layers that ``conv.wino24_takes``): ``ToRGB.fused_operands`` of the
-        ToRGB that follows; the convolution leaves its channel sum for ``ToRGB.finish_s``."""
+    def forward_s(self, input, wpk, s, dscale, noise=None, rgb=None, route=None):
+        """Fused layer given the already computed style vector ``s`` [B,Cin] and epilogue factors [B,Cout].  ``rgb`` (layers on
+        the "wino24" route): ``ToRGB.fused_operands`` of the ToRGB that follows; the convolution leaves its channel sum for
+        ``ToRGB.finish_s``.  ``route`` (stride-1 layers): ``conv.route(h, w)`` where the caller has asked already."""
         conv, act = self.conv, self.activate
         b, _, h, w = input.shape
         if conv.upsample:
@@ -373,7 +375,7 @@ class StyledConv(nn.Module):
         if noise is None:
             noise = input.new_empty(b, 1, h, w).normal_()
         return sis_hip.modconv2d(input, wpk, s, dscale, conv.kernel_size, noise, self.noise.weight, act.bias,
-                                 fuse_act=True, out=out, rgb=rgb, **conv.winograd_operand(h, w))
+                                 fuse_act=True, rgb=rgb, **conv.operand(route or conv.route(h, w)))
 
 
 class ToRGB(nn.Module):
@@ -392,15 +394,14 @@ class ToRGB(nn.Module):
         sis_hip.require_device(input, "input")
         return self.forward_s(input, conv.modulation(style), skip)
 
-    def forward_s(self, input, s, skip=None, out=None):
-        """``out``: result tensor to write into (a batch slice of the image: Generator.forward's tail)."""
+    def forward_s(self, input, s, skip=None):
         conv = self.conv
         if skip is None:
-            return sis_hip.to_rgb(input, conv.weight, s, self.bias, conv.scale, out=out)
+            return sis_hip.to_rgb(input, conv.weight, s, self.bias, conv.scale)
         up = self.upsample
         if up.factor != 2:
             return sis_hip.to_rgb(input, conv.weight, s, self.bias, conv.scale) + up(skip)
-        return sis_hip.to_rgb(input, conv.weight, s, self.bias, conv.scale, skip, up.kernel, up.pad, out=out)
+        return sis_hip.to_rgb(input, conv.weight, s, self.bias, conv.scale, skip, up.kernel, up.pad)
 
     # ---- the form whose channel sum the convolution in front has already formed (sis_hip.modconv2d(..., rgb=)) ----
     def fused_operands(self, s, batch, h, w):
@@ -413,10 +414,10 @@ class ToRGB(nn.Module):
             self._part_key = key
         return conv.weight, s, conv.scale, self._part
 
-    def finish_s(self, skip, out=None):
+    def finish_s(self, skip):
         """The image from the partial sums that the convolution given ``fused_operands`` has left."""
         up = self.upsample
-        return sis_hip.rgb_finish(self._part, self.bias, skip, up.kernel, up.pad, out=out)
+        return sis_hip.rgb_finish(self._part, self.bias, skip, up.kernel, up.pad)
 
 
 def truncate_styles(style, truncation, truncation_latent):
@@ -520,7 +521,9 @@ class Generator(nn.Module):
 
     # ---- one-launch modulation / demodulation for the whole forward (MI355X fast path) ----------------
     def _layer_sequence(self):
-        """(module, latent index) in execution order (model.py:534-552 of the reference)."""
+        """(module, latent index) in execution order (model.py:534-552 of the reference): per resolution the up-convolution, the
+        second convolution and the ToRGB.  A styled convolution's latent index n is also its noise index, and it writes
+        activation n + 1; a ToRGB takes no noise."""
         seq = [(self.conv1, 0), (self.to_rgb1, 1)]
         for r in range(self.log_size - 2):
             i = 1 + 2 * r
@@ -579,61 +582,15 @@ class Generator(nn.Module):
         return _RGB_STREAMS[device]
 
     @staticmethod
-    def _tail_parts(x, rgb, skip):
-        """In how many batch parts the last resolution's convolution + ToRGB run (``_tail``): SIS_RGB_TAIL_SPLIT when the batch
-        divides and holds at least 4 samples per part, else 1.  Default 1 (off): measured on one box at B = 32, two alternating
-        rounds, 15.01-15.02 ms unsplit against 15.02-15.04 (2 parts) and 15.06-15.09 ms (4 parts) -- what the hidden ToRGB
-        saves, the convolution loses to the extra launch tails and to sharing HBM with it (profiles/r05_syn_tail_split.txt)."""
-        parts = int(os.environ.get("SIS_RGB_TAIL_SPLIT", "1"))
-        b = x.shape[0]
-        if parts < 2 or b % parts or b // parts < 4 or skip is None or rgb.upsample.factor != 2:
-            return 1
-        return parts
-
-    @staticmethod
-    def _rgb_fused(conv, rgb, h, w, skip, parts=1):
+    def _rgb_fused(conv, rgb, h, w, skip, route=None):
         """Whether a resolution's second convolution also forms the channel sum of its ToRGB (``ToRGB.fused_operands``), which
         then only adds the channel blocks, the bias and the skip image instead of reading the activation again: wherever the
         F(2x4,3x3) kernel takes the convolution (32^2 and up in the 256^2 generator).  At the last resolution that pass was
         exposed on the main stream; the hidden ones no longer share HBM and CUs with the up-convolutions beside them
-        (profiles/wino24_rgb_epilogue.txt).  The batch-part form (``_tail``) keeps the separate ToRGB."""
-        if parts > 1 or skip is None or rgb.upsample.factor != 2 or rgb.conv.out_channel != 3:
+        (profiles/wino24_rgb_epilogue.txt).  ``route``: ``conv.conv.route(h, w)`` where the caller has asked already."""
+        if skip is None or rgb.upsample.factor != 2 or rgb.conv.out_channel != 3:
             return False
-        return conv.conv.wino24_takes(h, w)
-
-    def _tail(self, x, conv, rgb, s_conv, d_conv, s_rgb, noise, skip, main, side):
-        """The last StyledConv and its ToRGB by batch parts.  The final ToRGB has no later convolution to hide behind (196 us of
-        a 14.9 ms step at B = 32: an HBM-bound pass over the 1 GB activation with the matrix cores idle), so the batch is cut
-        in parts: while the convolution of part k + 1 runs, the side stream converts part k; only the last part's ToRGB is
-        exposed.  Results are written into batch slices of ONE activation tensor and ONE image: same values, same layout.
-        (Off by default; by default that exposed pass is gone instead: the last convolution forms the channel sum in its
-        epilogue, ``_rgb_fused``, and a finish launch over 3 x (Cout / 64 + 1) planes is what stays on the main stream.)"""
-        parts = self._tail_parts(x, rgb, skip)
-        b, _, h, w = x.shape
-        n = b // parts
-        cout = conv.conv.out_channel
-        act = x.new_empty((b, cout, h, w))
-        image = x.new_empty((b, 3, h, w))
-        wpk = conv.conv.packed_weights()[0]
-        per_sample_noise = noise is not None and noise.numel() == b * h * w
-        if noise is None:
-            noise = x.new_empty(b, 1, h, w).normal_()
-            per_sample_noise = True
-        for k in range(parts):
-            sl = slice(k * n, (k + 1) * n)
-            conv.forward_s(x[sl], wpk, s_conv[sl], d_conv[sl], noise[sl] if per_sample_noise else noise, out=act[sl])
-            if k + 1 < parts:
-                ready = main.record_event()
-                with torch.cuda.stream(side):
-                    side.wait_event(ready)
-                    rgb.forward_s(act[sl], s_rgb[sl], skip[sl], out=image[sl])
-            else:   # behind the side chain, on the main stream (as rgb_branch's last=True)
-                main.wait_event(side.record_event())
-                rgb.forward_s(act[sl], s_rgb[sl], skip[sl], out=image[sl])
-        for t in (act, image):
-            t.record_stream(side)
-        skip.record_stream(main)
-        return act, image
+        return (route or conv.conv.route(h, w)) == "wino24"
 
     def _modulate_all(self, latent):
         """Every layer's s [B,Cin] (and scale*demod [B,Cout] for the styled convs): two launches in total."""
@@ -648,6 +605,54 @@ class Generator(nn.Module):
         d_list = [None if sl is None else d_flat[sl[0]:sl[0] + b * sl[1]].view(b, sl[1]) for sl in plan['d_slices']]
         return s_list, d_list
 
+    @staticmethod
+    def _rgb_branch(layer, x, style, prev, main, side, last=False, fused=False):
+        """A ToRGB of the fast path.  The ToRGB / skip chain only reads each resolution's activation: it runs on the side stream
+        so that its HBM-bound passes overlap the MFMA-bound convolutions of the next resolution.  ``fused``: the convolution
+        that wrote x has left the layer's channel sum (ToRGB.fused_operands)."""
+        run = (lambda: layer.finish_s(prev)) if fused else (lambda: layer.forward_s(x, style, prev))
+        if side is None:
+            return run()
+        if last:  # nothing left to overlap it with: on the main stream, behind the side chain (no fork / join gap)
+            main.wait_event(side.record_event())
+            if prev is not None:
+                prev.record_stream(main)  # allocated on the side stream, read here
+            return run()
+        ready = main.record_event()
+        x.record_stream(side)
+        with torch.cuda.stream(side):
+            side.wait_event(ready)
+            return run()
+
+    def _forward_fast(self, latent, noise, tap):
+        """The image, layer by layer over ``_layer_sequence``: the styles of all layers in two launches, each styled convolution
+        asked for its route once, the ToRGB chain beside them."""
+        out = self.input(latent)
+        tap(0, out)
+        s, d = self._modulate_all(latent)
+        main, side = torch.cuda.current_stream(latent.device), self._rgb_stream(latent.device)
+        seq = self._layer_sequence()
+        skip, fused = None, False
+        for k, (layer, n) in enumerate(seq):
+            if isinstance(layer, ToRGB):
+                last = k + 1 == len(seq) and skip is not None   # the end of a chain: to_rgb1 alone (4 x 4 generator) is joined below
+                skip = self._rgb_branch(layer, out, s[k], skip, main, side, last=last, fused=fused)
+                continue
+            wpk = layer.conv.packed_weights()[0]
+            if layer.conv.upsample:
+                out = layer.forward_s(out, wpk, s[k], d[k], noise[n])
+            else:   # the convolution in front of a ToRGB
+                rgb, (h, w) = seq[k + 1][0], out.shape[2:]
+                route = layer.conv.route(h, w)
+                fused = self._rgb_fused(layer, rgb, h, w, skip, route)
+                operands = rgb.fused_operands(s[k + 1], out.shape[0], h, w) if fused else None
+                out = layer.forward_s(out, wpk, s[k], d[k], noise[n], rgb=operands, route=route)
+            tap(n + 1, out)
+        if side is not None and self.log_size == 2:  # 4 x 4 generator: to_rgb1 is the only (side-stream) ToRGB
+            main.wait_event(side.record_event())
+            skip.record_stream(main)
+        return skip
+
     def forward(self, styles, return_latents=False, inject_index=None, truncation=1, truncation_latent=None,
                 input_is_latent=False, noise=None, randomize_noise=True, return_intermediate_activations=False):
         latent, noise = resolve_latents(self, styles, inject_index, truncation, truncation_latent, input_is_latent,
@@ -659,54 +664,13 @@ class Generator(nn.Module):
             if acts is not None:
                 acts[idx] = t.detach()
 
+        if self._fast_path(latent):
+            image = self._forward_fast(latent, noise, tap)
+            if return_latents:
+                return image, latent
+            return (image, acts) if return_intermediate_activations else (image, None)
         out = self.input(latent)
         tap(0, out)
-        if self._fast_path(latent):
-            s, d = self._modulate_all(latent)
-            # The ToRGB / skip chain only reads each resolution's activation: it runs on a side stream so that its
-            # HBM-bound passes overlap the MFMA-bound convolutions of the next resolution.
-            main, side = torch.cuda.current_stream(latent.device), self._rgb_stream(latent.device)
-
-            def rgb_branch(layer, x, style, prev, last=False, fused=False):
-                # fused: the convolution that wrote x has left the layer's channel sum (ToRGB.fused_operands)
-                run = (lambda: layer.finish_s(prev)) if fused else (lambda: layer.forward_s(x, style, prev))
-                if side is None:
-                    return run()
-                if last:  # nothing left to overlap it with: on the main stream, behind the side chain (no fork / join gap)
-                    main.wait_event(side.record_event())
-                    if prev is not None:
-                        prev.record_stream(main)  # allocated on the side stream, read here
-                    return run()
-                ready = main.record_event()
-                x.record_stream(side)
-                with torch.cuda.stream(side):
-                    side.wait_event(ready)
-                    return run()
-
-            out = self.conv1.forward_s(out, self.conv1.conv.packed_weights()[0], s[0], d[0], noise[0])
-            tap(1, out)
-            skip = rgb_branch(self.to_rgb1, out, s[1], None)
-            for r in range(self.log_size - 2):
-                i, j = 1 + 2 * r, 2 + 3 * r
-                up, conv, rgb = self.convs[2 * r], self.convs[2 * r + 1], self.to_rgbs[r]
-                out = up.forward_s(out, up.conv.packed_weights()[0], s[j], d[j], noise[1 + 2 * r])
-                tap(i + 1, out)
-                last = r == self.log_size - 3
-                if last and side is not None and self._tail_parts(out, rgb, skip) > 1:
-                    out, skip = self._tail(out, conv, rgb, s[j + 1], d[j + 1], s[j + 2], noise[2 + 2 * r], skip, main, side)
-                    tap(i + 2, out)
-                    continue
-                fused = self._rgb_fused(conv, rgb, out.shape[2], out.shape[3], skip, self._tail_parts(out, rgb, skip) if last else 1)
-                operands = rgb.fused_operands(s[j + 2], out.shape[0], out.shape[2], out.shape[3]) if fused else None
-                out = conv.forward_s(out, conv.conv.packed_weights()[0], s[j + 1], d[j + 1], noise[2 + 2 * r], rgb=operands)
-                tap(i + 2, out)
-                skip = rgb_branch(rgb, out, s[j + 2], skip, last=last, fused=fused)
-            if side is not None and self.log_size == 2:  # 4 x 4 generator: to_rgb1 is the only (side-stream) ToRGB
-                main.wait_event(side.record_event())
-                skip.record_stream(main)
-            if return_latents:
-                return skip, latent
-            return (skip, acts) if return_intermediate_activations else (skip, None)
         out = self.conv1(out, latent[:, 0], noise=noise[0])
         tap(1, out)
         skip = self.to_rgb1(out, latent[:, 1])

@@ -1029,63 +1029,47 @@ def modconv2d(x, wpk, s, dscale, ksize, noise=None, noise_weight=None, bias=None
 
     ``rgb`` = (weight [3 * Cout], s_rgb [B, Cout], scale, part): the F(2x4,3x3) kernel also leaves the following ToRGB's channel
     sum in ``part`` (``rgb_part_shape``), in blocks of 64 channels, for ``rgb_finish``; an error where that kernel does not take
-    the layer."""
+    the layer.
+
+    ``out``: a caller's contiguous float32 result tensor to write into (tools/bench_gen_bf16.py rotates more outputs than the
+    cache holds)."""
     x = _f32(x, "input")
     batch, cin, h, w = x.shape
     cout = wpk.shape[2]
     noise, nbs = _noise_args(noise, batch, h, w)
     out = _out_or_new(out, (batch, cout, h, w), x.device, "modconv2d")
+    tail = (_ptr(s), _ptr(dscale), _ptr(noise), nbs, _ptr(noise_weight), _ptr(bias))
+    shape, fuse, fast = (batch, cin, cout, h, w), int(bool(fuse_act)), ksize == 3 and batch > 0
+    # The entry, chosen once: its C symbol, the factor on the direct-form FLOP count, what it reads besides x (with the element
+    # size) and its arguments up to the stream.  0.75 for the F(2x4,3x3) entries: bench.py prices every kernel whose name contains
+    # "wino" at 16/36 of the recorded count, and 3/4 x 16/36 = 24/72 is what that kernel executes.
     if rgb is not None:
-        if wino24_u is None or ksize != 3 or batch <= 0 or not modconv_wino24_eligible(cin, cout, h, w):
+        if wino24_u is None or not fast or not modconv_wino24_eligible(cin, cout, h, w):
             raise RuntimeError(f"modconv2d: rgb= needs the F(2x4,3x3) kernel, which does not take {cin} -> {cout} at {h}x{w}")
         rgb_w, rgb_s, rgb_scale, part = rgb
         rgb_w, rgb_s = _f32(rgb_w, "rgb weight"), _f32(rgb_s, "rgb style")
         if rgb_w.numel() != 3 * cout or tuple(rgb_s.shape) != (batch, cout):
             raise RuntimeError(f"modconv2d: rgb weight {tuple(rgb_w.shape)} / style {tuple(rgb_s.shape)} do not fit 3 x {cout} channels")
         _out_or_new(part, rgb_part_shape(batch, cout, h, w), x.device, "modconv2d rgb part")
-        with torch.cuda.device(x.device):
-            _check(_launch(None,
-                           0.75 * 2.0 * batch * cout * cin * 9 * h * w,
-                           4.0 * (x.numel() + out.numel() + wino24_u.numel() + part.numel()),
-                           lambda: lib().sis_modconv2d_wino24_rgb(_ptr(out), _ptr(part), _ptr(x), _ptr(wino24_u), _ptr(s), _ptr(dscale),
-                                                                  _ptr(noise), nbs, _ptr(noise_weight), _ptr(bias), _ptr(rgb_w),
-                                                                  _ptr(rgb_s), float(rgb_scale), batch, cin, cout, h, w,
-                                                                  int(bool(fuse_act)), int(wino24_tiles_per_wg), _stream())),
-                   "sis_modconv2d_wino24_rgb")
-        return out
-    if bf16_w is not None and rgb is None and ksize == 3 and batch > 0 and modconv_bf16_eligible(cin, cout, h, w):
+        symbol, factor, reads = "sis_modconv2d_wino24_rgb", 0.75, ((wino24_u, 4.0), (part, 4.0))
+        args = (_ptr(out), _ptr(part), _ptr(x), _ptr(wino24_u)) + tail + (_ptr(rgb_w), _ptr(rgb_s), float(rgb_scale)) + shape + (
+            fuse, int(wino24_tiles_per_wg))
+    elif bf16_w is not None and fast and modconv_bf16_eligible(cin, cout, h, w):
         if bf16_w.dtype != torch.bfloat16 or bf16_w.numel() != lib().sis_modconv_bf16_packed_elems(cin, cout) or not bf16_w.is_contiguous():
             raise RuntimeError(f"modconv2d: bf16_w is not the modconv_prepack_bf16 image of a {cin} -> {cout} layer")
-        with torch.cuda.device(x.device):
-            _check(_launch(None,
-                           2.0 * batch * cout * cin * 9 * h * w,
-                           4.0 * (x.numel() + out.numel()) + 2.0 * bf16_w.numel(),
-                           lambda: lib().sis_modconv2d_bf16(_ptr(out), _ptr(x), _ptr(bf16_w), _ptr(s), _ptr(dscale), _ptr(noise),
-                                                            nbs, _ptr(noise_weight), _ptr(bias), batch, cin, cout, h, w,
-                                                            int(bool(fuse_act)), _stream())),
-                   "sis_modconv2d_bf16")
-        return out
-    if wino24_u is not None and ksize == 3 and batch > 0 and modconv_wino24_eligible(cin, cout, h, w):
-        with torch.cuda.device(x.device):
-            # FLOPs recorded as direct form x 3/4: bench.py prices every kernel whose name contains "wino" at 16/36 of the
-            # recorded count, and 3/4 x 16/36 = 24/72 is what this kernel executes.
-            _check(_launch(None,
-                           0.75 * 2.0 * batch * cout * cin * 9 * h * w,
-                           4.0 * (x.numel() + out.numel() + wino24_u.numel()),
-                           lambda: lib().sis_modconv2d_wino24(_ptr(out), _ptr(x), _ptr(wino24_u), _ptr(s), _ptr(dscale), _ptr(noise),
-                                                              nbs, _ptr(noise_weight), _ptr(bias), batch, cin, cout, h, w,
-                                                              int(bool(fuse_act)), int(wino24_tiles_per_wg), _stream())),
-                   "sis_modconv2d_wino24")
-        return out
-    ws = _workspace(x.device)
+        symbol, factor, reads = "sis_modconv2d_bf16", 1.0, ((bf16_w, 2.0),)
+        args = (_ptr(out), _ptr(x), _ptr(bf16_w)) + tail + shape + (fuse,)
+    elif wino24_u is not None and fast and modconv_wino24_eligible(cin, cout, h, w):
+        symbol, factor, reads = "sis_modconv2d_wino24", 0.75, ((wino24_u, 4.0),)
+        args = (_ptr(out), _ptr(x), _ptr(wino24_u)) + tail + shape + (fuse, int(wino24_tiles_per_wg))
+    else:   # the general entry: F(2x2,3x3) where ``wino_u`` is given and that kernel takes the shape, else the direct kernels
+        ws = _workspace(x.device)
+        symbol, factor, reads = "sis_modconv2d", 1.0, ((wpk, 4.0),)
+        args = (_ptr(out), _ptr(x), _ptr(wpk)) + tail + shape + (ksize, fuse, _ptr(wino_u), _ptr(ws), ws.numel())
     with torch.cuda.device(x.device):
-        _check(_launch(None,
-                       2.0 * batch * cout * cin * ksize * ksize * h * w,
-                       4.0 * (x.numel() + out.numel() + wpk.numel()),
-                       lambda: lib().sis_modconv2d(_ptr(out), _ptr(x), _ptr(wpk), _ptr(s), _ptr(dscale), _ptr(noise),
-                                                   nbs, _ptr(noise_weight), _ptr(bias), batch, cin, cout, h, w, ksize,
-                                                   int(bool(fuse_act)), _ptr(wino_u), _ptr(ws), ws.numel(), _stream())),
-               "sis_modconv2d")
+        _check(_launch(None, factor * 2.0 * batch * cout * cin * ksize * ksize * h * w,
+                       4.0 * (x.numel() + out.numel()) + sum(size * t.numel() for t, size in reads),
+                       lambda: getattr(lib(), symbol)(*args, _stream())), symbol)
     return out
 
 
@@ -1150,7 +1134,7 @@ def blur_noise_act(x, taps, pad, noise=None, noise_weight=None, bias=None, fuse_
     return out
 
 
-def to_rgb(x, weight, s, bias, scale, skip=None, taps=None, pad=(0, 0), out=None):
+def to_rgb(x, weight, s, bias, scale, skip=None, taps=None, pad=(0, 0)):
     x = _f32(x, "input")
     w = _f32(weight, "weight")
     batch, cin, h, wd = x.shape
@@ -1160,7 +1144,7 @@ def to_rgb(x, weight, s, bias, scale, skip=None, taps=None, pad=(0, 0), out=None
         skip = _f32(skip, "skip")
         taps = _f32(taps, "kernel")
         kh, kw = taps.shape
-    out = _out_or_new(out, (batch, cout, h, wd), x.device, "to_rgb")
+    out = torch.empty((batch, cout, h, wd), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         _check(_launch("to_rgb_kernel", 0.0, 4.0 * (x.numel() + out.numel() + (skip.numel() if skip is not None else 0)),
                        lambda: lib().sis_to_rgb(_ptr(out), _ptr(x), _ptr(w), _ptr(s), _ptr(bias), _ptr(skip),
@@ -1169,7 +1153,7 @@ def to_rgb(x, weight, s, bias, scale, skip=None, taps=None, pad=(0, 0), out=None
     return out
 
 
-def rgb_finish(part, bias, skip=None, taps=None, pad=(0, 0), out=None):
+def rgb_finish(part, bias, skip=None, taps=None, pad=(0, 0)):
     """The ToRGB image from the channel-block sums ``part`` [Cout / 64, B, 3, H, W] of ``modconv2d(..., rgb=)``:
     sum over the blocks + bias + upsampled skip (as ``to_rgb``)."""
     part = _f32(part, "part")
@@ -1179,7 +1163,7 @@ def rgb_finish(part, bias, skip=None, taps=None, pad=(0, 0), out=None):
         skip = _f32(skip, "skip")
         taps = _f32(taps, "kernel")
         kh, kw = taps.shape
-    out = _out_or_new(out, (batch, cout, h, wd), part.device, "rgb_finish")
+    out = torch.empty((batch, cout, h, wd), dtype=torch.float32, device=part.device)
     with torch.cuda.device(part.device):
         _check(_launch("rgb_finish_kernel", 0.0, 4.0 * (part.numel() + out.numel() + (skip.numel() if skip is not None else 0)),
                        lambda: lib().sis_rgb_finish(_ptr(out), _ptr(part), _ptr(bias), _ptr(skip), _ptr(taps), batch, blocks, cout,

@@ -261,33 +261,50 @@ def test_generator_batch32_properties(device):
         assert torch.equal(a, b)
 
 
-def test_generator_tail_split_is_the_unsplit_forward(device, monkeypatch):
-    """SIS_RGB_TAIL_SPLIT: the last StyledConv + ToRGB run by batch parts so that the final ToRGB overlaps the convolution of
-    the next part (Generator._tail).  Whatever the number of parts -- 1 (off, the default), 2, 4 -- image and activations are
-    the same values in the same tensors (per-sample work, written into batch slices), with explicit shared noise, explicit
-    per-sample noise and fresh noise under a seeded device RNG."""
-    g, _ = _build(64, 512, 8, 2, 3, device)
-    z = torch.randn(16, 512, generator=torch.Generator().manual_seed(9)).to(device)
-    shared = [n.to(device) for n in R.seeded_inputs(64, 1, 512, seed=10)[1]]
-    per_sample = [torch.randn(16, 1, n.shape[2], n.shape[3], generator=torch.Generator().manual_seed(11 + i)).to(device)
-                  for i, n in enumerate(shared)]
-    results = {}
-    for parts in ("1", "2", "4"):
-        monkeypatch.setenv("SIS_RGB_TAIL_SPLIT", parts)
+# The kernels a stride-1 3x3 layer's launch may report (sis_last_kernel) on each route of ModulatedConv2d.route:
+ROUTE_KERNELS = {
+    "bf16": {"modconv_bf16_kernel"},                                    # sis_modconv2d_bf16 (csrc/modconv_bf16.h)
+    "wino24": {"modconv_wino24_kernel"},                                # sis_modconv2d_wino24 and _wino24_rgb (csrc/modconv_wino24.h)
+    "wino": {"modconv_wino2_kernel", "modconv_wino_kernel"},            # sis_modconv2d given wino_u (csrc/modconv_wino.hip)
+    "direct": {"modconv_v2_kernel<0, 3>", "modconv_mfma_kernel<0, 3>"},  # sis_modconv2d without (modconv_mfma2.hip, modconv_mfma.hip)
+}
+
+
+@pytest.mark.parametrize("position", ["default", "SIS_WINO24=0", "SIS_WINOGRAD=0", "bf16"])
+def test_generator_layers_run_on_the_route_they_name(device, monkeypatch, position):
+    """Generator(64, 512, 8, 2) at B = 2 reaches every route and both fused ToRGBs.  Each stride-1 3x3 layer's launch reports a
+    kernel of the route that ``route(h, w)`` named: the binding falls through silently where it finds a shape ineligible, so a
+    disagreement between the model's decision and the library's shows here and nowhere else."""
+    import sis_hip
+    for name in ("SIS_WINOGRAD", "SIS_WINO24", "SIS_GEN_PRECISION"):
+        monkeypatch.delenv(name, raising=False)
+    if "=" in position:
+        monkeypatch.setenv(*position.split("="))
+    g, _ = _build(64, 512, 8, 2, 21, device)
+    if position == "bf16":
+        g.set_matrix_precision("bf16")
+    z, noise = R.seeded_inputs(64, 2, 512, seed=22)
+    rec = []
+    sis_hip.set_profiler(rec)
+    try:
         with torch.no_grad():
-            out = []
-            for noise in (shared, per_sample, None):
-                torch.manual_seed(77)
-                img, acts = g([z], noise=noise, return_intermediate_activations=True)
-                out += [img] + [acts[k] for k in sorted(acts)]
-            torch.cuda.synchronize()
-        results[parts] = out
-    for parts in ("2", "4"):
-        # the same per-sample arithmetic (a smaller batch may pick another tile / split plan for the convolution, hence a
-        # tolerance instead of bitwise equality); fresh noise: the tail draws the layer's noise for the whole batch in one call,
-        # exactly as the unsplit layer does
-        for a, b in zip(results["1"], results[parts]):
-            assert a.shape == b.shape and _rel(a, b.cpu()) < 1e-6, parts
+            img, acts = g([z.to(device)], noise=[n.to(device) for n in noise], return_intermediate_activations=True)
+        torch.cuda.synchronize()
+    finally:
+        sis_hip.set_profiler(None)
+    assert bool(torch.isfinite(img).all())
+    names = [r[0] for r in rec]
+    # the launches of the stride-1 3x3 layers, in layer order (up-convolutions, ToRGB and the packs report other names)
+    launched = [n for n in names if any(n in kernels for kernels in ROUTE_KERNELS.values())]
+    layers = [g.conv1] + [g.convs[2 * r + 1] for r in range(g.log_size - 2)]
+    routes = [layer.conv.route(4 << i, 4 << i) for i, layer in enumerate(layers)]
+    print(f"{position}: routes {routes}, kernels {launched}")
+    assert routes == {"default": ["wino", "wino", "wino", "wino24", "wino24"], "SIS_WINO24=0": ["wino"] * 5,
+                      "SIS_WINOGRAD=0": ["direct"] * 5, "bf16": ["wino", "wino", "wino", "bf16", "bf16"]}[position]
+    assert len(launched) == len(layers)
+    for i, (route, kernel) in enumerate(zip(routes, launched)):
+        assert kernel in ROUTE_KERNELS[route], (4 << i, route, kernel)
+    assert names.count("rgb_finish_kernel") == routes.count("wino24")     # the ToRGBs behind them are the fused form
 
 
 def test_generator_batch32_first_and_last_sample_vs_oracle(device):

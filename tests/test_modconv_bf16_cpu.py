@@ -55,7 +55,7 @@ def test_switch_defaults_to_fp32(monkeypatch):
     g = Generator(64, 32, 1, channel_multiplier=2)
     for res in (8, 16, 32, 64):
         c = _conv(g, res)
-        assert c.matrix_precision is None and not c._bf16_switch() and not c.bf16_takes(res, res)
+        assert c.matrix_precision is None and not c._read_switches().bf16 and not c.bf16_takes(res, res)
     assert _conv(g, 64).wino24_takes(64, 64)
     monkeypatch.setenv("SIS_GEN_PRECISION", "fp32")
     assert not _conv(g, 64).bf16_takes(64, 64) and _conv(g, 64).wino24_takes(64, 64)
@@ -69,7 +69,7 @@ def test_switch_on_by_environment_and_by_method(monkeypatch):
     # where a layer runs bf16 the F(2x4,3x3) kernel does not take it, so its ToRGB is the separate pass
     assert not _conv(g, 64).wino24_takes(64, 64) and not g._rgb_fused(g.convs[7], g.to_rgbs[3], 64, 64, torch.zeros(1))
     # up-convolutions, ToRGB and the mapping network have no bf16 route
-    assert not g.convs[6].conv._bf16_switch() and not g.to_rgbs[3].conv._bf16_switch()
+    assert not g.convs[6].conv._read_switches().bf16 and not g.to_rgbs[3].conv._read_switches().bf16
     assert g.set_matrix_precision("fp32") is g
     assert not _conv(g, 64).bf16_takes(64, 64) and _conv(g, 64).wino24_takes(64, 64)
     monkeypatch.delenv("SIS_GEN_PRECISION")

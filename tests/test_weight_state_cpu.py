@@ -74,6 +74,7 @@ def _use(layer, image, stubs):
         return layer.packed_weights()[0]
     if image == "fir":
         return layer.fir_weights()
+    assert layer.route(32, 32) == image
     operand = layer.winograd_operand(32, 32)
     assert list(operand) == [{"wino": "wino_u", "wino24": "wino24_u", "bf16": "bf16_w"}[image]], operand
     return operand[list(operand)[0]]
@@ -156,7 +157,7 @@ def test_set_matrix_precision_keeps_the_fp32_operands(stubs):
     image = _use(layer, "bf16", stubs)
     pack = layer.packed_weights()
     layer.set_matrix_precision("fp32")
-    assert layer.packed_weights() is pack and layer._bf16 is None and stubs["pack"] == 1
+    assert layer.packed_weights() is pack and "bf16" not in layer._images and stubs["pack"] == 1
     stubs.route.update(bf16=True)
     assert not layer.bf16_takes(32, 32) and "bf16_w" not in layer.winograd_operand(32, 32)
     layer.set_matrix_precision("bf16")

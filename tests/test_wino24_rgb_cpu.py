@@ -1,6 +1,7 @@
 """Which resolutions of Generator.forward's fast path let the second convolution form the ToRGB channel sum
-(Generator._rgb_fused): those where sis_modconv_wino24_eligible takes the convolution, and never the batch-part form of
-SIS_RGB_TAIL_SPLIT > 1.  Host code only: no weights are packed and no kernel runs."""
+(Generator._rgb_fused): those where sis_modconv_wino24_eligible takes the convolution and a skip image exists; and which
+route (ModulatedConv2d.route) every layer of a generator takes in every switch position.  Host code only: no kernel runs, and
+where weights are packed the pack functions are stubs."""
 import functools
 
 import pytest
@@ -41,6 +42,9 @@ def test_fused_only_where_the_kernel_takes_the_convolution(monkeypatch):
     assert not real(512, 512, 16, 16) and not g._rgb_fused(conv, rgb, 16, 16, skip)
     monkeypatch.setattr(sis_hip, "modconv_wino24_eligible", lambda *a: False)
     assert not g._rgb_fused(conv, rgb, 64, 64, skip)
+    monkeypatch.setattr(sis_hip, "modconv_wino24_eligible", real)
+    # no skip image: the unfused launch (ToRGB without upsampling has no finish form)
+    assert g._rgb_fused(conv, rgb, 64, 64, skip) and not g._rgb_fused(conv, rgb, 64, 64, None)
 
 
 @pytest.mark.parametrize("switch", ["SIS_WINO24", "SIS_WINOGRAD"])
@@ -52,12 +56,56 @@ def test_not_fused_when_the_kernel_is_switched_off(monkeypatch, switch):
     assert not g._rgb_fused(conv, rgb, 64, 64, torch.zeros(1))
 
 
-def test_batch_parts_keep_the_separate_to_rgb(monkeypatch):
-    g = _generator()
-    conv, rgb = _resolutions(g)[-1][1:3]
-    x, skip = torch.zeros(8, 1, 1, 1), torch.zeros(1)
-    assert g._tail_parts(x, rgb, skip) == 1 and g._rgb_fused(conv, rgb, 64, 64, skip, g._tail_parts(x, rgb, skip))
-    monkeypatch.setenv("SIS_RGB_TAIL_SPLIT", "2")
-    assert g._tail_parts(x, rgb, skip) == 2 and not g._rgb_fused(conv, rgb, 64, 64, skip, g._tail_parts(x, rgb, skip))
-    # no skip image: the unfused launch (ToRGB without upsampling has no finish form)
-    assert not g._rgb_fused(conv, rgb, 64, 64, None)
+# ---- one route per layer: Generator(64, 512, 8, 2), the stride-1 3x3 layers at their own maps (4^2 .. 64^2)
+
+POSITIONS = {   # position: (environment, set_matrix_precision, routes)
+    "default": ({}, None, ["wino", "wino", "wino", "wino24", "wino24"]),
+    "SIS_WINO24=0": ({"SIS_WINO24": "0"}, None, ["wino"] * 5),
+    "SIS_WINOGRAD=0": ({"SIS_WINOGRAD": "0"}, None, ["direct"] * 5),
+    "bf16": ({}, "bf16", ["wino", "wino", "wino", "bf16", "bf16"]),
+    "bf16, SIS_WINOGRAD=0": ({"SIS_WINOGRAD": "0"}, "bf16", ["direct", "direct", "direct", "bf16", "bf16"]),
+}
+
+
+@pytest.mark.parametrize("position", POSITIONS)
+def test_route_of_every_layer(monkeypatch, position):
+    import sis_hip
+    from networks.stylegan2.model import ROUTES, Generator, ToRGB
+    env, precision, want = POSITIONS[position]
+    for name in ("SIS_WINOGRAD", "SIS_WINO24", "SIS_GEN_PRECISION"):
+        monkeypatch.delenv(name, raising=False)
+    for name, value in env.items():
+        monkeypatch.setenv(name, value)
+    packed = []
+    monkeypatch.setattr(sis_hip, "modconv_prepack", lambda w: (w, w))
+    for pack in ("modconv_prepack_bf16", "modconv_prepack_wino24", "modconv_prepack_wino", "modconv_prepack_up_fir"):
+        monkeypatch.setattr(sis_hip, pack, lambda w, pack=pack: packed.append(pack) or w)
+    g = Generator(64, 512, 8, channel_multiplier=2)
+    if precision is not None:
+        g.set_matrix_precision(precision)
+    assert ROUTES == ("bf16", "wino24", "wino", "direct")
+    res, skip, routes, images = 4, None, [], {}
+    for layer, _ in g._layer_sequence():
+        conv = layer.conv
+        if conv.upsample:
+            res *= 2
+            assert conv.fir_weights() is not None
+            images[layer] = {"up_fir"}
+            continue
+        route = conv.route(res, res)
+        assert route in ROUTES and conv.bf16_takes(res, res) == (route == "bf16") and conv.wino24_takes(res, res) == (route == "wino24")
+        conv.operand(route)
+        images[layer] = {route} - {"direct"}
+        if isinstance(layer, ToRGB):
+            assert route == "direct", res
+            assert g._rgb_fused(before, layer, res, res, skip) == (routes[-1] == "wino24" and skip is not None), res
+            assert not g._rgb_fused(before, layer, res, res, None)
+            skip = torch.zeros(1)
+        else:
+            routes.append(route)
+            before = layer
+    assert routes == want
+    # one route + operand request per layer: one image per stride-1 layer (none for "direct"), the fast-FIR planes on the
+    # up-convolutions (all of this generator's qualify), and none on a ToRGB
+    assert {layer: set(layer.conv._images) for layer in images} == images
+    assert len(packed) == sum(len(v) for v in images.values())
