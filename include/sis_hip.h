@@ -1071,6 +1071,58 @@ int sis_label_regions(uint8_t* has, int32_t* region_count, int32_t* regions, int
                       const uint8_t* colours, int classes, int batch, int p, int max_regions, int max_runs, void* workspace,
                       int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Page visualisation: regions and boxes of a whole assembled page, the colour-coded page, its overlay on the scan, box
+ * outlines and cut-out regions (csrc/page_visual.h; the visual half of the reference's
+ * segmentation/evaluation/analyze_image_segments.py).  A page is pred float32 [classes][height][width] on the device with
+ * 1 <= height, width <= 8192 and 2 <= classes <= 16; every entry declines anything else with an error code and launches
+ * nothing.  Integers and bytes only, launch sequence fixed by the arguments, caller's stream, no host sync, the same bytes
+ * on every run.  Stated in DESIGN.md §17 and tested against an independent restatement; NOT pinned against OpenCV's
+ * findContours / boundingRect / drawContours.
+ * sis_page_regions_workspace_bytes (segmentation_utils.py:88-121): bytes of device workspace of one call (9 per pixel and
+ *   class); 0 for a shape outside the limits.
+ * sis_page_regions (segmentation_utils.py:88-121 get_contours_from_prediction / find_class_contours;
+ *   segmentation_visualization.py:35-45 get_bounding_boxes): per plane k other than background_class_id and the classes whose
+ *   bit is set in filter_classes: M0 = (pred * 255.0f) >= 1.0f, M = 5x5 closing of M0, regions = the
+ *   8-connected components of everything the 4-connected background of M cannot reach from outside the plane (step 4),
+ *   twice_area by the 2x2-block rule (step 5).  regions [classes][max_regions][8] int32 = root (the smallest y * width + x of
+ *   the region), x0, y0, w, h (tight box), twice_area, kept (twice_area >= 2 * min_contour_area; the reference's default is
+ *   10), 0; rows in ascending root order.  The reference lists contours in OpenCV's order, so a region's position in this
+ *   table is not the `i` of the reference's file names.  region_count, kept_count [classes] int32: the true numbers, also
+ *   above max_regions; rows beyond max_regions are not stored, rows between the count and max_regions are left as they were.
+ *   region_labels (may be NULL) [classes][height][width] int32: root + 1 of the pixel's region, 0 outside any region.  Skipped
+ *   planes get zero counts and a zero label plane.  regions may be NULL with max_regions == 0.  workspace 4-byte aligned.
+ * sis_page_render (visualization/utils.py:9-68 linear_gradient / network_output_to_color_image;
+ *   segmentation_visualization.py:22-78 save_overlayed_segmentation_image / draw_bounding_boxes / draw_segmentation): up to
+ *   four uint8 [height][width][3] outputs, a NULL pointer skips one.  page uint8 [height][width][page_channels], 1 (grey,
+ *   replicated) or 3 channels; colours uint8 [classes][3] on the HOST.  segmented: confidence_table == NULL: the colour of the
+ *   FIRST maximal class (all-zero pixels: class 0's).  Otherwise confidence_table is uint8 [classes][100][3] on the device
+ *   (entry t = int(255 + (t / 99) * (c - 255))): a pixel whose float32 sum of the non-background planes, in class order, is
+ *   > 0 takes table[first maximal class of ALL classes][(int)(100.0 * (double)max) - 1], where index -1 is entry 99 (the
+ *   reference's negative list index) and so is an index above 99 (the reference raises); other pixels the background colour.
+ *   overlay: the page where segmented equals the background colour on all three bytes, segmented elsewhere.  boxes_on_page /
+ *   boxes_on_segmented: the page / segmented with outlines.  First, in (0,255,0) and stroke 3, every row of regions
+ *   [classes][max_regions][8] below min(region_count[k], max_regions) with `kept` set, as the box x0, y0, x0 + w, y0 + h with
+ *   both ends INCLUSIVE (the reference's BBox(x, y, x + w, y + h) handed to PIL); then, in (255,0,0) and stroke 1, the
+ *   `patches` rows x0, y0, x1, y1 (inclusive) of patch_boxes int32 [patches][4] on the device.  A pixel is painted iff it lies
+ *   in [x0,x1] x [y0,y1], within the image, and one of x-x0, x1-x, y-y0, y1-y is < stroke: ImageDraw.rectangle's outline
+ *   whenever both extents are >= stroke; thinner boxes are filled, where PIL paints outside the box.
+ * sis_page_crops (segmentation_visualization.py:81-133 extract_and_save_bounding_boxes / extract_and_save_contours): table
+ *   int64 [rows][7] on the device = plane, root, x0, y0, w, h, byte offset; every crop is written as uint8 [h][w][3] at its
+ *   offset of out (out_bytes long).  mode 0 (bbox): the page's pixels; mode 1 (contour): the page's pixel where
+ *   region_labels == root + 1, (255,255,255) elsewhere -- the filled outer contour, holes and islands included.  A row whose
+ *   box leaves the page, whose plane does not exist or whose crop does not fit into out is not written. */
+int64_t sis_page_regions_workspace_bytes(int classes, int height, int width);
+int sis_page_regions(int32_t* regions, int32_t* region_count, int32_t* kept_count, int32_t* region_labels, const float* pred,
+                     int classes, int height, int width, int background_class_id, uint32_t filter_classes, int min_contour_area,
+                     int max_regions, void* workspace, int64_t workspace_bytes, void* stream);
+int sis_page_render(uint8_t* segmented, uint8_t* overlay, uint8_t* boxes_on_page, uint8_t* boxes_on_segmented, const float* pred,
+                    const uint8_t* page, int page_channels, const uint8_t* colours, const uint8_t* confidence_table,
+                    const int32_t* regions, const int32_t* region_count, int max_regions, const int32_t* patch_boxes, int patches,
+                    int classes, int height, int width, int background_class_id, void* stream);
+int sis_page_crops(uint8_t* out, int64_t out_bytes, const int64_t* table, int rows, const uint8_t* page, int page_channels,
+                   const int32_t* region_labels, int classes, int height, int width, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

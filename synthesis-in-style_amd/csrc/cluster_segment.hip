@@ -365,7 +365,7 @@ extern "C" int sis_cluster_segment(uint8_t* class_map, uint8_t* colour, uint8_t*
     const int blocks = sis_cdiv(g.n, CTHREADS);
     const dim3 plane_tiles(sis_cdiv(size, CT), sis_cdiv(size, CT), all_planes), job_tiles(plane_tiles.x, plane_tiles.y, all_jobs);
     const int border_blocks = sis_cdiv((int64_t)2 * lines * size, CTHREADS);
-    const Plane all{size, g.n, 1, -1};   // no plane is skipped
+    const Plane all{size, size, g.n, 1, -1, 0u};   // no plane is skipped
 
     if (hipMemsetAsync((char*)workspace + zero_from, 0, need - zero_from, st) != hipSuccess)
         return sis_fail("sis_cluster_segment: clearing the accumulators failed");

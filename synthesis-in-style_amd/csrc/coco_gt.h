@@ -143,8 +143,8 @@ __global__ __launch_bounds__(CTHREADS) void gt_stats_kernel(int* __restrict__ ta
     int* rows = table + (int64_t)plane * cap * GT_ROW;
     const int i = blockIdx.x * CTHREADS + threadIdx.x, lane = threadIdx.x & 63;
     const bool valid = i < g.n;
-    const int y = valid ? i / g.p : 0, x = valid ? i % g.p : 0;
-    const int before = y > 0 ? i - g.p : (x > 0 ? (g.p - 1) * g.p + x - 1 : -1);
+    const int y = valid ? i / g.w : 0, x = valid ? i % g.w : 0;
+    const int before = y > 0 ? i - g.w : (x > 0 ? (g.h - 1) * g.w + x - 1 : -1);
     const int mine = valid ? lab[i] : 0, pred = valid && before >= 0 ? lab[before] : 0;
     const int change = mine != pred;
     int slot = mine != 0 ? slots[mine - 1] : 0, pred_slot = pred != 0 ? slots[pred - 1] : 0;
@@ -233,32 +233,32 @@ __global__ __launch_bounds__(CTHREADS) void gt_emit_kernel(int* __restrict__ run
         const int offset = row[GT_OFFSET];
         if (row[GT_TRANS] == 0 || offset >= max_runs) continue;   // wave-uniform
         const int root = row[GT_ROOT] + 1, x0 = row[GT_MINX], x1 = row[GT_MAXX], y0 = row[GT_MINY], y1 = row[GT_MAXY];
-        const int y_end = min(y1 + 1, g.p - 1);
+        const int y_end = min(y1 + 1, g.h - 1);
         int k = 0, last = 0;
         unsigned long long state = 0;   // the indicator at the position before
         for (int x = x0; x <= x1; ++x) {
             for (int yc = y0; yc <= y_end; yc += 64) {
                 const int y = yc + lane, rows_here = min(64, y_end - yc + 1);
-                const unsigned long long in = __ballot(y <= y_end && lab[y * g.p + x] == root);
+                const unsigned long long in = __ballot(y <= y_end && lab[y * g.w + x] == root);
                 const unsigned long long span = rows_here == 64 ? ~0ull : (1ull << rows_here) - 1ull;
                 const unsigned long long turns = (in ^ ((in << 1) | state)) & span;
                 if ((turns >> lane) & 1ull) {
                     const unsigned long long below = turns & below_me;
                     const int at = k + __popcll(below);
-                    const int before = below ? x * g.p + yc + 63 - __clzll((long long)below) : last;
-                    if (offset + at < max_runs) out[offset + at] = x * g.p + y - before;
+                    const int before = below ? x * g.h + yc + 63 - __clzll((long long)below) : last;
+                    if (offset + at < max_runs) out[offset + at] = x * g.h + y - before;
                 }
                 if (turns) {
-                    last = x * g.p + yc + 63 - __clzll((long long)turns);
+                    last = x * g.h + yc + 63 - __clzll((long long)turns);
                     k += __popcll(turns);
                 }
                 state = (in >> (rows_here - 1)) & 1ull;
             }
             // the column ended inside the region (its last row is the plane's): the next position is the top of column x + 1,
             // which is the region's only where the box starts at row 0 and has that column
-            if (state && x + 1 < g.p && !(y0 == 0 && x < x1)) {
-                if (lane == 0 && offset + k < max_runs) out[offset + k] = (x + 1) * g.p - last;
-                last = (x + 1) * g.p;
+            if (state && x + 1 < g.w && !(y0 == 0 && x < x1)) {
+                if (lane == 0 && offset + k < max_runs) out[offset + k] = (x + 1) * g.h - last;
+                last = (x + 1) * g.h;
                 ++k;
                 state = 0;
             }
@@ -288,7 +288,7 @@ extern "C" int sis_label_regions(uint8_t* has, int32_t* region_count, int32_t* r
     SIS_REQUIRE(workspace_bytes >= sis_label_regions_workspace_bytes(batch, classes, p), "sis_label_regions: workspace too small");
     SIS_REQUIRE(((uintptr_t)workspace & 3) == 0, "sis_label_regions: workspace not 4-byte aligned");
     const int planes = batch * classes, cap = gt_region_capacity(p);
-    const Plane g{p, p * p, classes, -1};   // no plane is skipped
+    const Plane g{p, p, p * p, classes, -1, 0u};   // no plane is skipped
     const int64_t total = (int64_t)planes * g.n;
     int* outside = (int*)workspace;            // pass-1 labels, later the slot of every root
     int* region = outside + total;             // pass-2 labels

@@ -14,11 +14,17 @@ constexpr int CT2 = CT * CT;
 constexpr int CTHREADS = 256;
 constexpr int CMAXP = 1024;
 
+// A plane is w pixels wide and h high (the square callers pass p, p); pixel (y, x) has index y * w + x.  skip_classes: bit k set
+// skips class k as the background class is skipped (the page entries' filter_classes; 0 elsewhere).
 struct Plane {
-    int p, n, classes, background;   // n = p*p
+    int w, h, n, classes, background;   // n = w*h
+    unsigned skip_classes;
 };
 
-__device__ __forceinline__ bool skip_plane(const Plane& g, int plane) { return plane % g.classes == g.background; }
+__device__ __forceinline__ bool skip_plane(const Plane& g, int plane) {
+    const int k = plane % g.classes;
+    return k == g.background || ((g.skip_classes >> (k & 31)) & 1u) != 0;
+}
 
 // ---- union-find on 1-based labels; 0 is a root of its own --------------------------------------------------------------------
 __device__ __forceinline__ int find_lds(const volatile int* s, int lab) {
@@ -92,14 +98,14 @@ __global__ __launch_bounds__(CTHREADS) void contour_label_tile_kernel(int* __res
         const int k = threadIdx.x + j * CTHREADS;
         const int lx = k % CT, y = y0 + k / CT, x = x0 + lx;
         bool on = false, edge = false;
-        if (y < g.p && x < g.p) {
-            const int i = y * g.p + x;
+        if (y < g.h && x < g.w) {
+            const int i = y * g.w + x;
             if (REGION) {
                 int budget = g.n + 1;
                 on = find_global<false>(outside_labels + base, i + 1, budget) != 0;
             } else {
                 on = active[base + i] == 0;
-                edge = y == 0 || x == 0 || y == g.p - 1 || x == g.p - 1;
+                edge = y == 0 || x == 0 || y == g.h - 1 || x == g.w - 1;
             }
         }
         const unsigned row = (unsigned)(__ballot(on) >> (lane & 32));
@@ -134,12 +140,12 @@ __global__ __launch_bounds__(CTHREADS) void contour_label_tile_kernel(int* __res
     __syncthreads();
     for (int k = threadIdx.x; k < CT2; k += CTHREADS) {
         const int y = y0 + k / CT, x = x0 + k % CT;
-        if (y >= g.p || x >= g.p) continue;
-        const int i = y * g.p + x;
+        if (y >= g.h || x >= g.w) continue;
+        const int i = y * g.w + x;
         int lab;
         if (act[k]) {
             const int root = find_lds(s, k + 1);
-            lab = root == 0 ? 0 : (y0 + (root - 1) / CT) * g.p + x0 + (root - 1) % CT + 1;
+            lab = root == 0 ? 0 : (y0 + (root - 1) / CT) * g.w + x0 + (root - 1) % CT + 1;
         } else {
             lab = REGION ? 0 : i + 1;
         }
@@ -154,23 +160,24 @@ __global__ __launch_bounds__(CTHREADS) void contour_merge_borders_kernel(int* __
                                                                          const uint8_t* __restrict__ active, Plane g) {
     const int plane = blockIdx.y;
     if (skip_plane(g, plane)) return;
-    const int lines = (g.p - 1) / CT;   // interior tile borders per direction
+    const int across = ((g.w - 1) / CT) * g.h;   // pixels on the first columns of the tiles right of an interior tile border
+    const int below = ((g.h - 1) / CT) * g.w;    // pixels on the first rows of the tiles under one
     const int id = blockIdx.x * CTHREADS + threadIdx.x;
-    if (id >= 2 * lines * g.p) return;
-    const bool vertical = id < lines * g.p;
-    const int r = vertical ? id : id - lines * g.p;
-    const int line = (r / g.p + 1) * CT, along = r % g.p;
+    if (id >= across + below) return;
+    const bool vertical = id < across;
+    const int r = vertical ? id : id - across, length = vertical ? g.h : g.w;
+    const int line = (r / length + 1) * CT, along = r % length;
     const int y = vertical ? along : line, x = vertical ? line : along;
     int* lab = labels + (int64_t)plane * g.n;
     const uint8_t* act = active + (int64_t)plane * g.n;
     const uint8_t on = REGION ? 1 : 0;
-    if (act[y * g.p + x] != on) return;
-    const int me = y * g.p + x + 1, budget = 4 * g.n + 64;
+    if (act[y * g.w + x] != on) return;
+    const int me = y * g.w + x + 1, budget = 4 * g.n + 64;
     for (int d = -1; d <= 1; ++d) {
         if (!REGION && d != 0) continue;
         const int ny = vertical ? y + d : y - 1, nx = vertical ? x - 1 : x + d;
-        if (ny < 0 || ny >= g.p || nx < 0 || nx >= g.p) continue;
-        if (act[ny * g.p + nx] == on) union_global(lab, me, ny * g.p + nx + 1, budget);
+        if (ny < 0 || ny >= g.h || nx < 0 || nx >= g.w) continue;
+        if (act[ny * g.w + nx] == on) union_global(lab, me, ny * g.w + nx + 1, budget);
     }
 }
 

@@ -32,7 +32,7 @@ __global__ __launch_bounds__(CTHREADS) void contour_mask_kernel(uint8_t* __restr
         const int ly = k / (CT + 8), lx = k % (CT + 8);
         const int y = y0 + ly - 4, x = x0 + lx - 4;
         uint8_t v = 0;
-        if (y >= 0 && y < g.p && x >= 0 && x < g.p) v = (threshold(src[y * g.p + x], min_confidence) * 255.0f) >= 1.0f;
+        if (y >= 0 && y < g.h && x >= 0 && x < g.w) v = (threshold(src[y * g.w + x], min_confidence) * 255.0f) >= 1.0f;
         m0[ly][lx] = v;
     }
     __syncthreads();
@@ -40,7 +40,7 @@ __global__ __launch_bounds__(CTHREADS) void contour_mask_kernel(uint8_t* __restr
         const int ly = k / (CT + 4), lx = k % (CT + 4);
         const int y = y0 + ly - 2, x = x0 + lx - 2;
         uint8_t v = 1;
-        if (y >= 0 && y < g.p && x >= 0 && x < g.p) {
+        if (y >= 0 && y < g.h && x >= 0 && x < g.w) {
             v = 0;
 #pragma unroll
             for (int dy = 0; dy < 5; ++dy)
@@ -53,13 +53,13 @@ __global__ __launch_bounds__(CTHREADS) void contour_mask_kernel(uint8_t* __restr
     for (int k = threadIdx.x; k < CT2; k += CTHREADS) {
         const int ly = k / CT, lx = k % CT;
         const int y = y0 + ly, x = x0 + lx;
-        if (y >= g.p || x >= g.p) continue;
+        if (y >= g.h || x >= g.w) continue;
         uint8_t v = 1;
 #pragma unroll
         for (int dy = 0; dy < 5; ++dy)
 #pragma unroll
             for (int dx = 0; dx < 5; ++dx) v &= dil[ly + dy][lx + dx];
-        mask[(int64_t)plane * g.n + y * g.p + x] = v;
+        mask[(int64_t)plane * g.n + y * g.w + x] = v;
     }
 }
 
@@ -82,18 +82,18 @@ __global__ __launch_bounds__(CTHREADS) void contour_area_kernel(int* __restrict_
                                                                 const uint8_t* __restrict__ member, Plane g) {
     const int plane = blockIdx.y;
     if (skip_plane(g, plane)) return;
-    const int id = blockIdx.x * CTHREADS + threadIdx.x, side = g.p + 1;
+    const int id = blockIdx.x * CTHREADS + threadIdx.x, side = g.w + 1;
     const int64_t base = (int64_t)plane * g.n;
     int add = 0, lab = 0;
-    if (id < side * side) {
+    if (id < side * (g.h + 1)) {
         const int by = id / side, bx = id % side;   // pixels (by-1 .. by, bx-1 .. bx)
         int count = 0;
         for (int dy = -1; dy <= 0; ++dy)
             for (int dx = -1; dx <= 0; ++dx) {
                 const int y = by + dy, x = bx + dx;
-                if (y >= 0 && y < g.p && x >= 0 && x < g.p && member[base + y * g.p + x]) {
+                if (y >= 0 && y < g.h && x >= 0 && x < g.w && member[base + y * g.w + x]) {
                     ++count;
-                    lab = labels[base + y * g.p + x];
+                    lab = labels[base + y * g.w + x];
                 }
             }
         add = count == 4 ? 2 : (count == 3 ? 1 : 0);
@@ -148,7 +148,7 @@ extern "C" int sis_remove_small_contours(float* out, const float* pred, void* wo
     const int planes = batch * classes;
     SIS_REQUIRE(workspace_bytes >= sis_contour_workspace_bytes(planes, p), "sis_remove_small_contours: workspace too small");
     SIS_REQUIRE(((uintptr_t)workspace & 3) == 0, "sis_remove_small_contours: workspace not 4-byte aligned");
-    const Plane g{p, p * p, classes, background_class_id};
+    const Plane g{p, p, p * p, classes, background_class_id, 0u};
     const int64_t total = (int64_t)planes * g.n;
     int* outside = (int*)workspace;        // pass-1 labels, later the area accumulator
     int* region = outside + total;         // pass-2 labels
@@ -186,3 +186,4 @@ extern "C" int sis_remove_small_contours(float* out, const float* pred, void* wo
 }
 
 #include "coco_gt.h"   // the dataset's ground truth: region tables and COCO run lengths on the same labelling kernels
+#include "page_visual.h"   // page visualisation: regions of whole pages, colouring, outlines and crops on the same kernels

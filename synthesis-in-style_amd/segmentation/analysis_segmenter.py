@@ -24,8 +24,11 @@ BBox = Tuple[int, int, int, int]  # left, top, right, bottom (utils/segmentation
 
 class AnalysisSegmenter:
     def __init__(self, network, patch_size: int, device, batch_size: int = 1, max_image_size: int = 0,
-                 patch_overlap: int = 0, patch_overlap_factor: float = 0.0):
+                 patch_overlap: int = 0, patch_overlap_factor: float = 0.0, class_to_color_map=None,
+                 show_confidence_in_segmentation: bool = False):
         self.network = network.eval()
+        self.class_to_color_map = class_to_color_map
+        self.show_confidence_in_segmentation = show_confidence_in_segmentation
         self.device = torch.device(device)
         self.batch_size = batch_size
         self.patch_size = int(patch_size)
@@ -122,6 +125,16 @@ class AnalysisSegmenter:
         page = self._page_tensor(image)
         predictions = self.predict_patches(self.crop_and_batch_patches(page))
         return self.assemble_predictions(predictions, (page.shape[1], page.shape[0]), with_labels=True)[1]
+
+    def prediction_to_color_image(self, assembled_prediction: torch.Tensor):
+        """The colour-coded page as a PIL image (reference :190-195, visualization/utils.py:29-68), coloured on the device
+        by ``sis_hip.page_render``; with ``show_confidence_in_segmentation`` the lighter a pixel, the lower its confidence."""
+        from PIL import Image
+        from segmentation.evaluation.segmentation_visualization import page_palette
+        colours, background, table = page_palette(self)
+        segmented = sis_hip.page_render(assembled_prediction, None, colours, background_class_id=background,
+                                        confidence_table=table, outputs=("segmented",)).segmented
+        return Image.fromarray(segmented.cpu().numpy())
 
 
 class VotingAssemblySegmenter(AnalysisSegmenter):

@@ -8,8 +8,9 @@ Where the work happens differs from the reference: the page, its patches, the po
 small-contour removal), the vote, the ground-truth class map and the confusion matrices stay on the device, and one run copies
 its matrices to the host once.  ``main`` is a thin layer of file handling over ``evaluate_pages``.
 
-The drawing half of the reference tool (``-vis``, bounding boxes, contour export, overlays) is OpenCV / PIL drawing and is not
-part of this port: those flags raise.
+The drawing half of the reference tool (``-vis``, bounding boxes, contour export, overlays) is a command of its own,
+``python -m segmentation.evaluation.segmentation_visualization``, which takes the same flags; here those flags
+raise.
 """
 import argparse
 import itertools
@@ -38,7 +39,7 @@ def build_parser() -> argparse.ArgumentParser:
     mode.add_argument("-cio", "--calculate-iou", action="store_true", default=False)
     mode.add_argument("-cpr", "--calculate-precision", action="store_true", default=False)
     mode.add_argument("-cre", "--calculate-recall", action="store_true", default=False)
-    mode.add_argument("-vis", "--visualize-segmentation", action="store_true", default=False, help="not part of this port")
+    mode.add_argument("-vis", "--visualize-segmentation", action="store_true", default=False, help="see segmentation_visualization")
 
     files = parser.add_argument_group("File management")
     files.add_argument("image_dir", type=Path, help="directory that contains the images that should be analyzed")
@@ -65,7 +66,7 @@ def build_parser() -> argparse.ArgumentParser:
     hyper.add_argument("--min-confidence", nargs="+", type=float, default=[0.7])
     hyper.add_argument("--min-contour-area", nargs="+", type=int, default=[55])
 
-    visual = parser.add_argument_group("Visual output determination (not part of this port)")
+    visual = parser.add_argument_group("Visual output determination (python -m segmentation.evaluation.segmentation_visualization)")
     for flag in ("--extract-bboxes", "--draw-patches", "--draw-bboxes-on-segmentation", "--save-bboxes", "--save-contours",
                  "--show-confidence", "--overlay-segmentation"):
         visual.add_argument(flag, action="store_true", default=False)
@@ -76,8 +77,9 @@ def parse_and_check_arguments(argv=None) -> argparse.Namespace:
     args = build_parser().parse_args(argv)
     asked = [flag for flag in VISUAL_FLAGS if getattr(args, flag)]
     if asked:
-        raise NotImplementedError("visualisation, bounding-box and contour export are OpenCV / PIL drawing and not part of this "
-                                  f"port: {', '.join('--' + f.replace('_', '-') for f in asked)}")
+        raise NotImplementedError("visualisation, bounding-box and contour export are not part of this command (use python -m "
+                                  "segmentation.evaluation.segmentation_visualization, which takes the same flags): "
+                                  f"{', '.join('--' + f.replace('_', '-') for f in asked)}")
     if not any(selected_metrics(args).values()):
         raise SystemExit("No metric selected (-cds, -cio, -cpr, -cre): there would be no output.")
     if args.ground_truth_dir is None:

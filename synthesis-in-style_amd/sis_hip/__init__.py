@@ -222,6 +222,10 @@ _SIGNATURES = {
     "sis_autoencoder_batch": ([_vp] * 8 + [_i64, _i, _i, _vp], _i),
     "sis_label_regions_workspace_bytes": ([_i, _i, _i], _i64),
     "sis_label_regions": ([_vp] * 7 + [_i] * 5 + [_vp, _i64, _vp], _i),
+    "sis_page_regions_workspace_bytes": ([_i, _i, _i], _i64),
+    "sis_page_regions": ([_vp] * 5 + [_i] * 4 + [ctypes.c_uint32, _i, _i, _vp, _i64, _vp], _i),
+    "sis_page_render": ([_vp] * 6 + [_i, _vp, _vp, _vp, _vp, _i, _vp] + [_i] * 5 + [_vp], _i),
+    "sis_page_crops": ([_vp, _i64, _vp, _i, _vp, _i, _vp] + [_i] * 4 + [_vp], _i),
 }
 
 
@@ -3563,3 +3567,180 @@ def label_regions(label, colours, runs=True, max_regions=None, max_runs=None):
                                                        _ptr(label), c_colours, k, b, p, max_regions, max_runs, _ptr(ws),
                                                        ws.numel() * 4, _stream())), "sis_label_regions")
     return LabelRegions(has, region_count, regions, run_total, counts)
+
+
+# ------------------------------------------------------------------------------ page visualisation (csrc/page_visual.h)
+
+PageRegions = collections.namedtuple("PageRegions", "regions region_count kept_count region_labels")
+PageRender = collections.namedtuple("PageRender", "segmented overlay boxes_on_page boxes_on_segmented")
+PAGE_MAX_EDGE, PAGE_MAX_CLASSES, PAGE_GRADIENT_STEPS = 8192, 16, 100
+PAGE_DEFAULT_MAX_REGIONS = 4096
+PAGE_RENDER_OUTPUTS = PageRender._fields
+
+
+def _page_pred(pred, who):
+    require_device(pred, "pred")
+    if pred.dtype != torch.float32 or pred.dim() != 3:
+        raise RuntimeError(f"{who}: float32 [classes, H, W] confidences are needed, got {pred.dtype} {tuple(pred.shape)}")
+    return pred.contiguous()
+
+
+def _page_image(page, height, width, who):
+    require_device(page, "page")
+    if page.dim() == 2:
+        page = page.unsqueeze(-1)
+    if page.dtype != torch.uint8 or page.dim() != 3 or page.shape[2] not in (1, 3) or tuple(page.shape[:2]) != (height, width):
+        raise RuntimeError(f"{who}: a uint8 [{height}, {width}, 1 or 3] page is needed, got {page.dtype} {tuple(page.shape)}")
+    return page.contiguous()
+
+
+def page_regions_capacity(height, width):
+    """The number of regions no plane can exceed: an aligned 2x2 block holds pixels of one region at most."""
+    return ((int(height) + 1) // 2) * ((int(width) + 1) // 2)
+
+
+def page_regions(pred, background_class_id=0, filter_classes=(), min_contour_area=10, max_regions=None, labels=True):
+    """float32 [classes, H, W] confidences of an assembled page (device) -> a ``PageRegions`` of device tensors (DESIGN.md
+    §17.1): ``regions`` int32 [classes, max_regions, 8] with rows (root, x0, y0, w, h, twice_area, kept, 0) in ascending root
+    order, ``region_count`` and ``kept_count`` int32 [classes] (the true numbers, also above ``max_regions``), ``region_labels``
+    int32 [classes, H, W] (root + 1 per pixel, 0 outside any region; None with ``labels=False``).  The background plane and the
+    planes in ``filter_classes`` are skipped: zero counts, zero labels.  Rows from the count on are not written.
+    ``max_regions`` defaults to ``min(page_regions_capacity(H, W), PAGE_DEFAULT_MAX_REGIONS)``; 0 stores no rows (``regions``
+    is None).  Fixed launch sequence on the current stream, no host sync."""
+    pred = _page_pred(pred, "page_regions")
+    classes, height, width = pred.shape
+    mask = 0
+    for k in filter_classes:
+        if not 0 <= int(k) < classes:
+            raise RuntimeError(f"page_regions: filter class {k} outside the {classes} classes")
+        mask |= 1 << int(k)
+    if max_regions is None:
+        max_regions = min(page_regions_capacity(height, width), PAGE_DEFAULT_MAX_REGIONS)
+    max_regions = int(max_regions)
+    if max_regions < 0:
+        raise RuntimeError("page_regions: negative capacity")
+    dev = pred.device
+    regions = torch.empty((classes, max_regions, 8), dtype=torch.int32, device=dev) if max_regions > 0 else None
+    region_count = torch.empty((classes,), dtype=torch.int32, device=dev)
+    kept_count = torch.empty((classes,), dtype=torch.int32, device=dev)
+    region_labels = torch.empty((classes, height, width), dtype=torch.int32, device=dev) if labels else None
+    ws_bytes = int(lib().sis_page_regions_workspace_bytes(classes, height, width))
+    ws = torch.empty(((max(ws_bytes, 4) + 3) // 4,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _check(_launch("pv_box_kernel", 0.0, 40.0 * pred.numel(),
+                       lambda: lib().sis_page_regions(_ptr(regions), _ptr(region_count), _ptr(kept_count), _ptr(region_labels),
+                                                      _ptr(pred), classes, height, width, int(background_class_id), mask,
+                                                      int(min_contour_area), max_regions, _ptr(ws), ws.numel() * 4, _stream())),
+               "sis_page_regions")
+    return PageRegions(regions, region_count, kept_count, region_labels)
+
+
+def page_confidence_table(colours):
+    """[classes][100][3] integers: per class the reference's ``linear_gradient((255, 255, 255), colour, 100)``
+    (visualization/utils.py:9-26), entry t = int(255 + (t / 99) * (c - 255)) in Python float arithmetic, entry 0 white."""
+    n = PAGE_GRADIENT_STEPS
+    return [[[255, 255, 255]] + [[int(255 + (float(t) / (n - 1)) * (int(c) - 255)) for c in colour] for t in range(1, n)]
+            for colour in colours]
+
+
+def _page_colours(colours, classes, who):
+    flat = [int(v) for colour in colours for v in colour]
+    if len(flat) != 3 * classes or any(len(colour) != 3 for colour in colours) or any(not 0 <= v <= 255 for v in flat):
+        raise RuntimeError(f"{who}: {classes} colours of three bytes are needed, got {colours!r}")
+    return flat
+
+
+def page_render(pred, page, colours, background_class_id=0, confidence_table=None, regions=None, region_count=None,
+                patch_boxes=None, outputs=PAGE_RENDER_OUTPUTS):
+    """The page's pictures as a ``PageRender`` of uint8 [H, W, 3] device tensors, None for every name not in
+    ``outputs``.  ``pred`` float32 [classes, H, W]; ``page`` uint8 [H, W, 1 or 3] (may be None when neither ``overlay`` nor
+    ``boxes_on_page`` is asked for); ``colours`` [classes][3] host integers; ``confidence_table`` uint8 [classes, 100, 3] on the
+    device (``page_confidence_table`` uploaded) selects the confidence mode; ``regions`` / ``region_count`` are
+    ``page_regions``' tables, whose kept rows are outlined in green, stroke 3; ``patch_boxes`` int32 [m, 4] on the device
+    (x0, y0, x1, y1, inclusive) are outlined in red, stroke 1, afterwards.  At most three launches on the current stream."""
+    pred = _page_pred(pred, "page_render")
+    classes, height, width = pred.shape
+    unknown = [name for name in outputs if name not in PAGE_RENDER_OUTPUTS]
+    if unknown or not outputs:
+        raise RuntimeError(f"page_render: outputs must be some of {PAGE_RENDER_OUTPUTS}, got {tuple(outputs)}")
+    flat = _page_colours(colours, classes, "page_render")
+    if page is not None:
+        page = _page_image(page, height, width, "page_render")
+    elif "overlay" in outputs or "boxes_on_page" in outputs:
+        raise RuntimeError("page_render: overlay and boxes_on_page need the page")
+    dev = pred.device
+    if confidence_table is not None:
+        require_device(confidence_table, "confidence_table")
+        if confidence_table.dtype != torch.uint8 or tuple(confidence_table.shape) != (classes, PAGE_GRADIENT_STEPS, 3):
+            raise RuntimeError(f"page_render: a uint8 [{classes}, {PAGE_GRADIENT_STEPS}, 3] confidence table is needed")
+        confidence_table = confidence_table.contiguous()
+    max_regions = 0
+    if regions is not None:
+        require_device(regions, "regions")
+        if regions.dtype != torch.int32 or regions.dim() != 3 or regions.shape[0] != classes or regions.shape[2] != 8 \
+                or region_count is None or region_count.dtype != torch.int32 or tuple(region_count.shape) != (classes,) \
+                or not region_count.is_cuda:
+            raise RuntimeError("page_render: regions int32 [classes, max_regions, 8] and region_count int32 [classes] are needed")
+        regions, region_count, max_regions = regions.contiguous(), region_count.contiguous(), regions.shape[1]
+    patches = 0
+    if patch_boxes is not None:
+        require_device(patch_boxes, "patch_boxes")
+        if patch_boxes.dtype != torch.int32 or patch_boxes.dim() != 2 or patch_boxes.shape[1] != 4:
+            raise RuntimeError("page_render: int32 [m, 4] patch boxes are needed")
+        patch_boxes, patches = patch_boxes.contiguous(), patch_boxes.shape[0]
+    images = [torch.empty((height, width, 3), dtype=torch.uint8, device=dev) if name in outputs else None
+              for name in PAGE_RENDER_OUTPUTS]
+    c_colours = (ctypes.c_uint8 * (3 * classes))(*flat)
+    with torch.cuda.device(dev):
+        _check(_launch("pv_colour_kernel", 0.0, 4.0 * pred.numel() + 3.0 * height * width * (1 + len(outputs)),
+                       lambda: lib().sis_page_render(*[_ptr(t) for t in images], _ptr(pred), _ptr(page),
+                                                     0 if page is None else page.shape[2], c_colours, _ptr(confidence_table),
+                                                     _ptr(regions) if max_regions else None,
+                                                     _ptr(region_count) if max_regions else None, max_regions,
+                                                     _ptr(patch_boxes) if patches else None, patches, classes, height, width,
+                                                     int(background_class_id), _stream())), "sis_page_render")
+    return PageRender(*images)
+
+
+def page_crops(page, rows, mode, region_labels=None):
+    """Cut-out regions of a page.  ``rows``: host sequence or array of (plane, root, x0, y0, w, h); ``mode`` "bbox"
+    copies the page's pixels, "contour" keeps them where ``region_labels`` (``page_regions``' int32 [classes, H, W]) equals
+    root + 1 and paints (255, 255, 255) elsewhere.  Returns (packed uint8 device buffer, list of byte offsets): crop i is
+    ``buffer[offsets[i]:offsets[i] + h * w * 3].view(h, w, 3)``.  One table upload, one launch on the current stream."""
+    if mode not in ("bbox", "contour"):
+        raise RuntimeError(f"page_crops: mode must be 'bbox' or 'contour', got {mode!r}")
+    require_device(page, "page")
+    if page.dim() == 2:
+        page = page.unsqueeze(-1)
+    height, width = int(page.shape[0]), int(page.shape[1])
+    page = _page_image(page, height, width, "page_crops")
+    classes = PAGE_MAX_CLASSES
+    if mode == "contour":
+        if region_labels is None or not region_labels.is_cuda or region_labels.dtype != torch.int32 or region_labels.dim() != 3 \
+                or tuple(region_labels.shape[1:]) != (height, width):
+            raise RuntimeError(f"page_crops: contour mode needs int32 [classes, {height}, {width}] region labels on the device")
+        region_labels, classes = region_labels.contiguous(), region_labels.shape[0]
+    else:
+        region_labels = None
+    table = torch.as_tensor(rows, dtype=torch.int64).reshape(-1, 6)   # on the host: plane, root, x0, y0, w, h
+    plane, x0, y0, w, h = table[:, 0], table[:, 2], table[:, 3], table[:, 4], table[:, 5]
+    bad = (plane < 0) | (plane >= classes) | (x0 < 0) | (y0 < 0) | (w < 1) | (h < 1) | (x0 + w > width) | (y0 + h > height)
+    if bool(bad.any()):
+        row = tuple(table[int(bad.nonzero()[0])].tolist())
+        raise RuntimeError(f"page_crops: row {row} leaves the {height} x {width} page")
+    sizes = 3 * w * h
+    ends = torch.cumsum(sizes, 0)
+    total = int(ends[-1]) if len(table) else 0
+    offsets = (ends - sizes).tolist()
+    dev = page.device
+    out = torch.empty((total,), dtype=torch.uint8, device=dev)
+    if not len(table):
+        return out, offsets
+    device_table = torch.empty((len(table), 7), dtype=torch.int64, device=dev)
+    device_table.copy_(torch.cat([table, (ends - sizes)[:, None]], dim=1))
+    with torch.cuda.device(dev):
+        _check(_launch("pv_crops_kernel", 0.0, 2.0 * total,
+                       lambda: lib().sis_page_crops(_ptr(out), total, _ptr(device_table), len(table), _ptr(page), page.shape[2],
+                                                    _ptr(region_labels), classes, height, width, 1 if mode == "contour" else 0,
+                                                    _stream())), "sis_page_crops")
+    return out, offsets

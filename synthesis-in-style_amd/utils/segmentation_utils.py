@@ -2,13 +2,52 @@
 
 The reference walks the class-to-colour map with one ``numpy.where`` over the whole image per class; here the image is
 uploaded once and ``sis_color_to_class`` compares every pixel against the colour table in one pass.  The contour helpers of
-the reference file are OpenCV code and have no counterpart: the contour filter is ``sis_hip.remove_small_contours``.
+the reference file are OpenCV code and have no counterpart here: the contour filter is ``sis_hip.remove_small_contours``,
+``find_class_contours`` + ``cv2.boundingRect`` are ``sis_hip.page_regions`` (segmentation/evaluation/segmentation_visualization.py).
+``BBox`` is the reference's (:21-64).
 """
-from typing import Dict
+from typing import Dict, NamedTuple, Tuple
 
 import torch
 
 import sis_hip
+
+
+class BBox(NamedTuple):
+    left: int
+    top: int
+    right: int
+    bottom: int
+
+    @classmethod
+    def from_opencv_bounding_rect(cls, x, y, width, height):
+        return cls(x, y, x + width, y + height)
+
+    def top_left(self) -> Tuple:
+        return self.left, self.top
+
+    def bottom_right(self) -> Tuple:
+        return self.right, self.bottom
+
+    @property
+    def width(self) -> int:
+        return self.right - self.left
+
+    @property
+    def height(self) -> int:
+        return self.bottom - self.top
+
+    def as_points(self) -> Tuple:
+        """top left, top right, bottom right, bottom left"""
+        return self.top_left(), (self.right, self.top), self.bottom_right(), (self.left, self.bottom)
+
+    def is_overlapping_with(self, other_box: "BBox") -> bool:
+        return self.left < other_box.right and self.right > other_box.left and self.top < other_box.bottom \
+            and self.bottom > other_box.top
+
+    def get_mutual_bbox(self, other_box: "BBox") -> "BBox":
+        return BBox(min(self.left, other_box.left), min(self.top, other_box.top), max(self.right, other_box.right),
+                    max(self.bottom, other_box.bottom))
 
 
 def get_class_id_map(background_class_name: str, class_to_color_map: dict) -> Dict[str, int]:
