@@ -1123,6 +1123,32 @@ int sis_page_render(uint8_t* segmented, uint8_t* overlay, uint8_t* boxes_on_page
 int sis_page_crops(uint8_t* out, int64_t out_bytes, const int64_t* table, int rows, const uint8_t* page, int page_channels,
                    const int32_t* region_labels, int classes, int height, int width, int mode, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * GAN training patches cut from document scans (csrc/scan_patches.h).  Pages are uint8 [height][width][3] on the
+ * device with 1 <= height, width <= 16384.  Integer arithmetic only, no atomics: two calls give the same bytes, and for 8-bit
+ * RGB they are Pillow's bytes.  Every entry declines with an error code and launches nothing outside its stated range.
+ * sis_scan_reduce (scripts/create_stylegan_train_dataset.py:45, random_resize: the reduce step inside Image.thumbnail, :167 the
+ *   same for --max-size): Pillow's reduce((fx, fy)) over the whole page -> out uint8 [ceil(height / fy)][ceil(width / fx)][3],
+ *   every output ((sum + n / 2) * m(n)) >> 24 in uint32 over the n pixels of its box that exist, m(n) = (uint32)(2^32 /
+ *   (float)(256 n)) in float arithmetic.  fx, fy >= 1, fx * fy <= 65536.
+ * sis_scan_resample_workspace_bytes (scripts/create_stylegan_train_dataset.py:45, random_resize): bytes of device workspace of
+ *   one two-pass call: in_h rows of out_w pixels, each row padded to a multiple of 4 bytes.  0 for a side outside 1..16384.
+ * sis_scan_resample (scripts/create_stylegan_train_dataset.py:45, random_resize: the resample step inside Image.thumbnail,
+ *   :167): the two-pass antialiased resample, horizontal pass first, from host-built tables on the device: per axis coef int32
+ *   [out][ksize], first int32 [out] (first source index) and count int32 [out] (taps, <= ksize).  Every output is
+ *   clip8((2^21 + sum_j source[first + j] * coef[j]) >> 22) in tap order.  ksize odd and <= 67; ksize 0 with three NULL tables
+ *   skips that axis' pass, whose size must then not change (both skipped: a copy).  The horizontal result is uint8 in the
+ *   caller's workspace (4-byte aligned, used only when both passes run).  A table entry that would leave the page is clamped.
+ * sis_scan_patches (scripts/create_stylegan_train_dataset.py:18-34, crop_patches): n windows of size x size at origins int32
+ *   [n][2] = (x, y) on the device -> out uint8 [n][size][size][3], 0 where a window leaves the page (Image.crop's black).
+ *   1 <= n <= 65535, 1 <= size <= 4096 (what sis_png_encode_pairs takes); out and origins 4-byte aligned. */
+int sis_scan_reduce(uint8_t* out, const uint8_t* page, int height, int width, int fx, int fy, void* stream);
+int64_t sis_scan_resample_workspace_bytes(int in_h, int in_w, int out_h, int out_w);
+int sis_scan_resample(uint8_t* out, const uint8_t* page, int in_h, int in_w, int out_h, int out_w, const int32_t* coef_x,
+                      const int32_t* first_x, const int32_t* count_x, int ksize_x, const int32_t* coef_y, const int32_t* first_y,
+                      const int32_t* count_y, int ksize_y, void* workspace, int64_t workspace_bytes, void* stream);
+int sis_scan_patches(uint8_t* out, const uint8_t* page, const int32_t* origins, int n, int size, int height, int width, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

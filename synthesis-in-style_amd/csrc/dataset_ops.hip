@@ -780,3 +780,6 @@ extern "C" int sis_make_image_u8(uint8_t* out, const float* x, int batch, int ch
 
 // the PNG files of the [image | label] pairs, encoded on the device (create_dataset_for_segmentation.py:84-90, save_image)
 #include "png_encode.h"
+
+// GAN training patches cut from document scans (scripts/create_stylegan_train_dataset.py:18-46, random_resize / crop_patches)
+#include "scan_patches.h"

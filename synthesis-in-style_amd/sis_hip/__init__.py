@@ -226,6 +226,10 @@ _SIGNATURES = {
     "sis_page_regions": ([_vp] * 5 + [_i] * 4 + [ctypes.c_uint32, _i, _i, _vp, _i64, _vp], _i),
     "sis_page_render": ([_vp] * 6 + [_i, _vp, _vp, _vp, _vp, _i, _vp] + [_i] * 5 + [_vp], _i),
     "sis_page_crops": ([_vp, _i64, _vp, _i, _vp, _i, _vp] + [_i] * 4 + [_vp], _i),
+    "sis_scan_reduce": ([_vp, _vp] + [_i] * 4 + [_vp], _i),
+    "sis_scan_resample_workspace_bytes": ([_i] * 4, _i64),
+    "sis_scan_resample": ([_vp, _vp] + [_i] * 4 + [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i64, _vp], _i),
+    "sis_scan_patches": ([_vp, _vp, _vp] + [_i] * 4 + [_vp], _i),
 }
 
 
@@ -3744,3 +3748,120 @@ def page_crops(page, rows, mode, region_labels=None):
                                                     _ptr(region_labels), classes, height, width, 1 if mode == "contour" else 0,
                                                     _stream())), "sis_page_crops")
     return out, offsets
+
+
+# ------------------------------------------------------------------------------ scan patches (csrc/scan_patches.h)
+
+
+def _scan_page(page, what):
+    require_device(page, "page")
+    if page.dtype != torch.uint8 or page.dim() != 3 or page.shape[2] != 3 or page.shape[0] < 1 or page.shape[1] < 1:
+        raise RuntimeError(f"{what}: a uint8 [H, W, 3] page is needed, got {page.dtype} {tuple(page.shape)}")
+    return page.contiguous()
+
+
+def scan_reduce(page, fx, fy):
+    """uint8 [H, W, 3] page (device) -> uint8 [ceil(H / fy), ceil(W / fx), 3]: Pillow's ``Image.reduce((fx, fy))``, byte for
+    byte; ragged last rows and columns are averaged over the pixels that exist.  One launch on the current stream."""
+    page = _scan_page(page, "scan_reduce")
+    h, w = int(page.shape[0]), int(page.shape[1])
+    fx, fy = int(fx), int(fy)
+    if fx < 1 or fy < 1:
+        raise RuntimeError(f"scan_reduce: factors ({fx}, {fy}) must be >= 1")
+    out = torch.empty((-(-h // fy), -(-w // fx), 3), dtype=torch.uint8, device=page.device)
+    with torch.cuda.device(page.device):
+        _check(_launch("scan_reduce_kernel", 0.0, float(page.numel() + out.numel()),
+                       lambda: lib().sis_scan_reduce(_ptr(out), _ptr(page), h, w, fx, fy, _stream())), "sis_scan_reduce")
+    return out
+
+
+def _scan_axis_tables(table, in_size, out_size, device, what):
+    """One axis' host table (utils.scan_patches.AxisTable) checked and uploaded: (coef, first, count, ksize)."""
+    if table is None:
+        return None, None, None, 0
+    coef = torch.tensor(table.coef, dtype=torch.int32).reshape(out_size, table.ksize)
+    first = torch.tensor(table.first, dtype=torch.int32).reshape(out_size)
+    count = torch.tensor(table.count, dtype=torch.int32).reshape(out_size)
+    if bool((first < 0).any()) or bool((count < 0).any()) or bool((count > table.ksize).any()) or bool((first + count > in_size).any()):
+        raise RuntimeError(f"{what}: a tap of the table leaves the {in_size} source pixels")
+    on_device = []
+    for host in (coef, first, count):
+        t = torch.empty(host.shape, dtype=torch.int32, device=device)
+        t.copy_(host)
+        on_device.append(t)
+    return on_device[0], on_device[1], on_device[2], int(table.ksize)
+
+
+def scan_resample_plan(page, plan):
+    """One two-pass antialiased resample of a uint8 [H, W, 3] page (device) from the host tables of ``plan``
+    (utils.scan_patches.ResamplePlan: output size, horizontal and vertical AxisTable, None for a pass Pillow skips) ->
+    uint8 [h, w, 3].  Horizontal pass first, its uint8 result in a workspace; at most two launches on the current stream."""
+    page = _scan_page(page, "scan_resample")
+    h, w = int(page.shape[0]), int(page.shape[1])
+    out_w, out_h = (int(v) for v in plan.size)
+    dev = page.device
+    cx, fx, nx, kx = _scan_axis_tables(plan.horizontal, w, out_w, dev, "scan_resample")
+    cy, fy, ny, ky = _scan_axis_tables(plan.vertical, h, out_h, dev, "scan_resample")
+    out = torch.empty((out_h, out_w, 3), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = None, 0
+    if kx and ky:
+        ws_bytes = int(lib().sis_scan_resample_workspace_bytes(h, w, out_h, out_w))
+        ws = torch.empty((max(ws_bytes, 4),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(_launch("scan_hpass_kernel", 0.0, float(page.numel() + 2 * ws_bytes + out.numel()),
+                       lambda: lib().sis_scan_resample(_ptr(out), _ptr(page), h, w, out_h, out_w, _ptr(cx), _ptr(fx), _ptr(nx), kx, _ptr(cy),
+                                                       _ptr(fy), _ptr(ny), ky, _ptr(ws), ws_bytes, _stream())), "sis_scan_resample")
+    return out
+
+
+def scan_resample(page, size, box=None):
+    """uint8 [H, W, 3] page (device) -> uint8 [h, w, 3] for ``size`` = (w, h): Pillow's ``Image.resize(size, BICUBIC, box=box,
+    reducing_gap=None)``, byte for byte.  The taps are built on the host (utils/scan_patches.py)."""
+    from utils import scan_patches as tables
+    page = _scan_page(page, "scan_resample")
+    for plan in tables.resize_plans(int(page.shape[1]), int(page.shape[0]), (int(size[0]), int(size[1])), box):
+        page = scan_resample_plan(page, plan)
+    return page
+
+
+def scan_thumbnail(page, size):
+    """uint8 [H, W, 3] page (device) -> what ``Image.thumbnail((size, size))`` leaves of a fully decoded RGB image, byte for
+    byte: BICUBIC, reducing_gap 2.0 (``scan_reduce`` by ``int(W / w / 2) or 1`` per axis, then ``scan_resample`` from the box
+    (0, 0, W / fx, H / fy)).  A page that already fits is returned as it is, the same tensor."""
+    from utils import scan_patches as tables
+    page = _scan_page(page, "scan_thumbnail")
+    plan = tables.thumbnail_plan(int(page.shape[1]), int(page.shape[0]), size)
+    if plan is None:
+        return page
+    if plan.factors != (1, 1):
+        page = scan_reduce(page, *plan.factors)
+    for step in plan.resamples:
+        page = scan_resample_plan(page, step)
+    return page
+
+
+def scan_patches(page, origins, size):
+    """``size`` x ``size`` windows of a uint8 [H, W, 3] page (device) at ``origins`` -- a host sequence of (x, y) or an int32
+    [n, 2] device tensor -- gathered into uint8 [n, size, size, 3], 0 outside the page (``Image.crop``'s black).  The result
+    is what ``png_encode_pairs`` takes as its images.  One table upload, one launch on the current stream."""
+    page = _scan_page(page, "scan_patches")
+    h, w = int(page.shape[0]), int(page.shape[1])
+    size = int(size)
+    dev = page.device
+    if isinstance(origins, torch.Tensor) and origins.is_cuda:
+        if origins.dtype != torch.int32 or origins.dim() != 2 or origins.shape[1] != 2 or origins.device != dev:
+            raise RuntimeError(f"scan_patches: device origins must be int32 [n, 2] on the page's device, got {origins.dtype} "
+                               f"{tuple(origins.shape)}")
+        table = origins.contiguous()
+    else:
+        host = torch.as_tensor(origins, dtype=torch.int32).reshape(-1, 2)
+        table = torch.empty(host.shape, dtype=torch.int32, device=dev)
+        table.copy_(host)
+    n = int(table.shape[0])
+    if n < 1 or size < 1:
+        raise RuntimeError(f"scan_patches: {n} windows of size {size}: both must be >= 1")
+    out = torch.empty((n, size, size, 3), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(_launch("scan_patches_kernel", 0.0, 2.0 * out.numel(),
+                       lambda: lib().sis_scan_patches(_ptr(out), _ptr(page), _ptr(table), n, size, h, w, _stream())), "sis_scan_patches")
+    return out
