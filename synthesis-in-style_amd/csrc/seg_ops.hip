@@ -13,24 +13,7 @@
 
 namespace {
 
-// PyTorch's upsample_bilinear2d source-index rule for align_corners=True: src = dst * (in-1)/(out-1),
-// i0 = (int)src, i1 = i0 + (i0 < in-1), lambda = src - i0.
-struct Lerp { int i0, i1; float l0, l1; };
-// The product is rounded to float BEFORE i0 is taken from it and subtracted from it (no contraction in here): as
-// fma(scale, dst, -i0) the lambda comes from the unrounded product while i0 comes from the rounded one, so where the rounded
-// product lands on an integer from below, l1 is a negative 1e-7 and cell i1 gets a gradient it has no part in (2e-11 where
-// the gradient is 1e-26), and every other lambda differs from the float32 rule by up to half an ulp of src.
-__device__ __forceinline__ Lerp lerp_index(int dst, float scale, int in_size) {
-#pragma clang fp contract(off)
-    const float src = scale * (float)dst;
-    Lerp r;
-    r.i0 = (int)src;
-    if (r.i0 > in_size - 1) r.i0 = in_size - 1;
-    r.i1 = r.i0 + (r.i0 < in_size - 1 ? 1 : 0);
-    r.l1 = src - (float)r.i0;
-    r.l0 = 1.f - r.l1;
-    return r;
-}
+// the source-index rule: sis_lerp_index (sis_device.h)
 
 constexpr int CE_MAXC = 32;
 
@@ -41,8 +24,8 @@ struct CeParams {
     int blocks_per_sample;
 };
 
-__device__ __forceinline__ void interp_logits(const float* __restrict__ xb, const CeParams& p, const Lerp& ly,
-                                              const Lerp& lx, float* v) {
+__device__ __forceinline__ void interp_logits(const float* __restrict__ xb, const CeParams& p, const sis_lerp& ly,
+                                              const sis_lerp& lx, float* v) {
     const int hw = p.h * p.w;
     for (int c = 0; c < p.C; ++c) {
         const float* xc = xb + (int64_t)c * hw;
@@ -65,7 +48,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(float* __restrict__ partial
         if (lab == p.ignore) continue;
         const int y = pix / p.W, xx = pix - y * p.W;
         float v[CE_MAXC];
-        interp_logits(xb, p, lerp_index(y, p.sy, p.h), lerp_index(xx, p.sx, p.w), v);
+        interp_logits(xb, p, sis_lerp_index(y, p.sy, p.h), sis_lerp_index(xx, p.sx, p.w), v);
         float m = v[0];
         for (int c = 1; c < p.C; ++c) m = fmaxf(m, v[c]);
         float s = 0.f;
@@ -116,13 +99,13 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(float* __restrict__ gx, con
     float acc[CE_MAXC];
     for (int c = 0; c < p.C; ++c) acc[c] = 0.f;
     for (int y = y_lo + sub; y <= y_hi; y += CE_BWD_SUB) {
-        const Lerp ly = lerp_index(y, p.sy, p.h);
+        const sis_lerp ly = sis_lerp_index(y, p.sy, p.h);
         float wy = 0.f;
         if (ly.i0 == i) wy += ly.l0;
         if (ly.i1 == i) wy += ly.l1;
         if (wy == 0.f) continue;
         for (int xx = x_lo; xx <= x_hi; ++xx) {
-            const Lerp lx = lerp_index(xx, p.sx, p.w);
+            const sis_lerp lx = sis_lerp_index(xx, p.sx, p.w);
             float wx = 0.f;
             if (lx.i0 == j) wx += lx.l0;
             if (lx.i1 == j) wx += lx.l1;

@@ -10,7 +10,8 @@
 #include "../../include/sis_hip.h"
 
 extern thread_local char sis_err_buf[512];
-extern thread_local const char* sis_kernel_name;  // device kernel the last sis_modconv2d* call dispatched to
+extern thread_local const char* sis_kernel_name;  // device kernel the last call of an entry point that names its kernel dispatched to
+                                                  // (the convolutions, norms, encoder, k-means, upsampling: sis_last_kernel())
 
 static inline int sis_fail(const char* fmt, ...) {
     va_list ap;

@@ -18,6 +18,27 @@ typedef __attribute__((ext_vector_type(2))) long long sis_i64x2;
 typedef unsigned short sis_u16;                                   // a bf16 / f16 element as raw bits
 typedef __attribute__((address_space(3))) void sis_lds_void;      // LDS destination of the LDS-DMA builtins
 
+// ---- the float32 source-index rule of bilinear interpolation with align_corners=True (PyTorch's upsample_bilinear2d):
+// src = dst * (in - 1) / (out - 1), i0 = (int) src, i1 = i0 + (i0 < in - 1), lambda1 = src - i0, lambda0 = 1 - lambda1.  ONE
+// definition for every kernel that interpolates (seg_ops.hip, upsample_ops.hip).
+// The product is rounded to float BEFORE i0 is taken from it and subtracted from it (no contraction in here): as
+// fma(scale, dst, -i0) the lambda comes from the unrounded product while i0 comes from the rounded one, so where the rounded
+// product lands on an integer from below, l1 is a negative 1e-7 and cell i1 gets a share it has no part in (3 -> 7 at output 3:
+// 3e-8 on a cell the rule gives weight exactly 0), and every other lambda differs from the float32 rule by up to half an ulp
+// of src.
+struct sis_lerp { int i0, i1; float l0, l1; };
+__device__ __forceinline__ sis_lerp sis_lerp_index(int dst, float scale, int in_size) {
+#pragma clang fp contract(off)
+    const float src = scale * (float)dst;
+    sis_lerp r;
+    r.i0 = (int)src;
+    if (r.i0 > in_size - 1) r.i0 = in_size - 1;
+    r.i1 = r.i0 + (r.i0 < in_size - 1 ? 1 : 0);
+    r.l1 = src - (float)r.i0;
+    r.l0 = 1.f - r.l1;
+    return r;
+}
+
 // ---- sums.  All lanes / threads get the result.
 // Sum over the 64 lanes of a wave: xor butterfly, partner distance 32, 16, 8, 4, 2, 1 in that order.
 template <typename T>

@@ -4,22 +4,11 @@
 // here the forward is one pass (x2: source tile through LDS, 16-byte stores; other ratios: each lane 4 consecutive outputs
 // of a row, the two source rows come from L2) and the backward is a gather (one lane per input pixel sums the <= 4 x 4 outputs whose footprint touches
 // it): deterministic, no atomics.  Index rule = PyTorch's: src = dst * (in - 1) / (out - 1), i0 = (int) src,
-// i1 = i0 + (i0 < in - 1), lambda1 = src - i0.  Arithmetic in fp32 for f32 / bf16 / f16 tensors.
-#include "sis_common.h"
+// i1 = i0 + (i0 < in - 1), lambda1 = src - i0, all in float32 with the product rounded before it is used (sis_lerp_index,
+// sis_device.h).  Arithmetic in fp32 for f32 / bf16 / f16 tensors.  launch_up names the kernel it launched (sis_last_kernel()).
+#include "sis_device.h"
 
 namespace {
-
-struct Lerp1 { int i0, i1; float l0, l1; };
-__device__ __forceinline__ Lerp1 lerp1(int dst, float scale, int in_size) {
-    const float src = scale * (float)dst;
-    Lerp1 r;
-    r.i0 = (int)src;
-    if (r.i0 > in_size - 1) r.i0 = in_size - 1;
-    r.i1 = r.i0 + (r.i0 < in_size - 1 ? 1 : 0);
-    r.l1 = src - (float)r.i0;
-    r.l0 = 1.f - r.l1;
-    return r;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void bilinear_up_fwd_kernel(T* __restrict__ out, const T* __restrict__ x, int h, int w,
@@ -31,7 +20,7 @@ __global__ __launch_bounds__(256) void bilinear_up_fwd_kernel(T* __restrict__ ou
         const int64_t row = i / ow4;
         const int oy = (int)(row % oh);
         const int64_t plane = row / oh;
-        const Lerp1 ly = lerp1(oy, sy, h);
+        const sis_lerp ly = sis_lerp_index(oy, sy, h);
         const T* r0 = x + (plane * h + ly.i0) * w;
         const T* r1 = x + (plane * h + ly.i1) * w;
         T* o = out + (plane * oh + oy) * (int64_t)ow + 4 * c4;
@@ -39,7 +28,7 @@ __global__ __launch_bounds__(256) void bilinear_up_fwd_kernel(T* __restrict__ ou
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int ox = 4 * c4 + e;
-            const Lerp1 lx = lerp1(ox < ow ? ox : ow - 1, sx, w);
+            const sis_lerp lx = sis_lerp_index(ox < ow ? ox : ow - 1, sx, w);
             v[e] = ly.l0 * (lx.l0 * sis_ld(r0, lx.i0) + lx.l1 * sis_ld(r0, lx.i1)) +
                    ly.l1 * (lx.l0 * sis_ld(r1, lx.i0) + lx.l1 * sis_ld(r1, lx.i1));
         }
@@ -79,8 +68,9 @@ __global__ __launch_bounds__(256) void bilinear_up2_fwd_tiled_kernel(T* __restri
     const int64_t plane = b / tiles_y;
     const int oy0 = ty_i * UF_OR, ox0 = tx_i * UF_OC;
     const int oy1 = min(oh, oy0 + UF_OR) - 1, ox1 = min(ow, ox0 + UF_OC) - 1;   // last output row / column of the tile
-    const int r_lo = lerp1(oy0, sy, h).i0, r_hi = lerp1(oy1, sy, h).i1;         // <= UF_SR rows: src advances < 1/2 per output
-    const int c_lo = lerp1(ox0, sx, w).i0, c_hi = lerp1(ox1, sx, w).i1;
+    // <= UF_SR rows / UF_SC columns: src advances < 1/2 per output (test_upsample_cases_cpu.py checks every size up to 4096)
+    const int r_lo = sis_lerp_index(oy0, sy, h).i0, r_hi = sis_lerp_index(oy1, sy, h).i1;
+    const int c_lo = sis_lerp_index(ox0, sx, w).i0, c_hi = sis_lerp_index(ox1, sx, w).i1;
     const int nr = r_hi - r_lo + 1, nc = c_hi - c_lo + 1;
     const T* src = x + plane * h * (int64_t)w;
     for (int e = threadIdx.x; e < nr * nc; e += 256) {
@@ -99,13 +89,13 @@ __global__ __launch_bounds__(256) void bilinear_up2_fwd_tiled_kernel(T* __restri
     float xl0[8], xl1[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        const Lerp1 lx = lerp1(min(ox + k, ow - 1), sx, w);
+        const sis_lerp lx = sis_lerp_index(min(ox + k, ow - 1), sx, w);
         xa[k] = lx.i0 - c_lo; xb[k] = lx.i1 - c_lo; xl0[k] = lx.l0; xl1[k] = lx.l1;
     }
     for (int ry = threadIdx.x / GROUPS; ry < UF_OR; ry += 256 / GROUPS) {
         const int oy = oy0 + ry;
         if (oy >= oh) break;
-        const Lerp1 ly = lerp1(oy, sy, h);
+        const sis_lerp ly = sis_lerp_index(oy, sy, h);
         const float* t0 = tile[ly.i0 - r_lo];
         const float* t1 = tile[ly.i1 - r_lo];
         float v[8];
@@ -160,7 +150,7 @@ __global__ __launch_bounds__(256) void bilinear_up_bwd_kernel(T* __restrict__ gx
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
             const int ox = ox_lo + k;
-            const Lerp1 lx = lerp1(ox <= ox_hi ? ox : ox_hi, sx, w);
+            const sis_lerp lx = sis_lerp_index(ox <= ox_hi ? ox : ox_hi, sx, w);
             float wx = 0.f;
             if (ox <= ox_hi && lx.i0 == xx) wx += lx.l0;
             if (ox <= ox_hi && lx.i1 == xx) wx += lx.l1;
@@ -170,7 +160,7 @@ __global__ __launch_bounds__(256) void bilinear_up_bwd_kernel(T* __restrict__ gx
         for (int j = 0; j < 6; ++j) {
             const int oy = oy_lo + j;
             if (oy > oy_hi) break;
-            const Lerp1 ly = lerp1(oy, sy, h);
+            const sis_lerp ly = sis_lerp_index(oy, sy, h);
             float wy = 0.f;
             if (ly.i0 == y) wy += ly.l0;
             if (ly.i1 == y) wy += ly.l1;
@@ -186,14 +176,14 @@ __global__ __launch_bounds__(256) void bilinear_up_bwd_kernel(T* __restrict__ gx
         return;
     }
     for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-        const Lerp1 ly = lerp1(oy, sy, h);
+        const sis_lerp ly = sis_lerp_index(oy, sy, h);
         float wy = 0.f;
         if (ly.i0 == y) wy += ly.l0;
         if (ly.i1 == y) wy += ly.l1;
         if (wy == 0.f) continue;
         float racc = 0.f;
         for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-            const Lerp1 lx = lerp1(ox, sx, w);
+            const sis_lerp lx = sis_lerp_index(ox, sx, w);
             float wx = 0.f;
             if (lx.i0 == xx) wx += lx.l0;
             if (lx.i1 == xx) wx += lx.l1;
@@ -256,7 +246,7 @@ __global__ __launch_bounds__(256) void bilinear_up2_bwd_tiled_kernel(T* __restri
         const int oy = oy0 + r, y = y0 + ty;
         float wgt = 0.f;
         if (oy >= 0 && oy < oh && y < h) {
-            const Lerp1 ly = lerp1(oy, sy, h);
+            const sis_lerp ly = sis_lerp_index(oy, sy, h);
             if (ly.i0 == y) wgt += ly.l0;
             if (ly.i1 == y) wgt += ly.l1;
         }
@@ -285,7 +275,7 @@ __global__ __launch_bounds__(256) void bilinear_up2_bwd_tiled_kernel(T* __restri
             for (int k = 0; k < 6; ++k) {  // outputs 2x - 3 .. 2x + 2
                 const int ox = 2 * x - 3 + k;
                 if (ox >= 0 && ox < ow) {
-                    const Lerp1 lx = lerp1(ox, sx, w);
+                    const sis_lerp lx = sis_lerp_index(ox, sx, w);
                     float wgt = 0.f;
                     if (lx.i0 == x) wgt += lx.l0;
                     if (lx.i1 == x) wgt += lx.l1;
@@ -410,7 +400,7 @@ __global__ __launch_bounds__(256) void bilinear_up2_fwd_direct_kernel(T* __restr
 
 // Backward of the same: a lane owns 4 source columns of RP consecutive source rows (RP = 2 when h is even: the 2 RP + 2 output rows
 // 2 i0 - 1 .. 2 i0 + 2 RP they gather from are loaded once for both -- 6 row loads per 2 source rows instead of 8); columns
-// 8g - 1 .. 8g + 8.  Weights by the index rule itself (lerp1 + comparison, as bilinear_up_bwd_kernel): a candidate that does not
+// 8g - 1 .. 8g + 8.  Weights by the index rule itself (sis_lerp_index + comparison, as bilinear_up_bwd_kernel): a candidate that does not
 // reference the pixel gets weight 0, the clamped last column / row gets both of its weights.
 template <typename T, int RP>
 __global__ __launch_bounds__(256) void bilinear_up2_bwd_direct_kernel(T* __restrict__ gx, const T* __restrict__ gout, int h, int w,
@@ -435,7 +425,7 @@ __global__ __launch_bounds__(256) void bilinear_up2_bwd_direct_kernel(T* __restr
             const int ox = 2 * j - 1 + k;
             float wgt = 0.f;
             if (ox >= 0 && ox < ow) {
-                const Lerp1 lx = lerp1(ox, sx, w);
+                const sis_lerp lx = sis_lerp_index(ox, sx, w);
                 if (lx.i0 == j) wgt += lx.l0;
                 if (lx.i1 == j) wgt += lx.l1;
             }
@@ -457,7 +447,7 @@ __global__ __launch_bounds__(256) void bilinear_up2_bwd_direct_kernel(T* __restr
         for (int q = 0; q < RP; ++q) {   // source row i0 + q gathers output rows 2 (i0 + q) - 1 .. + 2 = r in [2q, 2q + 3]
             wy[q] = 0.f;
             if (in && r >= 2 * q && r <= 2 * q + 3) {
-                const Lerp1 ly = lerp1(oy, sy, h);
+                const sis_lerp ly = sis_lerp_index(oy, sy, h);
                 if (ly.i0 == i0 + q) wy[q] += ly.l0;
                 if (ly.i1 == i0 + q) wy[q] += ly.l1;
             }
@@ -513,15 +503,18 @@ int launch_up(void* out, const void* x, int64_t planes, int h, int w, int oh, in
             hipLaunchKernelGGL(bilinear_up2_fwd_direct_kernel<T>, dim3(blocks), dim3(256), 0, st, (T*)out, (const T*)x, h, w, sy, sx, total,
                                planes_per_image, image_stride);
             SIS_CHECK_LAUNCH("bilinear_up2_fwd_direct_kernel");
+            sis_kernel_name = "bilinear_up2_fwd_direct_kernel";
         } else if (h % 2 == 0) {
             const int64_t total2 = total / 2;
             hipLaunchKernelGGL((bilinear_up2_bwd_direct_kernel<T, 2>), dim3((unsigned)((total2 + 255) / 256)), dim3(256), 0, st, (T*)out,
                                (const T*)x, h, w, sy, sx, total2, planes_per_image, image_stride);
             SIS_CHECK_LAUNCH("bilinear_up2_bwd_direct_kernel");
+            sis_kernel_name = "bilinear_up2_bwd_direct_kernel";
         } else {
             hipLaunchKernelGGL((bilinear_up2_bwd_direct_kernel<T, 1>), dim3(blocks), dim3(256), 0, st, (T*)out, (const T*)x, h, w, sy, sx, total,
                                planes_per_image, image_stride);
             SIS_CHECK_LAUNCH("bilinear_up2_bwd_direct_kernel");
+            sis_kernel_name = "bilinear_up2_bwd_direct_kernel";
         }
         return 0;
     }
@@ -531,6 +524,7 @@ int launch_up(void* out, const void* x, int64_t planes, int h, int w, int oh, in
             hipLaunchKernelGGL(bilinear_up2_fwd_tiled_kernel<T>, dim3((unsigned)(planes * tiles_x * tiles_y)), dim3(256), 0, st,
                                (T*)out, (const T*)x, h, w, oh, ow, sy, sx, tiles_x, tiles_y, planes_per_image, image_stride);
             SIS_CHECK_LAUNCH("bilinear_up2_fwd_tiled_kernel");
+            sis_kernel_name = "bilinear_up2_fwd_tiled_kernel";
             return 0;
         }
         SIS_REQUIRE(dense, "sis_upsample_bilinear: a strided result needs the x2 case");
@@ -539,18 +533,21 @@ int launch_up(void* out, const void* x, int64_t planes, int h, int w, int oh, in
         hipLaunchKernelGGL(bilinear_up_fwd_kernel<T>, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st,
                            (T*)out, (const T*)x, h, w, oh, ow, sy, sx, total4);
         SIS_CHECK_LAUNCH("bilinear_up_fwd_kernel");
+        sis_kernel_name = "bilinear_up_fwd_kernel";
     } else if (x2 && ow % 8 == 0 && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) && image_stride % 8 == 0 &&
                planes * sis_cdiv(w, UB_TX) * sis_cdiv(h, UB_TY) < ((int64_t)1 << 31)) {
         const int tiles_x = sis_cdiv(w, UB_TX), tiles_y = sis_cdiv(h, UB_TY);
         hipLaunchKernelGGL(bilinear_up2_bwd_tiled_kernel<T>, dim3((unsigned)(planes * tiles_x * tiles_y)), dim3(256), 0, st,
                            (T*)out, (const T*)x, h, w, oh, ow, sy, sx, tiles_x, tiles_y, planes_per_image, image_stride);
         SIS_CHECK_LAUNCH("bilinear_up2_bwd_tiled_kernel");
+        sis_kernel_name = "bilinear_up2_bwd_tiled_kernel";
     } else {  // out = grad_x [planes][h][w], x = grad_out [planes][oh][ow]
         SIS_REQUIRE(dense, "sis_upsample_bilinear: a strided gradient needs the aligned x2 case");
         const int64_t total = planes * h * w;
         hipLaunchKernelGGL(bilinear_up_bwd_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (T*)out,
                            (const T*)x, h, w, oh, ow, sy, sx, total);
         SIS_CHECK_LAUNCH("bilinear_up_bwd_kernel");
+        sis_kernel_name = "bilinear_up_bwd_kernel";
     }
     return 0;
 }

@@ -2,12 +2,23 @@
 and backward, f32 / bf16 / f16.  The interpolation weights are formed in fp32 exactly as ATen forms them (src = dst * scale):
 against a float64 reference both this kernel and ATen's fp32 kernel sit at ~1e-5 on unit-variance data (measured
 1.04e-5 vs 1.08e-5 at 64 -> 128), hence atol 4e-5; 16-bit types: one rounding of the fp32 result."""
+import os
+
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
+
+
+def _ran(direct, tiled):
+    """The x2 kernel the last call must have run: ``direct``, or ``tiled`` in a process started with SIS_UP2_DIRECT=0 (the A/B
+    run of test_switches_gpu.py; the library reads the switch as its first character, once)."""
+    import sis_hip
+    off = os.environ.get("SIS_UP2_DIRECT", "")[:1] == "0"
+    name = sis_hip.lib().sis_last_kernel().decode()
+    assert name == (tiled if off else direct), name
 
 
 @pytest.mark.parametrize("shape,size", [((2, 3, 8, 8), (16, 16)), ((1, 5, 7, 9), (14, 18)), ((2, 4, 16, 12), (32, 27)),
@@ -56,8 +67,10 @@ def test_x2_forward_tiles(device, shape):
     # by up to ~4e-5, times the difference of two unit-variance neighbours -> atol 3e-4 against float64 (measured 7.3e-5 here,
     # ATen's own fp32 kernel 1.3e-4 on the same input)
     y = sis_hip.upsample_bilinear(x, *size)
+    _ran("bilinear_up2_fwd_tiled_kernel", "bilinear_up2_fwd_tiled_kernel")
     np.testing.assert_allclose(y.cpu().numpy(), ref.float().cpu().numpy(), rtol=1e-5, atol=3e-4)
     yb = sis_hip.upsample_bilinear(x.bfloat16(), *size)
+    _ran("bilinear_up2_fwd_tiled_kernel", "bilinear_up2_fwd_tiled_kernel")
     refb = F.interpolate(x.bfloat16().double(), size=size, mode="bilinear", align_corners=True)
     np.testing.assert_allclose(yb.float().cpu().numpy(), refb.float().cpu().numpy(), rtol=1e-2, atol=1e-2)
 
@@ -66,7 +79,9 @@ def test_x2_forward_tiles(device, shape):
 def test_x2_direct_kernels(device, shape):
     """The LDS-free x2 kernels (csrc/upsample_ops.hip, bilinear_up2_*_direct_kernel: static source indices, 4 source columns per
     lane, neighbours by wave shuffle): rows narrower than a wave (several rows per wave), exactly a wave, wider than a wave (the
-    neighbour across the wave boundary is loaded), two-row planes -- forward and backward against float64, f32 and bf16."""
+    neighbour across the wave boundary is loaded), two-row planes -- forward and backward against float64, f32 and bf16.  The kernel
+    that ran is asserted: the direct one, or with SIS_UP2_DIRECT=0 the tiled one (ow % 8 == 0 at every shape here).  The
+    element-wise float64 bounds of these kernels are test_upsample_cases_gpu.py's."""
     import sis_hip
     g = torch.Generator().manual_seed(shape[2] + shape[3])
     x = torch.randn(*shape, generator=g).to(device)
@@ -76,16 +91,20 @@ def test_x2_direct_kernels(device, shape):
     ref = F.interpolate(xr, size=size, mode="bilinear", align_corners=True)
     ref.backward(gy.double())
     y = sis_hip.upsample_bilinear(x, *size)
+    _ran("bilinear_up2_fwd_direct_kernel", "bilinear_up2_fwd_tiled_kernel")
     np.testing.assert_allclose(y.cpu().numpy(), ref.detach().float().cpu().numpy(), rtol=1e-5, atol=3e-4)
     gx = sis_hip.upsample_bilinear(x, *size, grad_output=gy)
+    _ran("bilinear_up2_bwd_direct_kernel", "bilinear_up2_bwd_tiled_kernel")
     np.testing.assert_allclose(gx.cpu().numpy(), xr.grad.float().cpu().numpy(), rtol=1e-5, atol=1e-3)
     xb, gb = x.bfloat16(), gy.bfloat16()
     xbr = xb.double().requires_grad_(True)
     refb = F.interpolate(xbr, size=size, mode="bilinear", align_corners=True)
     refb.backward(gb.double())
     yb = sis_hip.upsample_bilinear(xb, *size)
+    _ran("bilinear_up2_fwd_direct_kernel", "bilinear_up2_fwd_tiled_kernel")
     np.testing.assert_allclose(yb.float().cpu().numpy(), refb.detach().float().cpu().numpy(), rtol=1e-2, atol=1e-2)
     gxb = sis_hip.upsample_bilinear(xb, *size, grad_output=gb)
+    _ran("bilinear_up2_bwd_direct_kernel", "bilinear_up2_bwd_tiled_kernel")
     np.testing.assert_allclose(gxb.float().cpu().numpy(), xbr.grad.float().cpu().numpy(), rtol=1e-2, atol=4e-2)
     assert torch.equal(y, sis_hip.upsample_bilinear(x, *size)) and torch.equal(gx, sis_hip.upsample_bilinear(x, *size, grad_output=gy))
 
