@@ -19,15 +19,13 @@ namespace {
 
 constexpr int PK = 64;  // pixels per chunk (one 256-byte row piece per channel)
 
-constexpr int PWG_JOBS_MAX = 16;   // layers of one shape per launch (grid.z), operands through pointer tables
-
 struct PwgParams {
     const float* gy; const float* x; float* out;  // out: dW or the slab of slice 0
     int B, Cout, Cin, HW;
     int chunks_total, chunks_per_slice;
     int64_t slab_stride;  // floats between slices (0: single slice, out = dW)
     int jobs;             // > 0: grid.z layers of this shape: gy / x / out from the tables (out of layer z: its dW or its first slab)
-    const float* gyj[PWG_JOBS_MAX]; const float* xj[PWG_JOBS_MAX]; float* outj[PWG_JOBS_MAX];
+    const float* gyj[SIS_JOBS_MAX]; const float* xj[SIS_JOBS_MAX]; float* outj[SIS_JOBS_MAX];
 };
 
 // WM x WN waves of MB stacked 32 x 32 tiles each: TM = 32 WM MB output channels, TN = 32 WN input channels
@@ -134,7 +132,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_wgrad_f32_kernel(const PwgPara
 // dW[i] = sum over slices, in a fixed order (8 interleaved partial sums, then their fixed tree): deterministic.  One float
 // per lane and 8 independent loads in flight per trip: the sum is latency bound otherwise (a float4 per lane walking 64
 // slices one after the other took longer than the GEMM for the 128 -> 512 layers).
-struct PwgDwTab { float* dw[PWG_JOBS_MAX]; };
+using PwgDwTab = SisJobTab<float>;
 
 __global__ __launch_bounds__(256) void conv1x1_wgrad_reduce_kernel(float* __restrict__ dw, const float* __restrict__ slab,
                                                                    int n_slices, int64_t n, int64_t slab_job_stride = 0,
@@ -252,23 +250,22 @@ static int pwg_jobs(float* const* dw, const float* const* gy, const float* const
     return 0;
 }
 
-extern "C" int sis_conv1x1_wgrad_f32(float* dw, const float* gy, const float* x, int batch, int cin, int cout, int hw,
-                                     void* workspace, int64_t workspace_bytes, void* stream) {
-    SIS_REQUIRE(dw && gy && x, "sis_conv1x1_wgrad_f32: null pointer");
-    return pwg_jobs(&dw, &gy, &x, 1, batch, cin, cout, hw, workspace, workspace_bytes, stream, "sis_conv1x1_wgrad_f32");
-}
-
-/* The same for n_jobs layers of ONE shape (EMANet's repeated bottleneck units, queued during the backward): `dw`, `gy`, `x` are
- * HOST arrays of n_jobs device pointers; one tile launch (grid.z = layer) + one reduction launch per <= 16 layers, the K slices
- * planned for the layers' joint tile count (fewer, longer slices per layer: less slab traffic). */
+/* n_jobs layers of ONE shape (EMANet's repeated bottleneck units, queued during the backward): `dw`, `gy`, `x` are HOST arrays of
+ * n_jobs device pointers; one tile launch (grid.z = layer) + one reduction launch per <= 16 layers, the K slices planned for the
+ * layers' joint tile count (fewer, longer slices per layer: less slab traffic). */
 extern "C" int sis_conv1x1_wgrad_f32_multi(float* const* dw, const float* const* gy, const float* const* x, int n_jobs, int batch, int cin,
                                            int cout, int hw, void* workspace, int64_t workspace_bytes, void* stream) {
     if (n_jobs <= 0) return 0;
     SIS_REQUIRE(dw && gy && x, "sis_conv1x1_wgrad_f32_multi: null pointer");
-    for (int j0 = 0; j0 < n_jobs; j0 += PWG_JOBS_MAX) {
-        const int n = n_jobs - j0 < PWG_JOBS_MAX ? n_jobs - j0 : PWG_JOBS_MAX;
-        const int rc = pwg_jobs(dw + j0, gy + j0, x + j0, n, batch, cin, cout, hw, workspace, workspace_bytes, stream, "sis_conv1x1_wgrad_f32_multi");
-        if (rc) return rc;
-    }
-    return 0;
+    return sis_run_jobs(
+        n_jobs, [](int) { return true; },   // any count fits: pwg_jobs cuts the K slices to the workspace it gets
+        [&](int j0, int n) {
+            return pwg_jobs(dw + j0, gy + j0, x + j0, n, batch, cin, cout, hw, workspace, workspace_bytes, stream, "sis_conv1x1_wgrad_f32_multi");
+        });
+}
+
+/* One layer: the one-job case of sis_conv1x1_wgrad_f32_multi. */
+extern "C" int sis_conv1x1_wgrad_f32(float* dw, const float* gy, const float* x, int batch, int cin, int cout, int hw,
+                                     void* workspace, int64_t workspace_bytes, void* stream) {
+    return sis_conv1x1_wgrad_f32_multi(&dw, &gy, &x, 1, batch, cin, cout, hw, workspace, workspace_bytes, stream);
 }

@@ -47,15 +47,13 @@ struct WgCfg {
     static_assert(LDS <= 160 * 1024, "LDS");
 };
 
-constexpr int WG_JOBS_MAX = 16;   // layers of one shape per launch (grid.z), operands through pointer tables
-
 struct WgParams {
     const sis_u16* x;    // [N, Cin, H, W]
     const sis_u16* gy;   // [N, Cout, H, W]
     float* slab;     // [units][9][co_pad][ci_pad]
     int jobs;        // > 0: grid.z layers of this shape: x / gy from the tables, slab of layer z at slab + z * slab_job_stride
     long long slab_job_stride;
-    const sis_u16* xj[WG_JOBS_MAX]; const sis_u16* gyj[WG_JOBS_MAX];
+    const sis_u16* xj[SIS_JOBS_MAX]; const sis_u16* gyj[SIS_JOBS_MAX];
     int N, Cin, Cout, H, W;
     int strips, row_blocks, rows_per_block;
     int co_tiles, ci_tiles;
@@ -115,6 +113,7 @@ __global__ __launch_bounds__(C::THREADS, 2) void conv_wgrad_bf16_kernel(WgParams
     const int x0 = strip * C::SW;
     const int y_begin = rb * p.rows_per_block, y_end = min(p.H, y_begin + p.rows_per_block);
     const int64_t plane = (int64_t)p.H * p.W;
+    // (one layer keeps its scalar operands, jobs = 0: reading the table always would change this code -- left for a measured change)
     const sis_u16* gy_base = (p.jobs ? p.gyj[blockIdx.z] : p.gy) + ((int64_t)n * p.Cout + co_t * C::MT) * plane;
     const sis_u16* x_base = (p.jobs ? p.xj[blockIdx.z] : p.x) + ((int64_t)n * p.Cin + ci_t * C::NT) * plane;
 
@@ -260,7 +259,7 @@ __global__ __launch_bounds__(C::THREADS, 2) void conv_wgrad_bf16_kernel(WgParams
 
 // dW[co][ci][tap] = sum over units of slab[unit][tap][co][ci].  One workgroup per (tap, co, 64 input channels): the
 // four waves add units w, w + 4, ... in order (coalesced 256-byte reads), then (s0 + s1) + (s2 + s3): a fixed order.
-struct WgDwTab { void* dw[WG_JOBS_MAX]; };
+using WgDwTab = SisJobTab<void>;
 
 template <typename T>
 __global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(T* __restrict__ dw, const float* __restrict__ slab, int units,
@@ -314,7 +313,7 @@ struct PwCfg {
 struct PwParams {
     const sis_u16* x; const sis_u16* gy; float* slab;
     int jobs; long long slab_job_stride;   // as WgParams
-    const sis_u16* xj[WG_JOBS_MAX]; const sis_u16* gyj[WG_JOBS_MAX];
+    const sis_u16* xj[SIS_JOBS_MAX]; const sis_u16* gyj[SIS_JOBS_MAX];
     int N, Cin, Cout, P;              // P = pixels per plane
     int units_per_image, unit_len;    // unit u: image u / units_per_image, pixels [k * unit_len, min(P, (k + 1) * unit_len))
     int co_tiles, ci_tiles;
@@ -533,6 +532,20 @@ int launch_wgrad(const WgParams& p, int units, hipStream_t st, const char* name)
     return 0;
 }
 
+// The reduction of n_jobs layers' slabs to their dW (float32 or bfloat16), for both families (taps = 9 / 1).
+int launch_wgrad_reduce(void* const* dw, int dw_dtype, const SisJobTab<void>& tab, int n_jobs, const void* workspace, int units, int cout,
+                        int cin, int co_pad, int ci_pad, int taps, long long stride, hipStream_t st) {
+    const dim3 grid(taps * cout * sis_cdiv(cin, 64), n_jobs);
+    if (dw_dtype == SIS_F32)
+        hipLaunchKernelGGL(conv_wgrad_reduce_kernel<float>, grid, dim3(256), 0, st, (float*)dw[0], (const float*)workspace, units, cout, cin,
+                           co_pad, ci_pad, taps, stride, tab);
+    else
+        hipLaunchKernelGGL(conv_wgrad_reduce_kernel<__hip_bfloat16>, grid, dim3(256), 0, st, (__hip_bfloat16*)dw[0], (const float*)workspace,
+                           units, cout, cin, co_pad, ci_pad, taps, stride, tab);
+    SIS_CHECK_LAUNCH("conv_wgrad_reduce_kernel");
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int sis_conv_bf16_wgrad_supported(int batch, int cin, int cout, int h, int w, int64_t workspace_bytes) {
@@ -574,52 +587,31 @@ static int conv_wgrad_jobs(void* const* dw, int dw_dtype, const void* const* x, 
     else if (pl.ks == 16) rc = launch_wgrad<WgCfg<1, 1, 16>>(p, pl.units, st, "conv_wgrad_bf16_kernel<1,1,16>");
     else rc = launch_wgrad<WgCfg<1, 1, 8>>(p, pl.units, st, "conv_wgrad_bf16_kernel<1,1,8>");
     if (rc) return rc;
-    const int mt = 32 * pl.wm, nt = 32 * pl.wn;
-    const int blocks = 9 * cout * sis_cdiv(cin, 64);
-    const long long stride = p.jobs ? p.slab_job_stride : 0;
-    if (dw_dtype == SIS_F32)
-        hipLaunchKernelGGL(conv_wgrad_reduce_kernel<float>, dim3(blocks, n_jobs), dim3(256), 0, st, (float*)dw[0], (const float*)workspace,
-                           pl.partials, cout, cin, pl.co_tiles * mt, pl.ci_tiles * nt, 9, stride, tab);
-    else
-        hipLaunchKernelGGL(conv_wgrad_reduce_kernel<__hip_bfloat16>, dim3(blocks, n_jobs), dim3(256), 0, st, (__hip_bfloat16*)dw[0],
-                           (const float*)workspace, pl.partials, cout, cin, pl.co_tiles * mt, pl.ci_tiles * nt, 9, stride, tab);
-    SIS_CHECK_LAUNCH("conv_wgrad_reduce_kernel");
-    return 0;
+    return launch_wgrad_reduce(dw, dw_dtype, tab, n_jobs, workspace, pl.partials, cout, cin, pl.co_tiles * 32 * pl.wm, pl.ci_tiles * 32 * pl.wn,
+                               9, p.jobs ? p.slab_job_stride : 0, st);
 }
 
-// layers per launch: at most WG_JOBS_MAX, and as many as leave every layer its slabs in the workspace
-template <typename PlanFits>
-static int jobs_per_launch(int n_jobs, PlanFits fits) {
-    int n = n_jobs < WG_JOBS_MAX ? n_jobs : WG_JOBS_MAX;
-    while (n > 1 && !fits(n)) n = (n + 1) / 2;
-    return n;
-}
-
-extern "C" int sis_conv_bf16_wgrad(void* dw, int dw_dtype, const void* x, const void* grad_y, int batch, int cin, int cout,
-                                   int h, int w, void* workspace, int64_t workspace_bytes, void* stream) {
-    if (batch <= 0) return 0;
-    SIS_REQUIRE(dw && x && grad_y && workspace, "sis_conv_bf16_wgrad: null pointer");
-    SIS_REQUIRE(dw_dtype == SIS_F32 || dw_dtype == SIS_BF16, "sis_conv_bf16_wgrad: dW must be float32 or bfloat16");
-    return conv_wgrad_jobs(&dw, dw_dtype, &x, &grad_y, 1, batch, cin, cout, h, w, workspace, workspace_bytes, stream, "sis_conv_bf16_wgrad");
-}
-
-/* The same for n_jobs layers of ONE shape (the trunk's repeated bottleneck units, queued during the backward): `dw`, `x`,
- * `grad_y` are HOST arrays of n_jobs device pointers.  One tile launch + one reduction launch per <= 16 layers; the tile plan
- * counts the layers' workgroups together, so every layer is cut into fewer, longer units than it would be alone. */
+/* n_jobs layers of ONE shape (the trunk's repeated bottleneck units, queued during the backward): `dw`, `x`, `grad_y` are HOST
+ * arrays of n_jobs device pointers.  One tile launch + one reduction launch per <= 16 layers; the tile plan counts the layers'
+ * workgroups together, so every layer is cut into fewer, longer units than it would be alone. */
 extern "C" int sis_conv_bf16_wgrad_multi(void* const* dw, int dw_dtype, const void* const* x, const void* const* grad_y, int n_jobs,
                                          int batch, int cin, int cout, int h, int w, void* workspace, int64_t workspace_bytes, void* stream) {
     if (batch <= 0 || n_jobs <= 0) return 0;
     SIS_REQUIRE(dw && x && grad_y && workspace, "sis_conv_bf16_wgrad_multi: null pointer");
     SIS_REQUIRE(dw_dtype == SIS_F32 || dw_dtype == SIS_BF16, "sis_conv_bf16_wgrad_multi: dW must be float32 or bfloat16");
-    for (int j0 = 0; j0 < n_jobs;) {
-        const int left = n_jobs - j0;
-        const int n = jobs_per_launch(left, [&](int k) { WgPlan pl; return wgrad_plan(batch, cin, cout, h, w, workspace_bytes, &pl, k); });
-        const int rc = conv_wgrad_jobs(dw + j0, dw_dtype, x + j0, grad_y + j0, n, batch, cin, cout, h, w, workspace, workspace_bytes, stream,
-                                       "sis_conv_bf16_wgrad_multi");
-        if (rc) return rc;
-        j0 += n;
-    }
-    return 0;
+    return sis_run_jobs(
+        n_jobs, [&](int n) { WgPlan pl; return wgrad_plan(batch, cin, cout, h, w, workspace_bytes, &pl, n); },
+        [&](int j0, int n) {
+            return conv_wgrad_jobs(dw + j0, dw_dtype, x + j0, grad_y + j0, n, batch, cin, cout, h, w, workspace, workspace_bytes, stream,
+                                   "sis_conv_bf16_wgrad_multi");
+        });
+}
+
+/* One layer: the one-job case of sis_conv_bf16_wgrad_multi. */
+extern "C" int sis_conv_bf16_wgrad(void* dw, int dw_dtype, const void* x, const void* grad_y, int batch, int cin, int cout,
+                                   int h, int w, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (batch <= 0) return 0;
+    return sis_conv_bf16_wgrad_multi(&dw, dw_dtype, &x, &grad_y, 1, batch, cin, cout, h, w, workspace, workspace_bytes, stream);
 }
 
 /* 1x1 stride-1 layers: dW [Cout][Cin] (float32 or bfloat16) from bf16 NCHW x [B][Cin][pixels] and dL/dy [B][Cout][pixels]. */
@@ -654,25 +646,8 @@ static int conv1x1_wgrad_jobs(void* const* dw, int dw_dtype, const void* const* 
     else if (pl.wn == 2) rc = launch_pw<PwCfg<1, 2, 1>>(p, pl.units, aligned, st);
     else rc = launch_pw<PwCfg<1, 1, 1>>(p, pl.units, aligned, st);
     if (rc) return rc;
-    const int mt = 64 * pl.wm, nt = 64 * pl.wn;
-    const int blocks = cout * sis_cdiv(cin, 64);
-    const long long stride = p.jobs ? p.slab_job_stride : 0;
-    if (dw_dtype == SIS_F32)
-        hipLaunchKernelGGL(conv_wgrad_reduce_kernel<float>, dim3(blocks, n_jobs), dim3(256), 0, st, (float*)dw[0], (const float*)workspace,
-                           pl.units, cout, cin, pl.co_tiles * mt, pl.ci_tiles * nt, 1, stride, tab);
-    else
-        hipLaunchKernelGGL(conv_wgrad_reduce_kernel<__hip_bfloat16>, dim3(blocks, n_jobs), dim3(256), 0, st, (__hip_bfloat16*)dw[0],
-                           (const float*)workspace, pl.units, cout, cin, pl.co_tiles * mt, pl.ci_tiles * nt, 1, stride, tab);
-    SIS_CHECK_LAUNCH("conv_wgrad_reduce_kernel");
-    return 0;
-}
-
-extern "C" int sis_conv1x1_bf16_wgrad(void* dw, int dw_dtype, const void* x, const void* grad_y, int batch, int cin, int cout,
-                                      int pixels, void* workspace, int64_t workspace_bytes, void* stream) {
-    if (batch <= 0) return 0;
-    SIS_REQUIRE(dw && x && grad_y && workspace, "sis_conv1x1_bf16_wgrad: null pointer");
-    SIS_REQUIRE(dw_dtype == SIS_F32 || dw_dtype == SIS_BF16, "sis_conv1x1_bf16_wgrad: dW must be float32 or bfloat16");
-    return conv1x1_wgrad_jobs(&dw, dw_dtype, &x, &grad_y, 1, batch, cin, cout, pixels, workspace, workspace_bytes, stream, "sis_conv1x1_bf16_wgrad");
+    return launch_wgrad_reduce(dw, dw_dtype, tab, n_jobs, workspace, pl.units, cout, cin, pl.co_tiles * 64 * pl.wm, pl.ci_tiles * 64 * pl.wn, 1,
+                               p.jobs ? p.slab_job_stride : 0, st);
 }
 
 extern "C" int sis_conv1x1_bf16_wgrad_multi(void* const* dw, int dw_dtype, const void* const* x, const void* const* grad_y, int n_jobs,
@@ -681,13 +656,17 @@ extern "C" int sis_conv1x1_bf16_wgrad_multi(void* const* dw, int dw_dtype, const
     if (batch <= 0 || n_jobs <= 0) return 0;
     SIS_REQUIRE(dw && x && grad_y && workspace, "sis_conv1x1_bf16_wgrad_multi: null pointer");
     SIS_REQUIRE(dw_dtype == SIS_F32 || dw_dtype == SIS_BF16, "sis_conv1x1_bf16_wgrad_multi: dW must be float32 or bfloat16");
-    for (int j0 = 0; j0 < n_jobs;) {
-        const int left = n_jobs - j0;
-        const int n = jobs_per_launch(left, [&](int k) { PwPlan pl; return pw_plan(batch, cin, cout, pixels, workspace_bytes, &pl, k); });
-        const int rc = conv1x1_wgrad_jobs(dw + j0, dw_dtype, x + j0, grad_y + j0, n, batch, cin, cout, pixels, workspace, workspace_bytes, stream,
-                                          "sis_conv1x1_bf16_wgrad_multi");
-        if (rc) return rc;
-        j0 += n;
-    }
-    return 0;
+    return sis_run_jobs(
+        n_jobs, [&](int n) { PwPlan pl; return pw_plan(batch, cin, cout, pixels, workspace_bytes, &pl, n); },
+        [&](int j0, int n) {
+            return conv1x1_wgrad_jobs(dw + j0, dw_dtype, x + j0, grad_y + j0, n, batch, cin, cout, pixels, workspace, workspace_bytes, stream,
+                                      "sis_conv1x1_bf16_wgrad_multi");
+        });
+}
+
+/* One layer: the one-job case of sis_conv1x1_bf16_wgrad_multi. */
+extern "C" int sis_conv1x1_bf16_wgrad(void* dw, int dw_dtype, const void* x, const void* grad_y, int batch, int cin, int cout,
+                                      int pixels, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (batch <= 0) return 0;
+    return sis_conv1x1_bf16_wgrad_multi(&dw, dw_dtype, &x, &grad_y, 1, batch, cin, cout, pixels, workspace, workspace_bytes, stream);
 }

@@ -32,13 +32,11 @@ constexpr int GK = 8;     // tiles per chunk (MFMA K = 2 per instruction: 4 inst
 constexpr int GBLK = 64;  // channels per workgroup on both GEMM axes
 constexpr int GTHR = 512;
 
-constexpr int GW_JOBS_MAX = 16;   // layers of one shape per launch (grid.z), operands through pointer tables
-
 struct WgradParams {
     const float* x; const float* gy; float* slab;
     int jobs;                   // > 0: grid.z layers: x / gy from the tables, slabs of layer z at slab + z * slab_job_stride floats
     long long slab_job_stride;
-    const float* xj[GW_JOBS_MAX]; const float* gyj[GW_JOBS_MAX];
+    const float* xj[SIS_JOBS_MAX]; const float* gyj[SIS_JOBS_MAX];
     int B, Cin, Cout, H, W;
     int chunks_total, chunks_per_slice, tiles_per_row, tiles_per_sample;
 };
@@ -262,7 +260,7 @@ __global__ __launch_bounds__(GTHR, 2) void conv_wgrad_wino_kernel(const WgradPar
 }
 
 // dW[co][ci][3][3] = G^T (sum over slices of S[.][co][ci]) G,  G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]
-struct GwDwTab { float* dw[GW_JOBS_MAX]; };
+using GwDwTab = SisJobTab<float>;
 
 __global__ __launch_bounds__(256) void conv_wgrad_finish_kernel(float* __restrict__ dw, const float* __restrict__ slab,
                                                                 int n_slices, int64_t n_pairs, long long slab_job_stride = 0,
@@ -395,29 +393,22 @@ static int gw_jobs(float* const* dw, const float* const* x, const float* const* 
     return 0;
 }
 
-extern "C" int sis_conv3x3_wgrad(float* dw, const float* x, const float* gy, int batch, int cin, int cout, int h, int w,
-                                 void* workspace, int64_t workspace_bytes, void* stream) {
-    SIS_REQUIRE(dw && x && gy && workspace, "sis_conv3x3_wgrad: null pointer");
-    return gw_jobs(&dw, &x, &gy, 1, batch, cin, cout, h, w, workspace, workspace_bytes, stream, "sis_conv3x3_wgrad");
-}
-
-/* The same for n_jobs layers of ONE shape (EMANet's repeated bottleneck units, queued during the backward): `dw`, `x`, `gy` are
- * HOST arrays of n_jobs device pointers.  One tile launch (grid.z = layer), one finish launch (and one slice reduction where the
- * plan has more than four slices) per <= 16 layers -- as few layers per launch as leave each its slabs in the workspace. */
+/* n_jobs layers of ONE shape (EMANet's repeated bottleneck units, queued during the backward): `dw`, `x`, `gy` are HOST arrays of
+ * n_jobs device pointers.  One tile launch (grid.z = layer), one finish launch (and one slice reduction where the plan has more
+ * than four slices) per <= 16 layers -- as few layers per launch as leave each its slabs in the workspace. */
 extern "C" int sis_conv3x3_wgrad_multi(float* const* dw, const float* const* x, const float* const* gy, int n_jobs, int batch, int cin,
                                        int cout, int h, int w, void* workspace, int64_t workspace_bytes, void* stream) {
     if (n_jobs <= 0) return 0;
     SIS_REQUIRE(dw && x && gy && workspace, "sis_conv3x3_wgrad_multi: null pointer");
-    for (int j0 = 0; j0 < n_jobs;) {
-        int n = n_jobs - j0 < GW_JOBS_MAX ? n_jobs - j0 : GW_JOBS_MAX;
-        for (; n > 1; n = (n + 1) / 2) {
-            WgradParams q;
-            int ks;
-            if (wgrad_plan(q, &ks, batch, cin, cout, h, w, workspace_bytes, n) == 0) break;
-        }
-        const int rc = gw_jobs(dw + j0, x + j0, gy + j0, n, batch, cin, cout, h, w, workspace, workspace_bytes, stream, "sis_conv3x3_wgrad_multi");
-        if (rc) return rc;
-        j0 += n;
-    }
-    return 0;
+    return sis_run_jobs(
+        n_jobs, [&](int n) { WgradParams q; int ks; return wgrad_plan(q, &ks, batch, cin, cout, h, w, workspace_bytes, n) == 0; },
+        [&](int j0, int n) {
+            return gw_jobs(dw + j0, x + j0, gy + j0, n, batch, cin, cout, h, w, workspace, workspace_bytes, stream, "sis_conv3x3_wgrad_multi");
+        });
+}
+
+/* One layer: the one-job case of sis_conv3x3_wgrad_multi. */
+extern "C" int sis_conv3x3_wgrad(float* dw, const float* x, const float* gy, int batch, int cin, int cout, int h, int w,
+                                 void* workspace, int64_t workspace_bytes, void* stream) {
+    return sis_conv3x3_wgrad_multi(&dw, &x, &gy, 1, batch, cin, cout, h, w, workspace, workspace_bytes, stream);
 }

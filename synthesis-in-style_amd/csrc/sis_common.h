@@ -47,6 +47,25 @@ static inline int sis_fail(const char* fmt, ...) {
 
 static inline int sis_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// Same-shape layers in one launch (the convolution weight gradients' *_multi entries: grid.z = layer, operands through pointer
+// tables in the kernel parameters).
+constexpr int SIS_JOBS_MAX = 16;   // layers per launch
+template <class T> struct SisJobTab { T* dw[SIS_JOBS_MAX]; };   // the layers' dW pointers, passed to the reduction kernels by value
+
+// Runs n_jobs layers in launches of at most SIS_JOBS_MAX: run(first, n), n halved while fits(n) says that the plan for n layers
+// does not leave every layer its slabs in the workspace (a single layer is left to run's own check).  Stops at the first failure.
+template <class Fits, class Run>
+static inline int sis_run_jobs(int n_jobs, Fits fits, Run run) {
+    for (int first = 0; first < n_jobs;) {
+        int n = n_jobs - first < SIS_JOBS_MAX ? n_jobs - first : SIS_JOBS_MAX;
+        while (n > 1 && !fits(n)) n = (n + 1) / 2;
+        const int rc = run(first, n);
+        if (rc) return rc;
+        first += n;
+    }
+    return 0;
+}
+
 // Device-side scalar conversion helpers (compute type for f16/bf16 is float, as the
 // reference kernels' scalar_t arithmetic on half promotes through float on the FMA path).
 template <typename T> struct sis_acc { typedef T type; };

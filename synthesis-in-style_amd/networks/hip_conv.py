@@ -249,6 +249,22 @@ def down_conv3x3(input, weight, fir, scale):
 _F32_POINTWISE = os.environ.get('SIS_F32_POINTWISE', '1') != '0'  # 0: fp32 1x1 convolutions stay on the library (A/B runs)
 
 
+def _pointwise_wgrad(site, grad_output, input, own=True, weight=None, defer=False, padded=None):
+    """dW [Cout, Cin, 1, 1] of an fp32 1x1 layer: csrc/conv1x1_wgrad_f32.hip where ``own`` and the kernel takes the operands,
+    else the batched GEMM on the library, counted under ``site``.  ``weight`` / ``defer``: the parameter whose gradient this is
+    (``for_param``) and the layer's leave to complete late.  ``padded``: dL/dy with zero channels appended (a narrow layer) --
+    the kernel multiplies that and its result is sliced back; ``weight`` is not given then (fresh tensor, never deferred)."""
+    b, cin, h, w = input.shape
+    cout = grad_output.shape[1]
+    gy = grad_output if padded is None else padded
+    if own and sis_hip.conv1x1_wgrad_f32_supported(gy, input):
+        late = {} if weight is None else dict(for_param=weight.data_ptr(), defer=defer and sis_hip.may_complete_late((weight,)))
+        dw = sis_hip.conv1x1_wgrad_f32(gy, input, **late)
+        return dw if padded is None else dw[:cout].contiguous()
+    sis_hip.library_call(site)
+    return torch.bmm(grad_output.view(b, cout, h * w), input.view(b, cin, h * w).transpose(1, 2)).sum(0).view(cout, cin, 1, 1)
+
+
 class _Pointwise(Function):
     """1x1 stride-1 convolution whose weight gradient is issued as the batched GEMM it is on the NCHW tensors,
     dW = sum_b dy_b x_b^T (``bmm`` + sum over the batch): the library's weight-gradient path goes through NHWC kernels
@@ -297,11 +313,7 @@ class _Pointwise(Function):
             if ctx.needs_input_grad[0]:
                 grad_input = sis_hip.conv1x1_f32(gy, wp, data_gradient=True)
             if ctx.needs_input_grad[1]:
-                if sis_hip.conv1x1_wgrad_f32_supported(gy, input):
-                    grad_weight = sis_hip.conv1x1_wgrad_f32(gy, input)[:cout].contiguous()
-                else:
-                    sis_hip.library_call("hip_conv._Pointwise.wgrad")
-                    grad_weight = torch.bmm(grad_output.view(b, cout, h * w), input.view(b, cin, h * w).transpose(1, 2)).sum(0).view(cout, cin, 1, 1)
+                grad_weight = _pointwise_wgrad("hip_conv._Pointwise.wgrad", grad_output, input, padded=gy)
             if ctx.has_bias and ctx.needs_input_grad[2]:
                 grad_bias = grad_output.sum((0, 2, 3))
             return grad_input, grad_weight, grad_bias, None
@@ -312,16 +324,10 @@ class _Pointwise(Function):
                 sis_hip.library_call("hip_conv._Pointwise.dgrad")
                 grad_input = torch.ops.aten.convolution_backward(grad_output, input, weight, None, (1, 1), (0, 0), (1, 1), False,
                                                                  (0, 0), 1, (True, False, False))[0]
-        g = grad_output.view(b, cout, h * w)
         if ctx.needs_input_grad[1]:
-            if _F32_POINTWISE and sis_hip.conv1x1_wgrad_f32_supported(grad_output, input):
-                grad_weight = sis_hip.conv1x1_wgrad_f32(grad_output, input, for_param=weight.data_ptr(),   # csrc/conv1x1_wgrad_f32.hip
-                                                        defer=ctx.defer and sis_hip.may_complete_late((weight,)))
-            else:
-                sis_hip.library_call("hip_conv._Pointwise.wgrad")
-                grad_weight = torch.bmm(g, input.view(b, cin, h * w).transpose(1, 2)).sum(0).view(cout, cin, 1, 1)
+            grad_weight = _pointwise_wgrad("hip_conv._Pointwise.wgrad", grad_output, input, _F32_POINTWISE, weight, ctx.defer)
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            grad_bias = g.sum((0, 2))
+            grad_bias = grad_output.view(b, cout, h * w).sum((0, 2))
         return grad_input, grad_weight, grad_bias, None
 
 
@@ -351,15 +357,8 @@ class _PointwiseWithSkip(Function):
                 grad_input = sis_hip.conv1x1_f32_dgrad_add(grad_output, weight, grad_skip.contiguous())
             else:
                 grad_input = sis_hip.conv1x1_f32(grad_output, weight, data_gradient=True)
-        if ctx.needs_input_grad[1]:
-            if sis_hip.conv1x1_wgrad_f32_supported(grad_output, input):
-                grad_weight = sis_hip.conv1x1_wgrad_f32(grad_output, input, for_param=weight.data_ptr(),
-                                                        defer=ctx.defer and sis_hip.may_complete_late((weight,)))
-            else:
-                sis_hip.library_call("hip_conv._PointwiseWithSkip.wgrad")
-                b, cin, h, w = input.shape
-                cout = weight.shape[0]
-                grad_weight = torch.bmm(grad_output.view(b, cout, h * w), input.view(b, cin, h * w).transpose(1, 2)).sum(0).view(cout, cin, 1, 1)
+        if ctx.needs_input_grad[1]:   # (own=True: this function is only entered where the fp32 pointwise kernels are switched on)
+            grad_weight = _pointwise_wgrad("hip_conv._PointwiseWithSkip.wgrad", grad_output, input, True, weight, ctx.defer)
         return grad_input, grad_weight, None
 
 

@@ -754,13 +754,10 @@ def conv3x3_wgrad(x, grad_output, for_param=None, defer=False):
     cout = gy.shape[1]
     dw = grad_out(for_param, (cout, cin, 3, 3), torch.float32, x.device)
     if defer and _flush_at_end():
-        _defer_conv_wgrad("f3", x, gy, dw, (batch, cin, cout, h, w))
-        return dw
-    ws = _workspace(x.device)
-    with torch.cuda.device(x.device):
-        _check(_launch(None, 2.0 * batch * cout * cin * 9 * h * w, 4.0 * (x.numel() + gy.numel() + dw.numel()),
-                       lambda: lib().sis_conv3x3_wgrad(_ptr(dw), _ptr(x), _ptr(gy), batch, cin, cout, h, w, _ptr(ws),
-                                                       ws.numel(), _stream())), "sis_conv3x3_wgrad")
+        _defer_conv_wgrad(CONV_WGRAD_F32_3X3, x, gy, dw, (batch, cin, cout, h, w))
+    else:
+        _launch_conv_wgrads(CONV_WGRAD_F32_3X3, (batch, cin, cout, h, w), dw.dtype, x.device, [(x.data_ptr(), gy.data_ptr(), dw.data_ptr())],
+                            4.0 * (x.numel() + gy.numel() + dw.numel()))
     return dw
 
 
@@ -860,6 +857,7 @@ def grad_out_fused(keys, rows, cols, device):
 _DEFER = os.environ.get("SIS_DEFER_REDUCES", "1") != "0"        # 0: every reduction where its partial results appear (A/B runs)
 _DEFER_WGRAD = os.environ.get("SIS_DEFER_WGRAD", "1") != "0"   # 0: every weight gradient where its operands appear (A/B runs)
 _deferred = {"ln": [], "wgrad": {}, "conv": {}}   # wgrad: (tokens, out, in, lda, ldb, device) -> [(grad, x, dw, db addresses, storages)]
+#                                                   conv: (kind, *dims, dW dtype, device) -> [(x, dL/dy, dw addresses, storages)], kind in _CONV_WGRADS
 _defer_blockers = set()         # ids of wrappers that read a gradient the moment autograd hands it over (torch's DistributedDataParallel)
 _defer_wgrad_blockers = set()   # ids of data-parallel wrappers with more than one rank: their buckets leave DURING the backward,
                                 # overlapped with it -- a weight gradient held back to its end would put the exchange behind it
@@ -906,10 +904,45 @@ def deferred_wgrad_pending():
     return any(_deferred["wgrad"].values()) or any(_deferred["conv"].values())
 
 
+# The convolution weight-gradient families, by the kind tag their jobs are queued under.  Per family: the C entry for n layers of
+# one shape, its operand order behind dW ("xg": x, dL/dy; "gx": dL/dy, x), whether it takes a dW dtype code, the flops of one
+# layer from the job's dims, and the kernel name for the profiler (None: the library reports it).
+CONV_WGRAD_F32_3X3, CONV_WGRAD_F32_1X1, CONV_WGRAD_BF16_3X3, CONV_WGRAD_BF16_1X1 = "f3", "f1", 3, 1
+_ConvWgrad = collections.namedtuple("_ConvWgrad", "entry order dw_dtype_code flops kernel")
+_CONV_WGRADS = {
+    CONV_WGRAD_F32_3X3: _ConvWgrad("sis_conv3x3_wgrad_multi", "xg", False,    # fp32 Winograd (EMANet); dims (b, cin, cout, h, w)
+                                   lambda b, cin, cout, h, w: 2.0 * b * cout * cin * 9 * h * w, None),
+    CONV_WGRAD_F32_1X1: _ConvWgrad("sis_conv1x1_wgrad_f32_multi", "gx", False,   # fp32 1x1 (EMANet); dims (b, cin, cout, pixels)
+                                   lambda b, cin, cout, pixels: 2.0 * b * cout * cin * pixels, "conv1x1_wgrad_f32_kernel"),
+    CONV_WGRAD_BF16_3X3: _ConvWgrad("sis_conv_bf16_wgrad_multi", "xg", True,   # dims (b, cin, cout, h, w)
+                                    lambda b, cin, cout, h, w: 2.0 * b * cout * cin * 9 * h * w, None),
+    CONV_WGRAD_BF16_1X1: _ConvWgrad("sis_conv1x1_bf16_wgrad_multi", "xg", True,   # dims (b, cin, cout, pixels)
+                                    lambda b, cin, cout, pixels: 2.0 * b * cout * cin * pixels, None),
+}
+
+
+def _launch_conv_wgrads(kind, dims, dw_dtype, device, jobs, nbytes=0.0, workspace=None):
+    """Launches the n >= 1 same-shape layers ``jobs`` = [(x, dL/dy, dW addresses, ...)] of one family: the immediate call of a
+    binding (one job) and the flush of the queue take this one path.  ``nbytes``: the profiler's byte figure.  ``workspace``:
+    (tensor or None, bytes) where the caller brings its own scratch; else the device's shared one."""
+    fam = _CONV_WGRADS[kind]
+    n = len(jobs)
+    arr = ctypes.c_void_p * n
+    xs, gys, dws = (arr(*[j[i] for j in jobs]) for i in range(3))
+    if workspace is None:
+        ws = _workspace(device)
+        workspace = (ws, ws.numel())
+    args = ((dws, _DTYPE_CODE[dw_dtype]) if fam.dw_dtype_code else (dws,)) + ((xs, gys) if fam.order == "xg" else (gys, xs)) \
+        + (n,) + tuple(dims) + (_ptr(workspace[0]), workspace[1])
+    with torch.cuda.device(device):
+        _check(_launch(fam.kernel, fam.flops(*dims) * n, nbytes, lambda: getattr(lib(), fam.entry)(*args, _stream())), fam.entry)
+
+
 def _defer_conv_wgrad(kind, x, grad_output, dw, dims):
-    """Queues a bf16 convolution's weight gradient (kind 3: 3x3, 1: 1x1) for the batched launch of ``flush_deferred``: layers of
-    one shape (the trunk's repeated bottleneck units) share one tile launch and one reduction launch, planned for their joint
-    workgroup count.  ``dw`` is valid after the flush only; the caller guarantees that nothing reads it before."""
+    """Queues a convolution's weight gradient (kind "f3": fp32 Winograd 3x3, "f1": fp32 1x1, 3: bf16 3x3, 1: bf16 1x1 -- the keys
+    of ``_CONV_WGRADS``) for the batched launch of ``flush_deferred``: layers of one shape (the trunks' repeated bottleneck units)
+    share one tile launch and one reduction launch, planned for their joint workgroup count.  ``dw`` is valid after the flush
+    only; the caller guarantees that nothing reads it before."""
     key = (kind,) + tuple(dims) + (dw.dtype, x.device)
     _deferred["conv"].setdefault(key, []).append((x.data_ptr(), grad_output.data_ptr(), dw.data_ptr(), _hold(x, grad_output, dw)))
 
@@ -917,32 +950,7 @@ def _defer_conv_wgrad(kind, x, grad_output, dw, dims):
 def _flush_conv_wgrads():
     queued, _deferred["conv"] = _deferred["conv"], {}
     for key, jobs in queued.items():
-        kind, dims, dtype, device = key[0], key[1:-2], key[-2], key[-1]
-        n = len(jobs)
-        arr = ctypes.c_void_p * n
-        xs, gys, dws = arr(*[j[0] for j in jobs]), arr(*[j[1] for j in jobs]), arr(*[j[2] for j in jobs])
-        ws = _workspace(device)
-        with torch.cuda.device(device):
-            if kind == "f3":   # fp32 Winograd weight gradient (EMANet)
-                b, cin, cout, h, w = dims
-                _check(_launch(None, 2.0 * b * cout * cin * 9 * h * w * n, 0.0,
-                               lambda: lib().sis_conv3x3_wgrad_multi(dws, xs, gys, n, b, cin, cout, h, w, _ptr(ws), ws.numel(), _stream())),
-                       "sis_conv3x3_wgrad_multi")
-            elif kind == "f1":   # fp32 1x1 weight gradient (EMANet)
-                b, cin, cout, hw = dims
-                _check(_launch("conv1x1_wgrad_f32_kernel", 2.0 * b * cout * cin * hw * n, 0.0,
-                               lambda: lib().sis_conv1x1_wgrad_f32_multi(dws, gys, xs, n, b, cin, cout, hw, _ptr(ws), ws.numel(), _stream())),
-                       "sis_conv1x1_wgrad_f32_multi")
-            elif kind == 3:
-                b, cin, cout, h, w = dims
-                _check(_launch(None, 2.0 * b * cout * cin * 9 * h * w * n, 0.0,
-                               lambda: lib().sis_conv_bf16_wgrad_multi(dws, _DTYPE_CODE[dtype], xs, gys, n, b, cin, cout, h, w, _ptr(ws),
-                                                                       ws.numel(), _stream())), "sis_conv_bf16_wgrad_multi")
-            else:
-                b, cin, cout, pixels = dims
-                _check(_launch(None, 2.0 * b * cout * cin * pixels * n, 0.0,
-                               lambda: lib().sis_conv1x1_bf16_wgrad_multi(dws, _DTYPE_CODE[dtype], xs, gys, n, b, cin, cout, pixels, _ptr(ws),
-                                                                          ws.numel(), _stream())), "sis_conv1x1_bf16_wgrad_multi")
+        _launch_conv_wgrads(key[0], key[1:-2], key[-2], key[-1], jobs)
 
 
 def defer_wgrad_bias(grad, x, dw=None):
@@ -1511,13 +1519,10 @@ def conv_bf16_wgrad(x, grad_output, out_dtype=torch.float32, for_param=None, def
     cout = grad_output.shape[1]
     dw = grad_out(for_param, (cout, cin, 3, 3), out_dtype, x.device)
     if defer and _flush_at_end():
-        _defer_conv_wgrad(3, x, grad_output, dw, (b, cin, cout, h, w))
-        return dw
-    ws = _workspace(x.device)
-    with torch.cuda.device(x.device):
-        _check(_launch(None, 2.0 * b * cout * cin * 9 * h * w, 2.0 * (x.numel() + grad_output.numel()) + 4.0 * dw.numel(),
-                       lambda: lib().sis_conv_bf16_wgrad(_ptr(dw), _DTYPE_CODE[out_dtype], _ptr(x), _ptr(grad_output), b, cin, cout,
-                                                         h, w, _ptr(ws), ws.numel(), _stream())), "sis_conv_bf16_wgrad")
+        _defer_conv_wgrad(CONV_WGRAD_BF16_3X3, x, grad_output, dw, (b, cin, cout, h, w))
+    else:
+        _launch_conv_wgrads(CONV_WGRAD_BF16_3X3, (b, cin, cout, h, w), out_dtype, x.device, [(x.data_ptr(), grad_output.data_ptr(), dw.data_ptr())],
+                            2.0 * (x.numel() + grad_output.numel()) + 4.0 * dw.numel())
     return dw
 
 
@@ -1698,13 +1703,10 @@ def conv1x1_bf16_wgrad(x, grad_output, out_dtype=torch.float32, for_param=None, 
         raise RuntimeError("conv1x1_bf16_wgrad: input and grad_output disagree on batch / plane size")
     dw = grad_out(for_param, (cout, cin, 1, 1), out_dtype, x.device)
     if defer and _flush_at_end():   # (as conv_bf16_wgrad)
-        _defer_conv_wgrad(1, x, grad_output, dw, (b, cin, cout, pixels))
-        return dw
-    ws = _workspace(x.device)
-    with torch.cuda.device(x.device):
-        _check(_launch(None, 2.0 * b * cout * cin * pixels, 2.0 * (x.numel() + grad_output.numel()) + 4.0 * dw.numel(),
-                       lambda: lib().sis_conv1x1_bf16_wgrad(_ptr(dw), _DTYPE_CODE[out_dtype], _ptr(x), _ptr(grad_output), b, cin, cout,
-                                                            pixels, _ptr(ws), ws.numel(), _stream())), "sis_conv1x1_bf16_wgrad")
+        _defer_conv_wgrad(CONV_WGRAD_BF16_1X1, x, grad_output, dw, (b, cin, cout, pixels))
+    else:
+        _launch_conv_wgrads(CONV_WGRAD_BF16_1X1, (b, cin, cout, pixels), out_dtype, x.device, [(x.data_ptr(), grad_output.data_ptr(), dw.data_ptr())],
+                            2.0 * (x.numel() + grad_output.numel()) + 4.0 * dw.numel())
     return dw
 
 
@@ -2320,18 +2322,17 @@ def conv1x1_wgrad_f32(grad_output, input, for_param=None, defer=False):
     require_device(input, "input")
     b, cin, h, w = input.shape
     cout = grad_output.shape[1]
-    L = lib()
     dw = grad_out(for_param, (cout, cin, 1, 1), torch.float32, input.device)
     if (defer and _flush_at_end() and grad_output.dtype == torch.float32 and input.dtype == torch.float32
             and grad_output.is_contiguous() and input.is_contiguous() and grad_output.data_ptr() % 16 == 0 and input.data_ptr() % 16 == 0):
-        _defer_conv_wgrad("f1", input, grad_output, dw, (b, cin, cout, h * w))
+        _defer_conv_wgrad(CONV_WGRAD_F32_1X1, input, grad_output, dw, (b, cin, cout, h * w))
         return dw
-    ws_bytes = int(L.sis_conv1x1_wgrad_f32_workspace(b, cin, cout, h * w))
+    # a scratch of exactly the planned slabs (none for a single K slice), not the shared workspace
+    ws_bytes = int(lib().sis_conv1x1_wgrad_f32_workspace(b, cin, cout, h * w))
     ws = torch.empty(max(ws_bytes // 4, 4), dtype=torch.float32, device=input.device)
-    with torch.cuda.device(input.device):
-        _check(_launch("conv1x1_wgrad_f32_kernel", 2.0 * b * cout * cin * h * w, 4.0 * (grad_output.numel() + input.numel() + dw.numel()),
-                       lambda: L.sis_conv1x1_wgrad_f32(_ptr(dw), _ptr(grad_output), _ptr(input), b, cin, cout, h * w,
-                                                       _ptr(ws) if ws_bytes else None, ws_bytes, _stream())), "sis_conv1x1_wgrad_f32")
+    _launch_conv_wgrads(CONV_WGRAD_F32_1X1, (b, cin, cout, h * w), dw.dtype, input.device,
+                        [(input.data_ptr(), grad_output.data_ptr(), dw.data_ptr())],
+                        4.0 * (grad_output.numel() + input.numel() + dw.numel()), workspace=(ws if ws_bytes else None, ws_bytes))
     return dw
 
 
