@@ -1149,6 +1149,29 @@ int sis_scan_resample(uint8_t* out, const uint8_t* page, int in_h, int in_w, int
                       const int32_t* count_y, int ksize_y, void* workspace, int64_t workspace_bytes, void* stream);
 int sis_scan_patches(uint8_t* out, const uint8_t* page, const int32_t* origins, int n, int size, int height, int width, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Validation pass of the segmenters (csrc/seg_eval.h).  The reference leaves its evaluator hook empty for them
+ * (training_builder/base_train_builder.py:64-65); the scores are those of evaluation/segmentation_metric_calculation.py:71-94
+ * (confusion matrix) and networks/trans_u_net/utils.py:7-42 (Dice sums), the cross entropy is nn.CrossEntropyLoss's.
+ * sis_seg_eval: logits [batch][classes][h][w] (SIS_F32, or SIS_BF16 when h == out_h and w == out_w), labels int64
+ *   [batch][out_h][out_w]; 2 <= classes <= 16, 1 <= h <= out_h, 1 <= w <= out_w, out_h * out_w <= 2^30,
+ *   batch * out_h * out_w <= 2^39, no alignment rule.
+ *   Per output pixel the values v[c] are the stored elements widened to float (h == out_h and w == out_w) or the align-corners
+ *   bilinear values with the scales and the function of sis_upsample_ce_fwd; the prediction is the first maximal class
+ *   (torch.argmax for finite logits; a NaN never wins, and non-finite logits make `sums` NaN).
+ *   ACCUMULATES (the caller zeroes both once per validation run) into
+ *     counts int64 [classes * classes + 2]: matrix[label][prediction] as sis_confusion_matrix lays it out, then `counted` (labels
+ *       in [0, classes)), then `ignored` (every other label: in no cell, not in the cross entropy);
+ *     sums double [1 + 3 * classes]: sum of -log softmax(v)[label] over the counted pixels, then per class c at 1 + 3c:
+ *       I_c = sum p_c [label == c], P_c = sum p_c^2, T_c = sum [label == c] over ALL pixels (an ignored label is an all-zero one-hot
+ *       row, sis_ce_dice_fwd's rule).
+ *   counts are exact and independent of any order; sums are added in a fixed order (two calls give the same bits).
+ *   workspace: sis_seg_eval_workspace_bytes(batch, classes, out_h, out_w) bytes, 8-byte aligned (0 for sizes out of range).
+ *   Everything else declines with an error code and launches nothing. */
+int64_t sis_seg_eval_workspace_bytes(int batch, int classes, int out_h, int out_w);
+int sis_seg_eval(int64_t* counts, double* sums, void* workspace, const void* logits, int dtype, const int64_t* labels, int batch,
+                 int classes, int h, int w, int out_h, int out_w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

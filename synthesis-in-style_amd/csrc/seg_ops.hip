@@ -9,6 +9,7 @@
 //                             in ONE launch (training_builder/ema_net_train_builder.py:27-48: three groups with
 //                             their own lr / weight decay), driven by a device-resident chunk table.
 //  * sis_ema_update           emau.mu <- m*mu + (1-m)*mean_b(mu_b)  (updater/segmentation_updater.py:56-66).
+//  * sis_seg_eval             the validation pass over a batch of logits (seg_eval.h, included below the loss entries).
 #include "sis_device.h"
 
 namespace {
@@ -237,6 +238,9 @@ extern "C" int sis_upsample_ce_bwd(float* grad_logits, const float* grad_loss, c
     SIS_CHECK_LAUNCH("ce_bwd_kernel");
     return 0;
 }
+
+// the validation pass: sis_seg_eval_workspace_bytes, sis_seg_eval (CeParams, interp_logits and ce_setup from above)
+#include "seg_eval.h"
 
 extern "C" int sis_sgd_chunk_elems(void) { return SGD_CHUNK; }
 

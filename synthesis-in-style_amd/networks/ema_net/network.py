@@ -399,6 +399,12 @@ class EMANet(BaseSegmenter):
         x, mu = self.emau(x)
         return self.fc2(self.fc1(x)), mu
 
+    def eval_logits(self, img):
+        """The logits at their native 1 / 8 size, inside the Winograd bank context as ``forward`` runs them: what a validation
+        pass hands to ``sis_hip.seg_eval``, which interpolates them as the training loss does (training/validation.py)."""
+        with _winograd_bank(self):
+            return self.logits(img)[0]
+
     def forward(self, img, lbl=None, size=None):
         with _winograd_bank(self):   # one launch transforms the weights of every 3x3 layer (19 launches per step before)
             x, mu = self.logits(img)

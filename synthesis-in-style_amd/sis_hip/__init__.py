@@ -230,6 +230,8 @@ _SIGNATURES = {
     "sis_scan_resample_workspace_bytes": ([_i] * 4, _i64),
     "sis_scan_resample": ([_vp, _vp] + [_i] * 4 + [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i64, _vp], _i),
     "sis_scan_patches": ([_vp, _vp, _vp] + [_i] * 4 + [_vp], _i),
+    "sis_seg_eval_workspace_bytes": ([_i] * 4, _i64),
+    "sis_seg_eval": ([_vp] * 4 + [_i, _vp] + [_i] * 6 + [_vp], _i),
 }
 
 
@@ -1220,6 +1222,52 @@ def upsample_ce_bwd(grad_loss, logits, labels, out_size, ignore_index):
         _check(lib().sis_upsample_ce_bwd(_ptr(gx), _ptr(g), _ptr(x), _ptr(lab), b, c, h, w, out_size[0], out_size[1],
                                          int(ignore_index), _stream()), "sis_upsample_ce_bwd")
     return gx
+
+
+def seg_eval_state(classes, device):
+    """Fresh zeroed state of ``seg_eval``: counts int64 [C*C + 2] and sums float64 [1 + 3C] on ``device``."""
+    return (torch.zeros(classes * classes + 2, dtype=torch.int64, device=device),
+            torch.zeros(1 + 3 * classes, dtype=torch.float64, device=device))
+
+
+def seg_eval(logits, labels, size=None, counts=None, sums=None):
+    """One validation pass over a batch (csrc/seg_eval.h): ``logits`` [B,C,h,w] (float32, or bfloat16 at the size
+    of the labels), ``labels`` int64 [B,H,W] or [B,1,H,W]; ``size`` = (H, W), taken from the labels when None.  Where (h, w) !=
+    (H, W) the logits are interpolated (bilinear, align_corners) inside the kernel, as ``upsample_ce_fwd`` does.  ACCUMULATES into
+    ``counts`` (int64 [C*C + 2]: matrix[label][argmax] row-major, counted, ignored) and ``sums`` (float64 [1 + 3C]: sum of -log
+    softmax[label] over the counted pixels, then I_c, P_c, T_c per class) and returns both; fresh zeroed state when None."""
+    require_device(logits, "logits")
+    require_device(labels, "labels")
+    if logits.dtype not in (torch.float32, torch.bfloat16) or logits.dim() != 4:
+        raise RuntimeError(f"logits must be a float32 or bfloat16 [B, C, h, w] tensor, got {logits.dtype} {tuple(logits.shape)}")
+    if labels.dtype != torch.int64:
+        raise RuntimeError(f"labels must be int64, got {labels.dtype}")
+    if labels.dim() == 4 and labels.shape[1] == 1:
+        labels = labels[:, 0]
+    b, c, h, w = logits.shape
+    if labels.dim() != 3 or labels.shape[0] != b:
+        raise RuntimeError(f"labels must be [B, H, W] or [B, 1, H, W] with B = {b}, got {tuple(labels.shape)}")
+    oh, ow = (int(size[0]), int(size[1])) if size is not None else (int(labels.shape[1]), int(labels.shape[2]))
+    if tuple(labels.shape[1:]) != (oh, ow):
+        raise RuntimeError(f"labels shape {tuple(labels.shape)} != {(b, oh, ow)}")
+    x, lab = logits.contiguous(), labels.contiguous()
+    if counts is None:
+        counts = torch.zeros(c * c + 2, dtype=torch.int64, device=x.device)
+    if sums is None:
+        sums = torch.zeros(1 + 3 * c, dtype=torch.float64, device=x.device)
+    if counts.dtype != torch.int64 or tuple(counts.shape) != (c * c + 2,) or not counts.is_contiguous() or counts.device != x.device:
+        raise RuntimeError(f"counts must be a contiguous int64 [{c * c + 2}] tensor on {x.device}, got {counts.dtype} {tuple(counts.shape)}")
+    if sums.dtype != torch.float64 or tuple(sums.shape) != (1 + 3 * c,) or not sums.is_contiguous() or sums.device != x.device:
+        raise RuntimeError(f"sums must be a contiguous float64 [{1 + 3 * c}] tensor on {x.device}, got {sums.dtype} {tuple(sums.shape)}")
+    L = lib()
+    ws_bytes = L.sis_seg_eval_workspace_bytes(b, c, oh, ow)
+    if ws_bytes <= 0:
+        raise RuntimeError(f"seg_eval: {c} classes (2..16) or batch {b}, size {oh} x {ow} out of range")
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(L.sis_seg_eval(_ptr(counts), _ptr(sums), _ptr(ws), _ptr(x), _DTYPE_CODE[x.dtype], _ptr(lab), b, c, h, w, oh, ow,
+                              _stream()), "sis_seg_eval")
+    return counts, sums
 
 
 def sgd_chunk_elems():

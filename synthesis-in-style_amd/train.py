@@ -7,7 +7,12 @@ per-iteration clamped-cosine LR, rank-0 snapshots, barrier before the first iter
 Launch either like the reference (``python train.py CONFIG ...`` spawns ``torch.cuda.device_count()`` workers)
 or under ``torch.distributed.run`` (RANK / WORLD_SIZE / LOCAL_RANK / MASTER_* taken from the environment).
 The third-party trainer / wandb / image-plotter extensions of the reference are not part of the step and are
-replaced by a plain loop with stdout logging.
+replaced by a plain loop with stdout logging.  The evaluator extension is part of the loop: with ``--val-images`` the
+builder's ``SegmentationValidator`` (training/validation.py) runs every ``--eval-iter`` iterations and once after the last
+(not twice where the two coincide), on all ranks; rank 0 prints one ``validation iter ...`` line, appends the scores to
+``<log_dir>/validation.jsonl`` and writes ``<log_dir>/best.pt`` whenever ``best_metric`` (config key, default
+``dice/weighted_avg``; ``ce`` and ``dice_loss`` count downwards) strictly improves.  Without ``--val-images`` nothing of this
+runs.
 """
 import argparse
 import json
@@ -21,6 +26,7 @@ import torch.distributed as dist
 import yaml
 
 from training.loop import get_current_reporter
+from training.validation import ValidationLog, default_eval_iter, validation_due
 from training_builder.train_builder_selection import get_train_builder_class
 from utils.clamped_cosine import ClampedCosineAnnealingLR
 from utils.synthetic_data import SyntheticSegmentationLoader
@@ -100,6 +106,16 @@ def main(rank: int, args: argparse.Namespace, world_size: int):
     max_iter = config['max_iter'] if 'max_iter' in config and config['max_iter'] else config['epochs'] * per_epoch
     schedulers = get_scheduler(config, per_epoch, builder.get_optimizers())
     snapshotter = builder.get_snapshotter()
+    validator = builder.get_evaluator()
+    if validator is not None:
+        eval_iter = default_eval_iter(config, per_epoch)
+        validation_log = ValidationLog(config.get('log_dir', 'logs'), config.get('best_metric') or 'dice/weighted_avg',
+                                       snapshotter) if rank == 0 else None
+
+        def validate(iteration):
+            scores = validator.run()   # every rank: the state is summed over the ranks
+            if validation_log is not None:
+                validation_log.record(iteration, scores, final=iteration == max_iter)
     if world_size > 1:
         dist.barrier()
     logging.info('Setup complete. Starting training...')
@@ -112,10 +128,12 @@ def main(rank: int, args: argparse.Namespace, world_size: int):
             if snapshotter is not None:
                 snapshotter.maybe_save(it)
             if rank == 0 and it % config.get('log_iter', 10) == 0:
-                obs = get_current_reporter().scalars()
+                obs = {k: v for k, v in get_current_reporter().scalars().items() if not k.startswith('validation/')}
                 rate = it * config['batch_size'] * world_size / (time.perf_counter() - t0)
                 print(f"iter {it} " + " ".join(f"{k}={v:.5f}" for k, v in obs.items()) + f" images/s={rate:.1f}",
                       flush=True)
+            if validator is not None and validation_due(it, eval_iter, max_iter):
+                validate(it)
     finally:
         if world_size > 1:
             dist.destroy_process_group()
@@ -134,6 +152,8 @@ def parse_args(argv=None):
     parser.add_argument('-l', '--log-dir', default='logs', help='where to write snapshots')
     parser.add_argument('--synthetic', action='store_true', help='feed synthetic batches (benchmarks / smoke runs)')
     parser.add_argument('--max-iter', dest='max_iter', type=int, help='stop after this many iterations')
+    parser.add_argument('--eval-iter', dest='eval_iter', type=int, help='with --val-images: validate every this many iterations '
+                        'and after the last (default: snapshot_save_iter when positive, else one epoch)')
     return parser.parse_args(argv)
 
 

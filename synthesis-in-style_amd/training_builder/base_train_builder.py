@@ -21,6 +21,7 @@ even a single rank (world_size 1 over RCCL: the rehearsal a one-GPU box allows).
 Reference quirk not reproduced: its ``get_optimizers()`` constructs a NEW optimizer on every call, so the LR
 scheduler built in train.py:39-56 schedules an optimizer that never trains.  Here the optimizer is created once.
 """
+import json
 from pathlib import Path
 from typing import Dict, Optional
 
@@ -53,6 +54,11 @@ class Snapshotter:
             self.log_dir.mkdir(parents=True, exist_ok=True)
             torch.save({k: strip_parallel_module(v).state_dict() for k, v in self.targets.items()},
                        self.log_dir / f"{iteration:06d}.pt")
+
+    def save_as(self, name: str):
+        """The same layout under a fixed file name (``best.pt``: the best validation so far), whatever ``every`` is."""
+        self.log_dir.mkdir(parents=True, exist_ok=True)
+        torch.save({k: strip_parallel_module(v).state_dict() for k, v in self.targets.items()}, self.log_dir / name)
 
 
 class BaseTrainBuilder:
@@ -151,8 +157,25 @@ class BaseTrainBuilder:
         return Snapshotter({'segmentation_network': self.segmentation_network, **self.get_optimizers()},
                            self.config.get('log_dir', 'logs'), self.config.get('snapshot_save_iter', 0))
 
-    def get_evaluator(self, logger):
-        return None
+    def validator_options(self) -> dict:
+        return {}
+
+    def class_names(self):
+        """The keys of ``class_to_color_map`` in file order (the order of the class ids); ``class_<i>`` without a map."""
+        path = self.config.get('class_to_color_map')
+        if path:
+            with open(path) as f:
+                return list(json.load(f).keys())
+        return [f"class_{i}" for i in range(self.config['num_classes'])]
+
+    def get_evaluator(self, logger=None):
+        """A ``SegmentationValidator`` over the validation loader, ``None`` without one.  The reference has this hook and leaves
+        it empty for the segmenters (training_builder/base_train_builder.py:64-65: ``return None``); this goes beyond it."""
+        if self.val_data_loader is None:
+            return None
+        from training.validation import SegmentationValidator
+        return SegmentationValidator(self.segmentation_network, self.val_data_loader, self.class_names(), self.device(),
+                                     **self.validator_options())
 
     def get_image_plotter(self):
         return None  # image grids are wandb / PIL visualisation, outside the training step

@@ -70,6 +70,10 @@ class PixelEnsembleTrainBuilder(BaseTrainBuilder):
                 fused=self.config.get('fused'))
         return self._updater
 
+    def get_evaluator(self, logger=None):
+        return None   # the DatasetGAN evaluator scores whole activation stacks with the reference's own id-valued "Dice": not
+        # the pixel-batch pass of training/validation.py
+
     def get_snapshotter(self):
         if self.rank != 0:
             return None

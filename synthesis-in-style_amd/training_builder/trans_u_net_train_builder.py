@@ -28,3 +28,6 @@ class TransUNetTrainBuilder(BaseTrainBuilder):
 
     def updater_options(self):
         return {'num_classes': self.config['num_classes'], 'amp': self.config.get('amp')}
+
+    def validator_options(self):
+        return {'amp': self.config.get('amp')}   # validation sees the logits under the autocast the updater trains with
