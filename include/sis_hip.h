@@ -156,6 +156,23 @@ int sis_modconv2d_wino24_rgb(float* out, float* rgb_part, const float* x, const 
                              const float* noise, int64_t noise_batch_stride, const float* noise_weight, const float* bias,
                              const float* rgb_w, const float* rgb_s, float rgb_scale, int batch, int cin, int cout, int h, int w,
                              int fuse_act, int tiles_per_wg, void* stream);
+
+/* The same layers in Winograd F(4x4,3x3) form (csrc/modconv_wino44.h): 36 multiplies per 4 x 4 output tile, 36/144 of the direct
+ * form.  sis_modconv_prepack_wino44 writes cin * 36 * cout floats, (G4 w[co,ci] G4^T)[i][j] with F(4,3) (points 0, +-1, +-2, inf)
+ * on both axes, in the kernel's private order [ci][9 rows][co][4] (head of csrc/modconv_wino44.h).  sis_modconv_wino44_eligible
+ * is sis_modconv_wino24_eligible's rule with h % 4 == 0 in place of h % 2 == 0.  sis_modconv2d_wino44 and
+ * sis_modconv2d_wino44_rgb take the operands of their wino24 twins with u44 in place of u24 and write the same things: rgb_part
+ * has the layout that sis_rgb_finish reads; the stored activation of the _rgb entry is that of the plain entry bit for bit, and a
+ * sample's results do not depend on the batch or on tiles_per_wg. */
+int sis_modconv_prepack_wino44(float* u, const float* w, int cout, int cin, void* stream);
+int sis_modconv_wino44_eligible(int cin, int cout, int h, int w);
+int sis_modconv2d_wino44(float* out, const float* x, const float* u44, const float* s, const float* dscale,
+                         const float* noise, int64_t noise_batch_stride, const float* noise_weight, const float* bias,
+                         int batch, int cin, int cout, int h, int w, int fuse_act, int tiles_per_wg, void* stream);
+int sis_modconv2d_wino44_rgb(float* out, float* rgb_part, const float* x, const float* u44, const float* s, const float* dscale,
+                             const float* noise, int64_t noise_batch_stride, const float* noise_weight, const float* bias,
+                             const float* rgb_w, const float* rgb_s, float rgb_scale, int batch, int cin, int cout, int h, int w,
+                             int fuse_act, int tiles_per_wg, void* stream);
 int sis_rgb_finish(float* out, const float* part, const float* bias, const float* skip, const float* taps, int batch, int blocks,
                    int cout, int h, int width, int kh, int kw, int pad0, int pad1, void* stream);
 

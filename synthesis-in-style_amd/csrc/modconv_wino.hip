@@ -1047,3 +1047,6 @@ int modconv_wino_launch(ConvParams& p, hipStream_t st, void* workspace, int64_t 
 
 // Winograd F(2x4,3x3) form of the same layers: kernel, prepack and C entries
 #include "modconv_wino24.h"
+
+// Winograd F(4x4,3x3) form of the same layers: kernel, prepack and C entries
+#include "modconv_wino44.h"

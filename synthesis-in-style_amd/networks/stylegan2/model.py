@@ -128,10 +128,17 @@ MATRIX_PRECISIONS = ("fp32", "bf16")
 # How a stride-1 3x3 layer runs an h x w map in inference (ModulatedConv2d.route), in order of precedence: bf16 operands on the
 # bf16 matrix cores (opt-in), Winograd F(2x4,3x3), Winograd F(2x2,3x3), the direct kernel.  Everything else is "direct".
 ROUTES = ("bf16", "wino24", "wino", "direct")
+# "wino44", Winograd F(4x4,3x3) (csrc/modconv_wino44.h), stands ahead of "wino24" for the layers of WINO44_LAYERS: the
+# (Cin, Cout, H, W) on which that kernel measured faster than F(2x4,3x3) beyond its launch spread, with a device error under half
+# the per-layer bound (profiles/wino44_layers.txt).  SIS_WINO44=0 restores the routes above exactly.
+WINO44_ROUTE = "wino44"
+WINO44_LAYERS = frozenset({(256, 256, 128, 128), (128, 128, 256, 256)})
+WINOGRAD_RGB_ROUTES = (WINO44_ROUTE, "wino24")   # the routes whose kernel can also leave the following ToRGB's channel sum
 # weight image of a route (and of the fast-FIR up-convolution): the keyword that carries it into sis_hip and what packs it
-_IMAGES = {"bf16": ("bf16_w", "modconv_prepack_bf16"), "wino24": ("wino24_u", "modconv_prepack_wino24"),
+_IMAGES = {"bf16": ("bf16_w", "modconv_prepack_bf16"), WINO44_ROUTE: ("wino44_u", "modconv_prepack_wino44"),
+           "wino24": ("wino24_u", "modconv_prepack_wino24"),
            "wino": ("wino_u", "modconv_prepack_wino"), "up_fir": ("fir_u", "modconv_prepack_up_fir")}
-_Switches = collections.namedtuple("_Switches", ROUTES[:3])   # whether the layer may take each route at all
+_Switches = collections.namedtuple("_Switches", ROUTES[:1] + (WINO44_ROUTE,) + ROUTES[1:3])   # whether the layer may take each route at all
 
 
 class ModulatedConv2d(nn.Module):
@@ -185,14 +192,17 @@ class ModulatedConv2d(nn.Module):
     def _read_switches(self):
         """SIS_GEN_PRECISION=bf16 (or set_matrix_precision) opts the stride-1 3x3 layers into the bf16 matrix-core route
         (csrc/modconv_bf16.h); the default, fp32, leaves every layer on the path it had.  SIS_WINOGRAD=0 selects the direct
-        kernel everywhere, SIS_WINO24=0 F(2x2,3x3) wherever a Winograd kernel runs (bisecting / A-B runs)."""
+        kernel everywhere, SIS_WINO24=0 F(2x2,3x3) wherever a Winograd kernel runs, SIS_WINO44=0 F(2x4,3x3) where F(4x4,3x3)
+        would run (bisecting / A-B runs)."""
         p = self.matrix_precision if self.matrix_precision is not None else os.environ.get("SIS_GEN_PRECISION", "fp32")
         if p not in MATRIX_PRECISIONS:
             raise ValueError(f"SIS_GEN_PRECISION / set_matrix_precision: {p!r} is not one of {MATRIX_PRECISIONS}")
         stride1 = self.kernel_size == 3 and not self.upsample and not self.downsample
         wino = (stride1 and self.in_channel % 8 == 0 and self.out_channel % 4 == 0
                 and os.environ.get("SIS_WINOGRAD", "1") != "0")
-        return _Switches(bf16=stride1 and p == "bf16", wino24=wino and os.environ.get("SIS_WINO24", "1") != "0", wino=wino)
+        wino24 = wino and os.environ.get("SIS_WINO24", "1") != "0"
+        return _Switches(bf16=stride1 and p == "bf16", wino44=wino24 and os.environ.get("SIS_WINO44", "1") != "0", wino24=wino24,
+                         wino=wino)
 
     def set_matrix_precision(self, precision):
         """"fp32" / "bf16" for this layer's inference route, None: as SIS_GEN_PRECISION says.  The switch of a live pack is read
@@ -206,11 +216,14 @@ class ModulatedConv2d(nn.Module):
             self._switches = self._switches._replace(bf16=self._read_switches().bf16)
 
     def route(self, h, w):
-        """The one of ROUTES an h x w map of this layer runs on: the switches as the current pack read them (afresh where there
-        is no pack), then the library's own eligibility answers -- the batch plays no part."""
+        """The one of ROUTES (or WINO44_ROUTE) an h x w map of this layer runs on: the switches as the current pack read them
+        (afresh where there is no pack), then the library's own eligibility answers -- the batch plays no part."""
         on = self._switches if self._pack_key is not None else self._read_switches()
         if on.bf16 and sis_hip.modconv_bf16_eligible(self.in_channel, self.out_channel, h, w):
             return "bf16"
+        if (on.wino44 and (self.in_channel, self.out_channel, h, w) in WINO44_LAYERS
+                and sis_hip.modconv_wino44_eligible(self.in_channel, self.out_channel, h, w)):
+            return WINO44_ROUTE
         if on.wino24 and sis_hip.modconv_wino24_eligible(self.in_channel, self.out_channel, h, w):
             return "wino24"
         return "wino" if on.wino else "direct"
@@ -358,7 +371,7 @@ class StyledConv(nn.Module):
 
     def forward_s(self, input, wpk, s, dscale, noise=None, rgb=None, route=None):
         """Fused layer given the already computed style vector ``s`` [B,Cin] and epilogue factors [B,Cout].  ``rgb`` (layers on
-        the "wino24" route): ``ToRGB.fused_operands`` of the ToRGB that follows; the convolution leaves its channel sum for
+        a route of WINOGRAD_RGB_ROUTES): ``ToRGB.fused_operands`` of the ToRGB that follows; the convolution leaves its channel sum for
         ``ToRGB.finish_s``.  ``route`` (stride-1 layers): ``conv.route(h, w)`` where the caller has asked already."""
         conv, act = self.conv, self.activate
         b, _, h, w = input.shape
@@ -585,12 +598,12 @@ class Generator(nn.Module):
     def _rgb_fused(conv, rgb, h, w, skip, route=None):
         """Whether a resolution's second convolution also forms the channel sum of its ToRGB (``ToRGB.fused_operands``), which
         then only adds the channel blocks, the bias and the skip image instead of reading the activation again: wherever the
-        F(2x4,3x3) kernel takes the convolution (32^2 and up in the 256^2 generator).  At the last resolution that pass was
+        F(2x4,3x3) or the F(4x4,3x3) kernel takes the convolution (32^2 and up in the 256^2 generator).  At the last resolution that pass was
         exposed on the main stream; the hidden ones no longer share HBM and CUs with the up-convolutions beside them
         (profiles/wino24_rgb_epilogue.txt).  ``route``: ``conv.conv.route(h, w)`` where the caller has asked already."""
         if skip is None or rgb.upsample.factor != 2 or rgb.conv.out_channel != 3:
             return False
-        return (route or conv.conv.route(h, w)) == "wino24"
+        return (route or conv.conv.route(h, w)) in WINOGRAD_RGB_ROUTES
 
     def _modulate_all(self, latent):
         """Every layer's s [B,Cin] (and scale*demod [B,Cout] for the styled convs): two launches in total."""

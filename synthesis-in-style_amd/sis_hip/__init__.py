@@ -51,6 +51,10 @@ _SIGNATURES = {
     "sis_modconv_wino24_eligible": ([_i] * 4, _i),
     "sis_modconv2d_wino24": ([_vp] * 6 + [_i64, _vp, _vp] + [_i] * 7 + [_vp], _i),
     "sis_modconv2d_wino24_rgb": ([_vp] * 7 + [_i64, _vp, _vp, _vp, _vp, _f] + [_i] * 7 + [_vp], _i),
+    "sis_modconv_prepack_wino44": ([_vp, _vp, _i, _i, _vp], _i),
+    "sis_modconv_wino44_eligible": ([_i] * 4, _i),
+    "sis_modconv2d_wino44": ([_vp] * 6 + [_i64, _vp, _vp] + [_i] * 7 + [_vp], _i),
+    "sis_modconv2d_wino44_rgb": ([_vp] * 7 + [_i64, _vp, _vp, _vp, _vp, _f] + [_i] * 7 + [_vp], _i),
     "sis_rgb_finish": ([_vp] * 5 + [_i] * 9 + [_vp], _i),
     "sis_modconv_bf16_eligible": ([_i] * 4, _i),
     "sis_modconv_bf16_packed_elems": ([_i] * 2, _i64),
@@ -612,6 +616,24 @@ def modconv_wino24_eligible(cin, cout, h, w):
     return bool(lib().sis_modconv_wino24_eligible(int(cin), int(cout), int(h), int(w)))
 
 
+def modconv_prepack_wino44(weight):
+    """[1, Cout, Cin, 3, 3] -> Winograd F(4x4,3x3) transformed weights G4 g G4^T, [Cin, 9 rows, Cout, 4] (csrc/modconv_wino44.h)."""
+    w = _f32(weight, "weight")
+    _, cout, cin, k, _ = w.shape
+    if k != 3:
+        raise RuntimeError("the Winograd transform is for 3x3 kernels")
+    u = torch.empty((cin, 9, cout, 4), dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        _check(_launch("modconv_prepack_wino44", 0.0, 4.0 * (w.numel() + u.numel()),
+                       lambda: lib().sis_modconv_prepack_wino44(_ptr(u), _ptr(w), cout, cin, _stream())), "sis_modconv_prepack_wino44")
+    return u
+
+
+def modconv_wino44_eligible(cin, cout, h, w):
+    """True when the F(4x4,3x3) kernel takes a stride-1 3x3 layer of this shape; the batch size plays no part."""
+    return bool(lib().sis_modconv_wino44_eligible(int(cin), int(cout), int(h), int(w)))
+
+
 BF16_KERNEL = "modconv_bf16_kernel"
 
 
@@ -1038,16 +1060,19 @@ def rgb_part_shape(batch, cout, h, w):
 
 
 def modconv2d(x, wpk, s, dscale, ksize, noise=None, noise_weight=None, bias=None, fuse_act=False, wino_u=None, out=None,
-              wino24_u=None, wino24_tiles_per_wg=0, rgb=None, bf16_w=None):
+              wino24_u=None, wino24_tiles_per_wg=0, rgb=None, bf16_w=None, wino44_u=None, wino44_tiles_per_wg=0):
     """``bf16_w`` (modconv_prepack_bf16): the layer runs with bf16 operands on the bf16 matrix cores where modconv_bf16_eligible
     says so, whatever the batch (not together with ``rgb``); other shapes take the path they took without it.
 
     ``wino24_u`` (modconv_prepack_wino24): the layer runs on the F(2x4,3x3) kernel where modconv_wino24_eligible says so,
     whatever the batch; other shapes take the path they took without it.  ``wino24_tiles_per_wg``: tests only.
 
-    ``rgb`` = (weight [3 * Cout], s_rgb [B, Cout], scale, part): the F(2x4,3x3) kernel also leaves the following ToRGB's channel
-    sum in ``part`` (``rgb_part_shape``), in blocks of 64 channels, for ``rgb_finish``; an error where that kernel does not take
-    the layer.
+    ``wino44_u`` (modconv_prepack_wino44): the layer runs on the F(4x4,3x3) kernel where modconv_wino44_eligible says so, ahead
+    of ``wino24_u``; an error where it does not (the caller asks first).  ``wino44_tiles_per_wg``: tests only.
+
+    ``rgb`` = (weight [3 * Cout], s_rgb [B, Cout], scale, part): the Winograd kernel that takes the layer (F(4x4,3x3) with
+    ``wino44_u``, else F(2x4,3x3)) also leaves the following ToRGB's channel sum in ``part`` (``rgb_part_shape``), in blocks of 64
+    channels, for ``rgb_finish``; an error where that kernel does not take the layer.
 
     ``out``: a caller's contiguous float32 result tensor to write into (tools/bench_gen_bf16.py rotates more outputs than the
     cache holds)."""
@@ -1060,18 +1085,28 @@ def modconv2d(x, wpk, s, dscale, ksize, noise=None, noise_weight=None, bias=None
     shape, fuse, fast = (batch, cin, cout, h, w), int(bool(fuse_act)), ksize == 3 and batch > 0
     # The entry, chosen once: its C symbol, the factor on the direct-form FLOP count, what it reads besides x (with the element
     # size) and its arguments up to the stream.  0.75 for the F(2x4,3x3) entries: bench.py prices every kernel whose name contains
-    # "wino" at 16/36 of the recorded count, and 3/4 x 16/36 = 24/72 is what that kernel executes.
+    # "wino" at 16/36 of the recorded count, and 3/4 x 16/36 = 24/72 is what that kernel executes; 9/16 for the F(4x4,3x3)
+    # entries: 9/16 x 16/36 = 36/144.
+    w44 = wino44_u is not None
+    if w44 and not (fast and modconv_wino44_eligible(cin, cout, h, w)):
+        raise RuntimeError(f"modconv2d: wino44_u= needs the F(4x4,3x3) kernel, which does not take {cin} -> {cout} at {h}x{w}")
     if rgb is not None:
-        if wino24_u is None or not fast or not modconv_wino24_eligible(cin, cout, h, w):
+        if not w44 and (wino24_u is None or not fast or not modconv_wino24_eligible(cin, cout, h, w)):
             raise RuntimeError(f"modconv2d: rgb= needs the F(2x4,3x3) kernel, which does not take {cin} -> {cout} at {h}x{w}")
         rgb_w, rgb_s, rgb_scale, part = rgb
         rgb_w, rgb_s = _f32(rgb_w, "rgb weight"), _f32(rgb_s, "rgb style")
         if rgb_w.numel() != 3 * cout or tuple(rgb_s.shape) != (batch, cout):
             raise RuntimeError(f"modconv2d: rgb weight {tuple(rgb_w.shape)} / style {tuple(rgb_s.shape)} do not fit 3 x {cout} channels")
         _out_or_new(part, rgb_part_shape(batch, cout, h, w), x.device, "modconv2d rgb part")
-        symbol, factor, reads = "sis_modconv2d_wino24_rgb", 0.75, ((wino24_u, 4.0), (part, 4.0))
-        args = (_ptr(out), _ptr(part), _ptr(x), _ptr(wino24_u)) + tail + (_ptr(rgb_w), _ptr(rgb_s), float(rgb_scale)) + shape + (
-            fuse, int(wino24_tiles_per_wg))
+        if w44:
+            symbol, factor, reads, u, tpw = "sis_modconv2d_wino44_rgb", 0.5625, ((wino44_u, 4.0), (part, 4.0)), wino44_u, wino44_tiles_per_wg
+        else:
+            symbol, factor, reads, u, tpw = "sis_modconv2d_wino24_rgb", 0.75, ((wino24_u, 4.0), (part, 4.0)), wino24_u, wino24_tiles_per_wg
+        args = (_ptr(out), _ptr(part), _ptr(x), _ptr(u)) + tail + (_ptr(rgb_w), _ptr(rgb_s), float(rgb_scale)) + shape + (
+            fuse, int(tpw))
+    elif w44:
+        symbol, factor, reads = "sis_modconv2d_wino44", 0.5625, ((wino44_u, 4.0),)
+        args = (_ptr(out), _ptr(x), _ptr(wino44_u)) + tail + shape + (fuse, int(wino44_tiles_per_wg))
     elif bf16_w is not None and fast and modconv_bf16_eligible(cin, cout, h, w):
         if bf16_w.dtype != torch.bfloat16 or bf16_w.numel() != lib().sis_modconv_bf16_packed_elems(cin, cout) or not bf16_w.is_contiguous():
             raise RuntimeError(f"modconv2d: bf16_w is not the modconv_prepack_bf16 image of a {cin} -> {cout} layer")
