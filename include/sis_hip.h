@@ -76,7 +76,9 @@ int sis_head_gemm_tile(void);
 
 /* EqualLinear, model.py:152-162: out[b,o] = sum_i x[b,i] * w[o,i] * scale + bias[o]*lr_mul, then
  * (activation != 0) leaky-relu(0.2) * sqrt(2) as fused_leaky_relu does (fused_act.py:85-86).
- * x rows are x_row_stride floats apart (lets a [B, n_latent, D] latent be indexed in place). */
+ * x rows are x_row_stride floats apart (lets a [B, n_latent, D] latent be indexed in place).
+ * sis_last_kernel() names the kernel in_dim picked: equal_linear_full_kernel<8> (512), equal_linear_full_kernel<4> (256),
+ * equal_linear_kernel (up to 1024), head_gemm_kernel<0> (wider). */
 int sis_equal_linear(float* out, const float* x, int64_t x_row_stride, const float* w,
                      const float* bias, int batch, int in_dim, int out_dim, float scale,
                      float lr_mul, int activation, void* stream);
@@ -232,7 +234,8 @@ int sis_blur_noise_act(float* out, const float* in, const float* taps, const flo
 /* ToRGB, model.py:355-364: out[b,c,y,x] = scale * sum_ci w[c,ci]*s[b,ci]*x[b,ci,y,x] + bias[c]
  * + upfirdn2d(skip, taps, up=2, pad=(pad0,pad1))[b,c,y,x]   (skip == NULL: first ToRGB).
  * w is the [1,3,Cin,1,1] parameter, skip is [B,3,H/2,W/2], taps [kh,kw]. out channels fixed to
- * `cout` <= 4. */
+ * `cout` <= 4.  sis_last_kernel() names the kernel that ran: to_rgb_kernel<4> (h * w a multiple of 4, at least 256,
+ * x and out 16-byte aligned), else to_rgb_kernel<1>. */
 int sis_to_rgb(float* out, const float* x, const float* w, const float* s, const float* bias,
                const float* skip, const float* taps, int batch, int cin, int cout, int h, int width,
                int kh, int kw, int pad0, int pad1, float scale, void* stream);

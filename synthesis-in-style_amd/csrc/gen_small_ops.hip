@@ -539,15 +539,19 @@ extern "C" int sis_equal_linear(float* out, const float* x, int64_t x_row_stride
     SIS_REQUIRE(in_dim > 0, "sis_equal_linear: in_dim %d", in_dim);
     const dim3 grid(sis_cdiv(out_dim, 4), sis_cdiv(batch, EL_ROWS));
     if (in_dim == 512) {
+        sis_kernel_name = "equal_linear_full_kernel<8>";
         hipLaunchKernelGGL(equal_linear_full_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, out, x, x_row_stride, w, bias, batch, out_dim,
                            scale, lr_mul, activation);
     } else if (in_dim == 256) {
+        sis_kernel_name = "equal_linear_full_kernel<4>";
         hipLaunchKernelGGL(equal_linear_full_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, out, x, x_row_stride, w, bias, batch, out_dim,
                            scale, lr_mul, activation);
     } else if (in_dim <= 64 * ELW) {
+        sis_kernel_name = "equal_linear_kernel";
         hipLaunchKernelGGL(equal_linear_kernel, grid, dim3(256), 0, (hipStream_t)stream, out, x,
                            x_row_stride, w, bias, batch, in_dim, out_dim, scale, lr_mul, activation);
     } else {  // wider than a wave's register row: the matrix-core tile kernel takes any in_dim
+        sis_kernel_name = "head_gemm_kernel<0>";
         HeadArgs h = {};
         h.out = out; h.a = x; h.w = w; h.bias = bias; h.a_row_stride = x_row_stride; h.batch = batch; h.k_dim = in_dim;
         h.out_dim = out_dim; h.scale = scale; h.lr_mul = lr_mul; h.activation = activation;
@@ -634,10 +638,12 @@ extern "C" int sis_to_rgb(float* out, const float* x, const float* w, const floa
     hipStream_t st = (hipStream_t)stream;
     if (hw % 4 == 0 && hw >= 256 && (((uintptr_t)x | (uintptr_t)out) & 15) == 0) {
         const size_t lds = ((size_t)cin * RGB_MAXC + 3 * RGB_MAXC * 4 * 64) * sizeof(float);
+        sis_kernel_name = "to_rgb_kernel<4>";
         hipLaunchKernelGGL(to_rgb_kernel<4>, dim3(batch * sis_cdiv(hw, 256)), dim3(256), lds, st, out, x, w, s, bias, skip,
                            taps, p);
     } else {
         const size_t lds = ((size_t)cin * RGB_MAXC + 3 * RGB_MAXC * 64) * sizeof(float);
+        sis_kernel_name = "to_rgb_kernel<1>";
         hipLaunchKernelGGL(to_rgb_kernel<1>, dim3(batch * sis_cdiv(hw, 64)), dim3(256), lds, st, out, x, w, s, bias, skip,
                            taps, p);
     }

@@ -11,7 +11,7 @@
 
 extern thread_local char sis_err_buf[512];
 extern thread_local const char* sis_kernel_name;  // device kernel the last call of an entry point that names its kernel dispatched to
-                                                  // (the convolutions, norms, encoder, k-means, upsampling: sis_last_kernel())
+                                                  // (the convolutions, norms, encoder, k-means, upsampling, EqualLinear, ToRGB: sis_last_kernel())
 
 static inline int sis_fail(const char* fmt, ...) {
     va_list ap;
