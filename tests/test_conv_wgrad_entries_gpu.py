@@ -2,7 +2,9 @@
 called immediately return the same bits.  The binding launches through the ``_multi`` entries only (immediate: one job; queued:
 the layers of a shape), and the single-layer entries forward to them: the plan for one job is the plan of the single layer and
 the kernels add in a fixed order, so equality is bitwise -- no tolerance.  Shapes (batch, cin, cout, h, w): the smallest of the
-families' own tests that reach each kernel form (unaligned maps, more than one K slice, both dW dtypes of the bf16 kernels)."""
+families' own tests that reach each kernel form (unaligned maps, more than one K slice, both dW dtypes of the bf16 kernels).
+What these launches compute is held to float64 elsewhere: the fp32 families bit for bit in test_conv_f32_exact_gpu.py, the bf16
+families in test_conv_bf16_exact_gpu.py."""
 import ctypes
 
 import pytest

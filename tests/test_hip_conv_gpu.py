@@ -220,7 +220,8 @@ def test_batched_fp32_weight_gradients_of_one_shape(device, kind, jobs, batch, c
     """EMANet's repeated bottleneck units: several fp32 layers of ONE shape through one tile launch + one finish / reduction launch
     (sis_conv3x3_wgrad_multi / sis_conv1x1_wgrad_f32_multi, what ``sis_hip.flush_deferred`` runs).  Every layer's dW against its own
     single-layer call: same products, K slices cut for the joint tile count -> another association of the fp32 partial sums
-    (1e-4 of the largest entry); more layers than one launch takes; bitwise repeatable."""
+    (1e-4 of the largest entry); more layers than one launch takes; bitwise repeatable.  (Every layer of such launches against
+    float64, bit for bit on exactly summable operands: test_conv_f32_exact_gpu.py::test_queued_weight_gradients_exact.)"""
     import sis_hip
     gen = torch.Generator().manual_seed(len(kind) * 100 + jobs * 10 + cin)
     xs = [torch.randn(batch, cin, h, w, generator=gen).to(device) for _ in range(jobs)]
