@@ -1045,6 +1045,9 @@ int modconv_wino_launch(ConvParams& p, hipStream_t st, void* workspace, int64_t 
     return p.ksplit > 1 ? modconv_splitk_finish_launch(p, st) : 0;
 }
 
+// What the two forms below share: transforms, layer tail, tile frame, plan and launch
+#include "modconv_wino_tile512.h"
+
 // Winograd F(2x4,3x3) form of the same layers: kernel, prepack and C entries
 #include "modconv_wino24.h"
 

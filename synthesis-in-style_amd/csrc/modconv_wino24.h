@@ -1,6 +1,6 @@
 // Stride-1 3x3 modulated convolution in Winograd F(2x4, 3x3) form: 2 output rows x 4 output columns per tile from a
 // 4 x 6 input patch, 24 multiplies per 8 outputs (24/72 of the direct form; F(2x2,3x3) in modconv_wino.hip: 16/36).
-// Included at the end of modconv_wino.hip (one translation unit: the helpers above are shared).
+// Included at the end of modconv_wino.hip behind modconv_wino_tile512.h, which holds what this form shares with F(4x4,3x3).
 //
 //   U[ci][xi][co] = (G2 g G4^T)[xi]     xi = 6 i + j, i = 0..3 (F(2,3) on the row axis), j = 0..5 (F(4,3), points
 //                                        0, +-1, +-2, inf, on the column axis); prepacked once per checkpoint
@@ -25,11 +25,8 @@
 
 namespace {
 
-constexpr int W24_CC = 4;                       // input channels per chunk
-constexpr int W24_UF = W24_CC * 24 * WMBLK;     // floats of a weight chunk  [ch][q][g][co][4]
-constexpr int W24_VF = W24_CC * 24 * WTILES;    // floats of a V chunk       [ch][q][g][tile][4]
-constexpr int W24_XT = 720;                     // floats per channel of the staged input tile: 10 x 72 or 18 x 40
-constexpr int W24_XP = 3;                       // 64-lane float4 pieces of a channel (the last one shifted back to end with the tile)
+constexpr int W24_UF = W512_CC * 24 * WMBLK;    // floats of a weight chunk  [ch][q][g][co][4]
+constexpr int W24_VF = W512_CC * 24 * WTILES;   // floats of a V chunk       [ch][q][g][tile][4]
 constexpr int W24_BAR = 19;                     // MFMA slot of a chunk behind which its barrier sits
 // MFMA slots of a chunk's five DMA instructions, all in front of the barrier: the two input pieces first (they come from HBM or
 // from the L2 of another XCD, and the barrier's vmcnt(0) waits for them), the three weight rows (L2-resident) behind them.  With
@@ -57,13 +54,8 @@ __global__ __launch_bounds__(256) void wino24_prepack_kernel(float* __restrict__
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const float a = t[i][0], b = t[i][1], c = t[i][2];
-        const float o[6] = {0.25f * a,
-                            (-1.f / 6.f) * (a + b + c),
-                            (-1.f / 6.f) * (a - b + c),
-                            (1.f / 24.f) * a + (1.f / 12.f) * b + (1.f / 6.f) * c,
-                            (1.f / 24.f) * a - (1.f / 12.f) * b + (1.f / 6.f) * c,
-                            c};
+        float o[6];
+        wino_g6<1, 1>(t[i], o);
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
             const int q = j / 3, e = 3 * i + j % 3;
@@ -88,21 +80,12 @@ __device__ unsigned int sis_wino24_trace_tile[TR_NWG][8][16][8];
 #define W24_TRACE(slot) do {} while (0)
 #endif
 
-// ToRGB operands of the instantiation that also emits RGB partial sums (RGB = true; the other one takes an empty struct).
-struct W24Rgb {
-    const float* w;   // [3][Cout]  ToRGB weight
-    const float* s;   // [B][Cout]  ToRGB style
-    float* part;      // [Cout / 64][B][3][H][W]  partial sums of the workgroup's channel block
-    float scale;
-};
-struct W24NoRgb {};
-
 // RGB: a workgroup additionally writes part[o0 / 64][b][c][y][x] = sum over its 64 channels of wr[b][c][co] * out[b][co][y][x],
 // wr = scale * w[c][co] * s[b][co] (ToRGB's modulated weight, no demodulation), from the values it stores to out.
 template <bool RGB>
 __global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvParams p, const int tiles_per_wg, const int xcd_group,
-                                                                  const std::conditional_t<RGB, W24Rgb, W24NoRgb> rgb) {
-    constexpr int CC = W24_CC, UF = W24_UF, VF = W24_VF, XT = W24_XT;
+                                                                  const std::conditional_t<RGB, WinoRgb, WinoNoRgb> rgb) {
+    constexpr int CC = W512_CC, UF = W24_UF, VF = W24_VF, XT = W512_XT;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* Ul = lds;                  // [2][UF]
     float* Vl = Ul + 2 * UF;          // [2][VF]   (Ul and Vl together: the column exchange of the epilogue, 96 KB)
@@ -118,6 +101,7 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvPara
     const int q = wave & 1, wn = (wave >> 1) & 1, wm = wave >> 2;
 
     // workgroup order: as modconv_wino2_kernel (output-channel block fastest; xcd_group: the blocks of a pixel tile on one XCD)
+    // (twin: modconv_wino44_kernel, down to txs, without the weight rows)
     const int n_co = p.Cout / WMBLK;
     const int wg = xcd_group ? (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
     const int o0 = (wg % n_co) * WMBLK;
@@ -141,9 +125,9 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvPara
     int xp_ch[2], xp_base[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        const int piece = k == 0 ? wave : (wave + 8) % (CC * W24_XP);
-        xp_ch[k] = piece / W24_XP;
-        xp_base[k] = min((piece % W24_XP) * 256, XT - 256);
+        const int piece = k == 0 ? wave : (wave + 8) % (CC * W512_XP);
+        xp_ch[k] = piece / W512_XP;
+        xp_base[k] = min((piece % W512_XP) * 256, XT - 256);
     }
     struct TileState {
         int b, h0, w0;
@@ -187,17 +171,8 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvPara
         };
         auto t_col = [&](int r) {  // (d B4)[r][3 Q + jj]
             const float a = dm[r].x, b = dm[r].y, c = dm[r].z, d = dm[r].w, e = de[r];
-            if (Q == 0) {
-                const float u = fmaf(-4.f, b, d), v = fmaf(-4.f, a, c);
-                ee[r][0] = fmaf(4.f, e, fmaf(-5.f, b, d));
-                ee[r][1] = u + v;
-                ee[r][2] = u - v;
-            } else {
-                const float u = d - b, v = c - a;
-                ee[r][0] = fmaf(2.f, v, u);
-                ee[r][1] = fmaf(-2.f, v, u);
-                ee[r][2] = fmaf(4.f, a, fmaf(-5.f, c, e));
-            }
+            const float lo[5] = {e, a, b, c, d}, hi[5] = {a, b, c, d, e};  // d0..d4, d1..d5
+            wino_b6_half<Q>(Q == 0 ? lo : hi, 1.f, ee[r]);
         };
         auto t_row = [&](int jj) {  // B2^T (d B4), scaled by the style
             oo[0][jj] = (ee[0][jj] - ee[2][jj]) * sv;
@@ -222,11 +197,7 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvPara
             for (int e = 0; e < 12; ++e)
 #pragma unroll
                 for (int j = 0; j < 16; ++j) acc[e][j] = 0.f;
-            // Lane-derived values of the tile start and of the epilogue come from copies of the thread index that the compiler
-            // cannot see through: it would otherwise compute them once and hold (spill) them across the chunk loop, whose
-            // registers are all taken.
-            int tp = tid;
-            asm volatile("" : "+v"(tp));
+            const int tp = wino_opaque_tid();
             tile_setup(pt_first + k * pt_step, T, tp & 63);
             if (k > 0) __syncthreads();  // everyone is done with the previous tile's exchange area and tail operands
             // first DMA of the tile: weights chunk 0, input chunks 0 and 1
@@ -236,18 +207,9 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvPara
             for (int kx = 0; kx < 2; ++kx) stage_x_piece(0, 0, kx);
 #pragma unroll
             for (int kx = 0; kx < 2; ++kx) stage_x_piece(min(CC, k_last), 1, kx);
-            // style row and layer-tail operands of the tile
+            // style row (twin: modconv_wino44_kernel) and layer-tail operands of the tile
             for (int e = tp; e < p.Cin; e += WNTHR) Sl[e] = p.s[(int64_t)T.b * p.Cin + e];
-            if (tp < WMBLK) {
-                Dl[tp] = p.dscale[(int64_t)T.b * p.Cout + o0 + tp];
-                Bl[tp] = (p.fuse && p.bias) ? p.bias[o0 + tp] : 0.f;
-            }
-            if constexpr (RGB) {
-                if (tp < 3 * WMBLK) {
-                    const int co = o0 + (tp & (WMBLK - 1));
-                    Wl[tp] = rgb.scale * rgb.w[(tp / WMBLK) * p.Cout + co] * rgb.s[(int64_t)T.b * p.Cout + co];
-                }
-            }
+            wino512_stage_tail_operands<RGB>(p, rgb, T.b, o0, tp, Dl, Bl, Wl);
             {
                 const int tt_ = tp >> 3, e = tp & 7;
                 const int yy = T.h0 + 2 * (tt_ >> txs) + (e >> 2), xx = T.w0 + 4 * (tt_ & ((1 << txs) - 1)) + (e & 3);
@@ -332,8 +294,7 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvPara
             // ---- epilogue.  m[r][jj] = (A2^T M)[r][column 3 Q + jj], r = 0, 1.  Wave Q finalises the accumulator rows j in
             // [8 Q, 8 Q + 8) and hands its m of the other 8 rows to its partner: [pair][sender Q][8 rows][6][64 lanes] over Ul / Vl.
             float mine[8][2][3];
-            int te = tid;
-            asm volatile("" : "+v"(te));
+            const int te = wino_opaque_tid();
             const int lane = te & 63, l31 = te & 31, half = (te >> 5) & 1;
             float* xch = lds + (wave >> 1) * (2 * 48 * 64);
 #pragma unroll
@@ -384,18 +345,13 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino24_kernel(const ConvPara
                     for (int r = 0; r < 2; ++r) {
                         const float* ma = Q == 0 ? mine[jr][r] : theirs[r];  // columns j = 0..2
                         const float* mb = Q == 0 ? theirs[r] : mine[jr][r];  // columns j = 3..5
-                        const float sa = ma[1] + ma[2], da = ma[1] - ma[2], sb = mb[0] + mb[1], db = mb[0] - mb[1];
-                        const float y[4] = {(ma[0] + sa) + sb, fmaf(2.f, db, da), fmaf(4.f, sb, sa), fmaf(8.f, db, da) + mb[2]};
+                        float y[4];
+                        wino_a4(ma, mb, y);
                         const sis_f32x4 nz = r == 0 ? nz0 : nz1;
                         const float nzv[4] = {nz.x, nz.y, nz.z, nz.w};
                         float o[4];
 #pragma unroll
-                        for (int x = 0; x < 4; ++x) {
-                            float val = y[x] * dd;
-                            val += nzv[x];
-                            val += bb;
-                            o[x] = fmaxf(val, val * slope) * gain;  // = (val > 0 ? val : 0.2 val) * sqrt(2) when the tail is on
-                        }
+                        for (int x = 0; x < 4; ++x) o[x] = wino_layer_tail(y[x], dd, nzv[x], bb, slope, gain);
                         *reinterpret_cast<sis_f32x4*>(obase + (int64_t)ro * HW + r * p.W) = sis_f32x4{o[0], o[1], o[2], o[3]};
                         if constexpr (RGB) {
 #pragma unroll
@@ -456,83 +412,23 @@ extern "C" int sis_modconv_prepack_wino24(float* u, const float* w, int cout, in
     return 0;
 }
 
-// The F(2x4,3x3) kernel takes a layer by (Cin, Cout, H, W) alone: 64-channel output blocks, 8-channel input steps, and a
-// map that one-sample tiles of 512 pixels (8 x 64 or 16 x 32) cover -- W > 16, H * W >= 512 after rounding up to powers of two.
-static int wino24_plan(ConvParams& p, int cin, int cout, int h, int w, bool rgb = false) {
-    if (cin <= 0 || cout <= 0 || h <= 0 || w <= 0) return -1;
-    if (cin % 8 || cout % WMBLK || h % 2 || w % 4) return -1;
-    if ((int64_t)cin * h * w * 4 >= ((int64_t)1 << 31) || (int64_t)cin * cout * 96 >= ((int64_t)1 << 31)) return -1;  // 32-bit DMA offsets
-    p.Cin = cin;
-    mc_reset_splitk(p);
-    mc_reset_tiles(p);
-    mc_add_class(p, 512, 2, 1, 0, h, 0, w, 64, 1);
-    const TileClass& tc = p.cls[0];
-    if (tc.nb != 1 || tc.th_log2 + tc.tw_log2 != 9 || tc.tw_log2 < 5) return -1;
-    if (((1 << tc.th_log2) + 2) * ((1 << tc.tw_log2) + 8) != W24_XT) return -1;
-    const size_t lds = (size_t)(2 * W24_UF + 2 * W24_VF + 2 * W24_CC * W24_XT + cin + (rgb ? 5 : 2) * WMBLK + WTILES * 8) * sizeof(float);
-    if (lds > 160 * 1024) return -1;
-    return (int)lds;
+namespace {
+constexpr Wino512Form WINO24_FORM = {2, 24, W24_UF, W24_VF, WTILES * 8, "modconv_wino24_kernel", "sis_modconv_wino24_eligible",
+                                     modconv_wino24_kernel<true>, modconv_wino24_kernel<false>};
 }
 
+// wino512_plan's rule (2 x 4 outputs per tile: H % 2, W % 4)
 extern "C" int sis_modconv_wino24_eligible(int cin, int cout, int h, int w) {
     ConvParams p;
-    return wino24_plan(p, cin, cout, h, w) > 0 ? 1 : 0;
-}
-
-// Both entries below: out as sis_modconv2d_wino24 documents it; rgb (or null) selects the instantiation with the RGB partial sums.
-static int wino24_launch(const char* name, float* out, const float* x, const float* u24, const float* s, const float* dscale,
-                         const float* noise, int64_t noise_batch_stride, const float* noise_weight, const float* bias, int batch,
-                         int cin, int cout, int h, int w, int fuse_act, int tiles_per_wg, const W24Rgb* rgb, void* stream) {
-    SIS_REQUIRE(out && x && u24 && s && dscale, "%s: null pointer", name);
-    SIS_REQUIRE(batch > 0, "%s: non-positive size", name);
-    if (noise) SIS_REQUIRE(noise_weight, "%s: noise given without noise_weight", name);
-    ConvParams p = mc_params(out, x, u24, s, dscale, noise, noise_batch_stride, noise_weight, bias, batch, cin, cout, h, w, h, w, w,
-                             fuse_act != 0);
-    const int lds = wino24_plan(p, cin, cout, h, w, rgb != nullptr);
-    SIS_REQUIRE(lds > 0, "%s: shape %dx%d, %d -> %d not eligible (sis_modconv_wino24_eligible)", name, h, w, cin, cout);
-    SIS_REQUIRE((int64_t)batch * (cin > cout ? cin : cout) * h * w < ((int64_t)1 << 31), "%s: tensor too large", name);
-    SIS_REQUIRE(((((uintptr_t)x | (uintptr_t)u24 | (uintptr_t)out) & 15) == 0) && (!noise || ((uintptr_t)noise & 3) == 0),
-                "%s: pointers must be 16-byte aligned", name);
-    const TileClass& tc = p.cls[0];
-    const int64_t tiles = (int64_t)batch * tc.nth * tc.ntw;  // one-sample tiles
-    p.npos_tiles = (int)tiles;
-    const int n_co = cout / WMBLK;
-    const int64_t blocks = tiles * n_co;
-    SIS_REQUIRE(blocks < ((int64_t)1 << 31), "%s: bad grid", name);
-    // pixel tiles per workgroup: as many as keep >= 1024 workgroups in flight (scheduling only: every tile is computed the same
-    // way whichever workgroup walks it); tiles_per_wg > 0 is the tests' override
-    int tpw = 1;
-    if (tiles_per_wg > 0) {
-        SIS_REQUIRE(tiles % tiles_per_wg == 0, "%s: %d tiles per workgroup do not divide %lld tiles", name, tiles_per_wg, (long long)tiles);
-        tpw = tiles_per_wg;
-    } else {
-        while (tpw * 2 <= 16 && tiles % (tpw * 2) == 0 && blocks / (tpw * 2) >= 1024) tpw *= 2;
-    }
-    const int64_t grid = blocks / tpw;
-    const int xcd_group = (double)cin * cout * 24 * sizeof(float) <= 5.0 * 1048576.0 && n_co > 1 && grid % (8 * n_co) == 0;
-    static bool have_attr[2] = {false, false};
-    const void* fn = rgb ? reinterpret_cast<const void*>(&modconv_wino24_kernel<true>) : reinterpret_cast<const void*>(&modconv_wino24_kernel<false>);
-    if (!have_attr[rgb != nullptr]) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return sis_fail("modconv: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-        have_attr[rgb != nullptr] = true;
-    }
-    sis_kernel_name = "modconv_wino24_kernel";  // both instantiations: one kernel to the per-kernel records
-    if (rgb) {
-        hipLaunchKernelGGL(modconv_wino24_kernel<true>, dim3((unsigned)grid), dim3(WNTHR), (size_t)lds, (hipStream_t)stream, p, tpw, xcd_group, *rgb);
-    } else {
-        hipLaunchKernelGGL(modconv_wino24_kernel<false>, dim3((unsigned)grid), dim3(WNTHR), (size_t)lds, (hipStream_t)stream, p, tpw, xcd_group, W24NoRgb{});
-    }
-    SIS_CHECK_LAUNCH(name);
-    return 0;
+    return wino512_plan(WINO24_FORM, p, cin, cout, h, w) > 0 ? 1 : 0;
 }
 
 extern "C" int sis_modconv2d_wino24(float* out, const float* x, const float* u24, const float* s, const float* dscale,
                                     const float* noise, int64_t noise_batch_stride, const float* noise_weight, const float* bias,
                                     int batch, int cin, int cout, int h, int w, int fuse_act, int tiles_per_wg, void* stream) {
     if (batch == 0) return 0;
-    return wino24_launch("sis_modconv2d_wino24", out, x, u24, s, dscale, noise, noise_batch_stride, noise_weight, bias, batch, cin, cout,
-                         h, w, fuse_act, tiles_per_wg, nullptr, stream);
+    return wino512_launch<WINO24_FORM>("sis_modconv2d_wino24", out, x, u24, s, dscale, noise, noise_batch_stride, noise_weight, bias,
+                                       batch, cin, cout, h, w, fuse_act, tiles_per_wg, nullptr, stream);
 }
 
 extern "C" int sis_modconv2d_wino24_rgb(float* out, float* rgb_part, const float* x, const float* u24, const float* s, const float* dscale,
@@ -542,7 +438,7 @@ extern "C" int sis_modconv2d_wino24_rgb(float* out, float* rgb_part, const float
     if (batch == 0) return 0;
     SIS_REQUIRE(rgb_part && rgb_w && rgb_s, "sis_modconv2d_wino24_rgb: null pointer");
     SIS_REQUIRE(((uintptr_t)rgb_part & 15) == 0, "sis_modconv2d_wino24_rgb: rgb_part must be 16-byte aligned");
-    const W24Rgb rgb = {rgb_w, rgb_s, rgb_part, rgb_scale};
-    return wino24_launch("sis_modconv2d_wino24_rgb", out, x, u24, s, dscale, noise, noise_batch_stride, noise_weight, bias, batch, cin,
-                         cout, h, w, fuse_act, tiles_per_wg, &rgb, stream);
+    const WinoRgb rgb = {rgb_w, rgb_s, rgb_part, rgb_scale};
+    return wino512_launch<WINO24_FORM>("sis_modconv2d_wino24_rgb", out, x, u24, s, dscale, noise, noise_batch_stride, noise_weight,
+                                       bias, batch, cin, cout, h, w, fuse_act, tiles_per_wg, &rgb, stream);
 }

@@ -1,6 +1,6 @@
 // Stride-1 3x3 modulated convolution in Winograd F(4x4, 3x3) form: 4 x 4 outputs per tile from a 6 x 6 input patch, 36 multiplies
-// per 16 outputs (36/144 of the direct form; F(2x4,3x3) in modconv_wino24.h: 24/72).  Included at the end of modconv_wino.hip
-// behind modconv_wino24.h (one translation unit: the helpers above and the DMA plan of that file are shared).
+// per 16 outputs (36/144 of the direct form; F(2x4,3x3): 24/72).  Included at the end of modconv_wino.hip
+// behind modconv_wino_tile512.h, which holds what this form shares with F(2x4,3x3).
 //
 //   U[ci][i][j][co] = (G4 g G4^T)[i][j]  i, j = 0..5: the 6-point transform (points 0, +-1, +-2, inf) on both axes; prepacked once
 //                                        per checkpoint (sis_modconv_prepack_wino44) as [ci][row][co][4], 9 rows per channel.
@@ -24,23 +24,20 @@
 // tile 2 x 11.25 KB: 139 KB of LDS.
 //
 // modconv_wino44_kernel<true> also forms the channel sum of the ToRGB layer that follows, per 64-channel block, in the layout of
-// modconv_wino24_kernel<true>.  Sum order within a block: a lane adds its 4 channels in ascending order (FMA chain from 0), the 16
+// the F(2x4) kernel.  Sum order within a block: a lane adds its 4 channels in ascending order (FMA chain from 0), the 16
 // lanes that hold a pixel's 64 channels are then added in the order wm, q, lane group (each ascending), i.e. by ascending channel.
 
 namespace {
 
-constexpr int W44_CC = 4;                        // input channels per chunk
 constexpr int W44_T = 32;                        // 4 x 4 tiles per workgroup
 constexpr int W44_UC = 9 * WMBLK * 4;            // floats of a channel's weight rows  [row][co][4]
 constexpr int W44_VC = 9 * W44_T * 4;            // floats of a channel's V rows       [row][tile][4]
-constexpr int W44_UF = W44_CC * W44_UC;          // floats of a weight chunk
-constexpr int W44_VF = W44_CC * W44_VC;          // floats of a V chunk
-constexpr int W44_XT = W24_XT;                   // floats per channel of the staged input tile: 10 x 72 or 18 x 40
-constexpr int W44_XP = W24_XP;
+constexpr int W44_UF = W512_CC * W44_UC;         // floats of a weight chunk
+constexpr int W44_VF = W512_CC * W44_VC;         // floats of a V chunk
 constexpr int W44_XCH = 48 * 64;                 // floats one wave sends to its partner in the epilogue
 constexpr int W44_BAR = 30;                      // MFMA slot of a chunk behind which its barrier sits
 // MFMA slots of a chunk's DMA instructions: the two input pieces first (they come from HBM or from the L2 of another XCD, and the
-// barrier's vmcnt(0) waits for them; see modconv_wino24.h), the weight rows behind them.  A third input buffer with the input two
+// barrier's vmcnt(0) waits for them; see the F(2x4) form), the weight rows behind them.  A third input buffer with the input two
 // chunks ahead and the barrier at vmcnt(2) measured no faster (profiles/wino44_layers.txt).
 constexpr int W44_SX[2] = {2, 4};
 constexpr int W44_SU[5] = {6, 10, 12, 14, 18};
@@ -59,23 +56,12 @@ __global__ __launch_bounds__(256) void wino44_prepack_kernel(float* __restrict__
     float t[6][3];  // G4 g
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const float a = g[c], b = g[3 + c], d = g[6 + c];
-        t[0][c] = 0.25f * a;
-        t[1][c] = (-1.f / 6.f) * (a + b + d);
-        t[2][c] = (-1.f / 6.f) * (a - b + d);
-        t[3][c] = (1.f / 24.f) * a + (1.f / 12.f) * b + (1.f / 6.f) * d;
-        t[4][c] = (1.f / 24.f) * a - (1.f / 12.f) * b + (1.f / 6.f) * d;
-        t[5][c] = d;
+        wino_g6<3, 3>(g + c, &t[0][c]);
     }
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
-        const float a = t[i][0], b = t[i][1], c = t[i][2];
-        const float o[6] = {0.25f * a,
-                            (-1.f / 6.f) * (a + b + c),
-                            (-1.f / 6.f) * (a - b + c),
-                            (1.f / 24.f) * a + (1.f / 12.f) * b + (1.f / 6.f) * c,
-                            (1.f / 24.f) * a - (1.f / 12.f) * b + (1.f / 6.f) * c,
-                            c};
+        float o[6];
+        wino_g6<1, 1>(t[i], o);
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
             const int q = j / 3, pl = w44_plane(i, j % 3);
@@ -87,8 +73,8 @@ __global__ __launch_bounds__(256) void wino44_prepack_kernel(float* __restrict__
 
 template <bool RGB>
 __global__ __launch_bounds__(WNTHR, 2) void modconv_wino44_kernel(const ConvParams p, const int tiles_per_wg, const int xcd_group,
-                                                                  const std::conditional_t<RGB, W24Rgb, W24NoRgb> rgb) {
-    constexpr int CC = W44_CC, UF = W44_UF, VF = W44_VF, XT = W44_XT, UC = W44_UC, VC = W44_VC;
+                                                                  const std::conditional_t<RGB, WinoRgb, WinoNoRgb> rgb) {
+    constexpr int CC = W512_CC, UF = W44_UF, VF = W44_VF, XT = W512_XT, UC = W44_UC, VC = W44_VC;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* Ul = lds;                  // [2][UF]
     float* Vl = Ul + 2 * UF;          // [2][VF]   (Ul and Vl together, 108 KB: the first 96 KB are the column exchange of the epilogue)
@@ -103,7 +89,7 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino44_kernel(const ConvPara
     const int l15 = lane & 15, lg = lane >> 4;
     const int q = wave & 1, wn = (wave >> 1) & 1, wm = wave >> 2;
 
-    // workgroup order: as modconv_wino24_kernel
+    // workgroup order (twin: modconv_wino24_kernel, down to txs, without the weight rows)
     const int n_co = p.Cout / WMBLK;
     const int wg = xcd_group ? (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
     const int o0 = (wg % n_co) * WMBLK;
@@ -124,14 +110,14 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino44_kernel(const ConvPara
         const int row = wave + it * 8;
         if (it < 4 || wave < 4) sis_buffer_load_lds16(u_rsrc, Ul + buf * UF + row * 256, u_voff, (unsigned)(ci0 * 9 + row) * u_row_bytes);
     };
-    // input tile: the pieces of modconv_wino24_kernel (4 channels x 3 pieces of 64 float4); wave w moves piece w, and the waves
+    // input tile: the pieces of the F(2x4) kernel (4 channels x 3 pieces of 64 float4); wave w moves piece w, and the waves
     // 0..3 piece w + 8 (a wave-uniform branch around the second)
     int xp_ch[2], xp_base[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        const int piece = k == 0 ? wave : (wave + 8) % (CC * W44_XP);   // (k = 1 is used by the waves 0..3 only)
-        xp_ch[k] = piece / W44_XP;
-        xp_base[k] = min((piece % W44_XP) * 256, XT - 256);
+        const int piece = k == 0 ? wave : (wave + 8) % (CC * W512_XP);   // (k = 1 is used by the waves 0..3 only)
+        xp_ch[k] = piece / W512_XP;
+        xp_base[k] = min((piece % W512_XP) * 256, XT - 256);
     }
     struct TileState {
         int b, h0, w0;
@@ -183,31 +169,15 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino44_kernel(const ConvPara
         };
         auto t_col = [&](int r) {  // (d B6)[S + r][3 Q + jj]
             const float a = dm[r].x, b = dm[r].y, c = dm[r].z, d = dm[r].w, e = de[r];
-            if (Q == 0) {
-                const float u = fmaf(-4.f, b, d), v = fmaf(-4.f, a, c);
-                ee[r][0] = fmaf(4.f, e, fmaf(-5.f, b, d));
-                ee[r][1] = u + v;
-                ee[r][2] = u - v;
-            } else {
-                const float u = d - b, v = c - a;
-                ee[r][0] = fmaf(2.f, v, u);
-                ee[r][1] = fmaf(-2.f, v, u);
-                ee[r][2] = fmaf(4.f, a, fmaf(-5.f, c, e));
-            }
+            const float lo[5] = {e, a, b, c, d}, hi[5] = {a, b, c, d, e};  // d0..d4, d1..d5
+            wino_b6_half<Q>(Q == 0 ? lo : hi, 1.f, ee[r]);
         };
         auto t_row = [&](int jj) {  // rows 3 S .. 3 S + 2 of B6^T (d B6), scaled by the style
-            const float e0 = ee[0][jj], e1 = ee[1][jj], e2 = ee[2][jj], e3 = ee[3][jj], e4 = ee[4][jj];
-            if (S == 0) {
-                const float u = fmaf(-4.f, e2, e4), v = fmaf(-4.f, e1, e3);
-                oo[0][jj] = fmaf(4.f, e0, fmaf(-5.f, e2, e4)) * sv;
-                oo[1][jj] = (u + v) * sv;
-                oo[2][jj] = (u - v) * sv;
-            } else {
-                const float u = e3 - e1, v = e2 - e0;
-                oo[0][jj] = fmaf(2.f, v, u) * sv;
-                oo[1][jj] = fmaf(-2.f, v, u) * sv;
-                oo[2][jj] = fmaf(4.f, e0, fmaf(-5.f, e2, e4)) * sv;
-            }
+            const float e[5] = {ee[0][jj], ee[1][jj], ee[2][jj], ee[3][jj], ee[4][jj]};
+            float o[3];
+            wino_b6_half<S>(e, sv, o);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) oo[i][jj] = o[i];
         };
         auto t_write = [&](float* vc) {
             *reinterpret_cast<sis_f32x4*>(vc + tvo) = sis_f32x4{oo[0][0], oo[0][1], oo[0][2], oo[1][0]};
@@ -234,9 +204,7 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino44_kernel(const ConvPara
             for (int e = 0; e < 18; ++e)
 #pragma unroll
                 for (int h = 0; h < 2; ++h) acc[e][h] = sis_f32x4{0.f, 0.f, 0.f, 0.f};
-            // lane-derived values of the tile start and of the epilogue: from opaque copies of the thread index (modconv_wino24.h)
-            int tp = tid;
-            asm volatile("" : "+v"(tp));
+            const int tp = wino_opaque_tid();
             tile_setup(pt_first + k * pt_step, T, tp & 63);
             if (k > 0) __syncthreads();  // everyone is done with the previous tile's exchange area and tail operands
             // first DMA of the tile: weights chunk 0, input chunks 0 and 1
@@ -246,18 +214,9 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino44_kernel(const ConvPara
             for (int kx = 0; kx < 2; ++kx) stage_x_piece(0, 0, kx);
 #pragma unroll
             for (int kx = 0; kx < 2; ++kx) stage_x_piece(min(CC, k_last), 1, kx);
-            // style row and layer-tail operands of the tile
+            // style row (twin: modconv_wino24_kernel) and layer-tail operands of the tile
             for (int e = tp; e < p.Cin; e += WNTHR) Sl[e] = p.s[(int64_t)T.b * p.Cin + e];
-            if (tp < WMBLK) {
-                Dl[tp] = p.dscale[(int64_t)T.b * p.Cout + o0 + tp];
-                Bl[tp] = (p.fuse && p.bias) ? p.bias[o0 + tp] : 0.f;
-            }
-            if constexpr (RGB) {
-                if (tp < 3 * WMBLK) {
-                    const int co = o0 + (tp & (WMBLK - 1));
-                    Wl[tp] = rgb.scale * rgb.w[(tp / WMBLK) * p.Cout + co] * rgb.s[(int64_t)T.b * p.Cout + co];
-                }
-            }
+            wino512_stage_tail_operands<RGB>(p, rgb, T.b, o0, tp, Dl, Bl, Wl);
             {
                 const int tt_ = tp >> 4, e = tp & 15;
                 const int yy = T.h0 + 4 * (tt_ >> txs) + (e >> 2), xx = T.w0 + 4 * (tt_ & ((1 << txs) - 1)) + (e & 3);
@@ -347,8 +306,7 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino44_kernel(const ConvPara
             // wm * 32 + 16 Q + 4 lg + reg) and hands its m of the other fragment to its partner:
             // [pair][sender Q][reg][r][jj][64 lanes] over Ul / Vl.
             float mine[4][4][3];
-            int te = tid;
-            asm volatile("" : "+v"(te));
+            const int te = wino_opaque_tid();
             const int lane = te & 63, l15 = te & 15, lg = (te >> 4) & 3;
             float* xch = lds + (wave >> 1) * (2 * W44_XCH);
 #pragma unroll
@@ -360,8 +318,9 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino44_kernel(const ConvPara
                     for (int jj = 0; jj < 3; ++jj) {
                         const float a0 = acc[w44_plane(0, jj)][h][reg], a1 = acc[w44_plane(1, jj)][h][reg], a2 = acc[w44_plane(2, jj)][h][reg];
                         const float a3 = acc[w44_plane(3, jj)][h][reg], a4 = acc[w44_plane(4, jj)][h][reg], a5 = acc[w44_plane(5, jj)][h][reg];
-                        const float s12 = a1 + a2, d12 = a1 - a2, s34 = a3 + a4, d34 = a3 - a4;
-                        const float m[4] = {(a0 + s12) + s34, fmaf(2.f, d34, d12), fmaf(4.f, s34, s12), fmaf(8.f, d34, d12) + a5};
+                        const float a6[6] = {a0, a1, a2, a3, a4, a5};
+                        float m[4];
+                        wino_a4(a6, a6 + 3, m);
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             if (h == Q) mine[reg][r][jj] = m[r];
@@ -401,17 +360,12 @@ __global__ __launch_bounds__(WNTHR, 2) void modconv_wino44_kernel(const ConvPara
                     for (int r = 0; r < 4; ++r) {
                         const float* ma = Q == 0 ? mine[reg][r] : theirs[r];  // columns j = 0..2
                         const float* mb = Q == 0 ? theirs[r] : mine[reg][r];  // columns j = 3..5
-                        const float sa = ma[1] + ma[2], da = ma[1] - ma[2], sb = mb[0] + mb[1], db = mb[0] - mb[1];
-                        const float y[4] = {(ma[0] + sa) + sb, fmaf(2.f, db, da), fmaf(4.f, sb, sa), fmaf(8.f, db, da) + mb[2]};
+                        float y[4];
+                        wino_a4(ma, mb, y);
                         const float nzv[4] = {nz[r].x, nz[r].y, nz[r].z, nz[r].w};
                         float o[4];
 #pragma unroll
-                        for (int x = 0; x < 4; ++x) {
-                            float val = y[x] * dd;
-                            val += nzv[x];
-                            val += bb;
-                            o[x] = fmaxf(val, val * slope) * gain;  // = (val > 0 ? val : 0.2 val) * sqrt(2) when the tail is on
-                        }
+                        for (int x = 0; x < 4; ++x) o[x] = wino_layer_tail(y[x], dd, nzv[x], bb, slope, gain);
                         *reinterpret_cast<sis_f32x4*>(obase + (int64_t)reg * HW + r * p.W) = sis_f32x4{o[0], o[1], o[2], o[3]};
                         if constexpr (RGB) {
 #pragma unroll
@@ -471,81 +425,23 @@ extern "C" int sis_modconv_prepack_wino44(float* u, const float* w, int cout, in
     return 0;
 }
 
-// The F(4x4,3x3) kernel takes a layer by (Cin, Cout, H, W) alone: the F(2x4) kernel's rule with whole 4 x 4 tiles (H % 4, W % 4).
-static int wino44_plan(ConvParams& p, int cin, int cout, int h, int w, bool rgb = false) {
-    if (cin <= 0 || cout <= 0 || h <= 0 || w <= 0) return -1;
-    if (cin % 8 || cout % WMBLK || h % 4 || w % 4) return -1;
-    if ((int64_t)cin * h * w * 4 >= ((int64_t)1 << 31) || (int64_t)cin * cout * 144 >= ((int64_t)1 << 31)) return -1;  // 32-bit DMA offsets
-    p.Cin = cin;
-    mc_reset_splitk(p);
-    mc_reset_tiles(p);
-    mc_add_class(p, 512, 2, 1, 0, h, 0, w, 64, 1);
-    const TileClass& tc = p.cls[0];
-    if (tc.nb != 1 || tc.th_log2 + tc.tw_log2 != 9 || tc.tw_log2 < 5) return -1;
-    if (((1 << tc.th_log2) + 2) * ((1 << tc.tw_log2) + 8) != W44_XT) return -1;
-    const size_t lds = (size_t)(2 * W44_UF + 2 * W44_VF + 2 * W44_CC * W44_XT + cin + (rgb ? 5 : 2) * WMBLK + W44_T * 16) * sizeof(float);
-    if (lds > 160 * 1024) return -1;
-    return (int)lds;
+namespace {
+constexpr Wino512Form WINO44_FORM = {4, 36, W44_UF, W44_VF, W44_T * 16, "modconv_wino44_kernel", "sis_modconv_wino44_eligible",
+                                     modconv_wino44_kernel<true>, modconv_wino44_kernel<false>};
 }
 
+// wino512_plan's rule (4 x 4 outputs per tile: H % 4, W % 4)
 extern "C" int sis_modconv_wino44_eligible(int cin, int cout, int h, int w) {
     ConvParams p;
-    return wino44_plan(p, cin, cout, h, w) > 0 ? 1 : 0;
-}
-
-// Both entries below: out as sis_modconv2d_wino44 documents it; rgb (or null) selects the instantiation with the RGB partial sums.
-static int wino44_launch(const char* name, float* out, const float* x, const float* u44, const float* s, const float* dscale,
-                         const float* noise, int64_t noise_batch_stride, const float* noise_weight, const float* bias, int batch,
-                         int cin, int cout, int h, int w, int fuse_act, int tiles_per_wg, const W24Rgb* rgb, void* stream) {
-    SIS_REQUIRE(out && x && u44 && s && dscale, "%s: null pointer", name);
-    SIS_REQUIRE(batch > 0, "%s: non-positive size", name);
-    if (noise) SIS_REQUIRE(noise_weight, "%s: noise given without noise_weight", name);
-    ConvParams p = mc_params(out, x, u44, s, dscale, noise, noise_batch_stride, noise_weight, bias, batch, cin, cout, h, w, h, w, w,
-                             fuse_act != 0);
-    const int lds = wino44_plan(p, cin, cout, h, w, rgb != nullptr);
-    SIS_REQUIRE(lds > 0, "%s: shape %dx%d, %d -> %d not eligible (sis_modconv_wino44_eligible)", name, h, w, cin, cout);
-    SIS_REQUIRE((int64_t)batch * (cin > cout ? cin : cout) * h * w < ((int64_t)1 << 31), "%s: tensor too large", name);
-    SIS_REQUIRE(((((uintptr_t)x | (uintptr_t)u44 | (uintptr_t)out) & 15) == 0) && (!noise || ((uintptr_t)noise & 3) == 0),
-                "%s: pointers must be 16-byte aligned", name);
-    const TileClass& tc = p.cls[0];
-    const int64_t tiles = (int64_t)batch * tc.nth * tc.ntw;  // one-sample tiles
-    p.npos_tiles = (int)tiles;
-    const int n_co = cout / WMBLK;
-    const int64_t blocks = tiles * n_co;
-    SIS_REQUIRE(blocks < ((int64_t)1 << 31), "%s: bad grid", name);
-    // pixel tiles per workgroup: as sis_modconv2d_wino24 (scheduling only; tiles_per_wg > 0 is the tests' override)
-    int tpw = 1;
-    if (tiles_per_wg > 0) {
-        SIS_REQUIRE(tiles % tiles_per_wg == 0, "%s: %d tiles per workgroup do not divide %lld tiles", name, tiles_per_wg, (long long)tiles);
-        tpw = tiles_per_wg;
-    } else {
-        while (tpw * 2 <= 16 && tiles % (tpw * 2) == 0 && blocks / (tpw * 2) >= 1024) tpw *= 2;
-    }
-    const int64_t grid = blocks / tpw;
-    const int xcd_group = (double)cin * cout * 36 * sizeof(float) <= 5.0 * 1048576.0 && n_co > 1 && grid % (8 * n_co) == 0;
-    static bool have_attr[2] = {false, false};
-    const void* fn = rgb ? reinterpret_cast<const void*>(&modconv_wino44_kernel<true>) : reinterpret_cast<const void*>(&modconv_wino44_kernel<false>);
-    if (!have_attr[rgb != nullptr]) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return sis_fail("modconv: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-        have_attr[rgb != nullptr] = true;
-    }
-    sis_kernel_name = "modconv_wino44_kernel";  // both instantiations: one kernel to the per-kernel records
-    if (rgb) {
-        hipLaunchKernelGGL(modconv_wino44_kernel<true>, dim3((unsigned)grid), dim3(WNTHR), (size_t)lds, (hipStream_t)stream, p, tpw, xcd_group, *rgb);
-    } else {
-        hipLaunchKernelGGL(modconv_wino44_kernel<false>, dim3((unsigned)grid), dim3(WNTHR), (size_t)lds, (hipStream_t)stream, p, tpw, xcd_group, W24NoRgb{});
-    }
-    SIS_CHECK_LAUNCH(name);
-    return 0;
+    return wino512_plan(WINO44_FORM, p, cin, cout, h, w) > 0 ? 1 : 0;
 }
 
 extern "C" int sis_modconv2d_wino44(float* out, const float* x, const float* u44, const float* s, const float* dscale,
                                     const float* noise, int64_t noise_batch_stride, const float* noise_weight, const float* bias,
                                     int batch, int cin, int cout, int h, int w, int fuse_act, int tiles_per_wg, void* stream) {
     if (batch == 0) return 0;
-    return wino44_launch("sis_modconv2d_wino44", out, x, u44, s, dscale, noise, noise_batch_stride, noise_weight, bias, batch, cin, cout,
-                         h, w, fuse_act, tiles_per_wg, nullptr, stream);
+    return wino512_launch<WINO44_FORM>("sis_modconv2d_wino44", out, x, u44, s, dscale, noise, noise_batch_stride, noise_weight, bias,
+                                       batch, cin, cout, h, w, fuse_act, tiles_per_wg, nullptr, stream);
 }
 
 extern "C" int sis_modconv2d_wino44_rgb(float* out, float* rgb_part, const float* x, const float* u44, const float* s, const float* dscale,
@@ -555,7 +451,7 @@ extern "C" int sis_modconv2d_wino44_rgb(float* out, float* rgb_part, const float
     if (batch == 0) return 0;
     SIS_REQUIRE(rgb_part && rgb_w && rgb_s, "sis_modconv2d_wino44_rgb: null pointer");
     SIS_REQUIRE(((uintptr_t)rgb_part & 15) == 0, "sis_modconv2d_wino44_rgb: rgb_part must be 16-byte aligned");
-    const W24Rgb rgb = {rgb_w, rgb_s, rgb_part, rgb_scale};
-    return wino44_launch("sis_modconv2d_wino44_rgb", out, x, u44, s, dscale, noise, noise_batch_stride, noise_weight, bias, batch, cin,
-                         cout, h, w, fuse_act, tiles_per_wg, &rgb, stream);
+    const WinoRgb rgb = {rgb_w, rgb_s, rgb_part, rgb_scale};
+    return wino512_launch<WINO44_FORM>("sis_modconv2d_wino44_rgb", out, x, u44, s, dscale, noise, noise_batch_stride, noise_weight,
+                                       bias, batch, cin, cout, h, w, fuse_act, tiles_per_wg, &rgb, stream);
 }

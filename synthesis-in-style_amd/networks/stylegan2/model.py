@@ -126,19 +126,18 @@ class EqualLinear(nn.Module):
 
 MATRIX_PRECISIONS = ("fp32", "bf16")
 # How a stride-1 3x3 layer runs an h x w map in inference (ModulatedConv2d.route), in order of precedence: bf16 operands on the
-# bf16 matrix cores (opt-in), Winograd F(2x4,3x3), Winograd F(2x2,3x3), the direct kernel.  Everything else is "direct".
-ROUTES = ("bf16", "wino24", "wino", "direct")
-# "wino44", Winograd F(4x4,3x3) (csrc/modconv_wino44.h), stands ahead of "wino24" for the layers of WINO44_LAYERS: the
-# (Cin, Cout, H, W) on which that kernel measured faster than F(2x4,3x3) beyond its launch spread, with a device error under half
-# the per-layer bound (profiles/wino44_layers.txt).  SIS_WINO44=0 restores the routes above exactly.
-WINO44_ROUTE = "wino44"
+# bf16 matrix cores (opt-in), Winograd F(4x4,3x3), F(2x4,3x3), F(2x2,3x3), the direct kernel.  Everything else is "direct".
+ROUTES = ("bf16", "wino44", "wino24", "wino", "direct")
+# "wino44" (csrc/modconv_wino44.h) is taken by the layers of WINO44_LAYERS only: the (Cin, Cout, H, W) on which that kernel
+# measured faster than F(2x4,3x3) beyond its launch spread, with a device error under half the per-layer bound (DESIGN 3.2e,
+# profiles/wino44_layers.txt).  SIS_WINO44=0 gives the routes of a tree without it exactly.
 WINO44_LAYERS = frozenset({(256, 256, 128, 128), (128, 128, 256, 256)})
-WINOGRAD_RGB_ROUTES = (WINO44_ROUTE, "wino24")   # the routes whose kernel can also leave the following ToRGB's channel sum
+WINOGRAD_RGB_ROUTES = ("wino44", "wino24")   # the routes whose kernel can also leave the following ToRGB's channel sum
 # weight image of a route (and of the fast-FIR up-convolution): the keyword that carries it into sis_hip and what packs it
-_IMAGES = {"bf16": ("bf16_w", "modconv_prepack_bf16"), WINO44_ROUTE: ("wino44_u", "modconv_prepack_wino44"),
+_IMAGES = {"bf16": ("bf16_w", "modconv_prepack_bf16"), "wino44": ("wino44_u", "modconv_prepack_wino44"),
            "wino24": ("wino24_u", "modconv_prepack_wino24"),
            "wino": ("wino_u", "modconv_prepack_wino"), "up_fir": ("fir_u", "modconv_prepack_up_fir")}
-_Switches = collections.namedtuple("_Switches", ROUTES[:1] + (WINO44_ROUTE,) + ROUTES[1:3])   # whether the layer may take each route at all
+_Switches = collections.namedtuple("_Switches", ROUTES[:4])   # whether the layer may take each route at all
 
 
 class ModulatedConv2d(nn.Module):
@@ -216,14 +215,14 @@ class ModulatedConv2d(nn.Module):
             self._switches = self._switches._replace(bf16=self._read_switches().bf16)
 
     def route(self, h, w):
-        """The one of ROUTES (or WINO44_ROUTE) an h x w map of this layer runs on: the switches as the current pack read them
+        """The one of ROUTES an h x w map of this layer runs on: the switches as the current pack read them
         (afresh where there is no pack), then the library's own eligibility answers -- the batch plays no part."""
         on = self._switches if self._pack_key is not None else self._read_switches()
         if on.bf16 and sis_hip.modconv_bf16_eligible(self.in_channel, self.out_channel, h, w):
             return "bf16"
         if (on.wino44 and (self.in_channel, self.out_channel, h, w) in WINO44_LAYERS
                 and sis_hip.modconv_wino44_eligible(self.in_channel, self.out_channel, h, w)):
-            return WINO44_ROUTE
+            return "wino44"
         if on.wino24 and sis_hip.modconv_wino24_eligible(self.in_channel, self.out_channel, h, w):
             return "wino24"
         return "wino" if on.wino else "direct"

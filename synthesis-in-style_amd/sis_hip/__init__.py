@@ -585,53 +585,53 @@ def modconv_prepack(weight):
     return wpk, wsq
 
 
-def modconv_prepack_wino(weight):
-    """[1, Cout, Cin, 3, 3] -> Winograd F(2x2,3x3) transformed weights [Cin, 16, Cout]."""
+def _prepack_winograd(form, weight, lead, trail):
+    """[1, Cout, Cin, 3, 3] -> the transformed weights of a Winograd form, [Cin, *lead, Cout, *trail], through its prepack entry."""
     w = _f32(weight, "weight")
     _, cout, cin, k, _ = w.shape
     if k != 3:
         raise RuntimeError("the Winograd transform is for 3x3 kernels")
-    u = torch.empty((cin, 16, cout), dtype=torch.float32, device=w.device)
+    u = torch.empty((cin,) + lead + (cout,) + trail, dtype=torch.float32, device=w.device)
+    symbol = f"sis_modconv_prepack_{form}"
     with torch.cuda.device(w.device):
-        _check(_launch("modconv_prepack_wino", 0.0, 4.0 * (w.numel() + u.numel()),
-                       lambda: lib().sis_modconv_prepack_wino(_ptr(u), _ptr(w), cout, cin, _stream())), "sis_modconv_prepack_wino")
+        _check(_launch(symbol[4:], 0.0, 4.0 * (w.numel() + u.numel()),
+                       lambda: getattr(lib(), symbol)(_ptr(u), _ptr(w), cout, cin, _stream())), symbol)
     return u
+
+
+def modconv_prepack_wino(weight):
+    """[1, Cout, Cin, 3, 3] -> Winograd F(2x2,3x3) transformed weights [Cin, 16, Cout]."""
+    return _prepack_winograd("wino", weight, (16,), ())
+
+
+def _wino512_eligible(form, cin, cout, h, w):
+    return bool(getattr(lib(), f"sis_modconv_{form}_eligible")(int(cin), int(cout), int(h), int(w)))
 
 
 def modconv_prepack_wino24(weight):
     """[1, Cout, Cin, 3, 3] -> Winograd F(2x4,3x3) transformed weights G2 g G4^T, [Cin, 2 column halves, 3, Cout, 4]."""
-    w = _f32(weight, "weight")
-    _, cout, cin, k, _ = w.shape
-    if k != 3:
-        raise RuntimeError("the Winograd transform is for 3x3 kernels")
-    u = torch.empty((cin, 2, 3, cout, 4), dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        _check(_launch("modconv_prepack_wino24", 0.0, 4.0 * (w.numel() + u.numel()),
-                       lambda: lib().sis_modconv_prepack_wino24(_ptr(u), _ptr(w), cout, cin, _stream())), "sis_modconv_prepack_wino24")
-    return u
+    return _prepack_winograd("wino24", weight, (2, 3), (4,))
 
 
 def modconv_wino24_eligible(cin, cout, h, w):
     """True when the F(2x4,3x3) kernel takes a stride-1 3x3 layer of this shape; the batch size plays no part."""
-    return bool(lib().sis_modconv_wino24_eligible(int(cin), int(cout), int(h), int(w)))
+    return _wino512_eligible("wino24", cin, cout, h, w)
 
 
 def modconv_prepack_wino44(weight):
     """[1, Cout, Cin, 3, 3] -> Winograd F(4x4,3x3) transformed weights G4 g G4^T, [Cin, 9 rows, Cout, 4] (csrc/modconv_wino44.h)."""
-    w = _f32(weight, "weight")
-    _, cout, cin, k, _ = w.shape
-    if k != 3:
-        raise RuntimeError("the Winograd transform is for 3x3 kernels")
-    u = torch.empty((cin, 9, cout, 4), dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        _check(_launch("modconv_prepack_wino44", 0.0, 4.0 * (w.numel() + u.numel()),
-                       lambda: lib().sis_modconv_prepack_wino44(_ptr(u), _ptr(w), cout, cin, _stream())), "sis_modconv_prepack_wino44")
-    return u
+    return _prepack_winograd("wino44", weight, (9,), (4,))
 
 
 def modconv_wino44_eligible(cin, cout, h, w):
     """True when the F(4x4,3x3) kernel takes a stride-1 3x3 layer of this shape; the batch size plays no part."""
-    return bool(lib().sis_modconv_wino44_eligible(int(cin), int(cout), int(h), int(w)))
+    return _wino512_eligible("wino44", cin, cout, h, w)
+
+
+# The Winograd forms on 512-pixel tiles, by precedence: (plain symbol, rgb symbol, factor on the direct-form FLOP count).  bench.py
+# prices a kernel named "...wino..." at 16/36 of the recorded count: 9/16 x 16/36 = 36/144 and 3/4 x 16/36 = 24/72 are what these run.
+_WINO512 = {"wino44": ("sis_modconv2d_wino44", "sis_modconv2d_wino44_rgb", 0.5625),
+            "wino24": ("sis_modconv2d_wino24", "sis_modconv2d_wino24_rgb", 0.75)}
 
 
 BF16_KERNEL = "modconv_bf16_kernel"
@@ -1084,37 +1084,37 @@ def modconv2d(x, wpk, s, dscale, ksize, noise=None, noise_weight=None, bias=None
     tail = (_ptr(s), _ptr(dscale), _ptr(noise), nbs, _ptr(noise_weight), _ptr(bias))
     shape, fuse, fast = (batch, cin, cout, h, w), int(bool(fuse_act)), ksize == 3 and batch > 0
     # The entry, chosen once: its C symbol, the factor on the direct-form FLOP count, what it reads besides x (with the element
-    # size) and its arguments up to the stream.  0.75 for the F(2x4,3x3) entries: bench.py prices every kernel whose name contains
-    # "wino" at 16/36 of the recorded count, and 3/4 x 16/36 = 24/72 is what that kernel executes; 9/16 for the F(4x4,3x3)
-    # entries: 9/16 x 16/36 = 36/144.
-    w44 = wino44_u is not None
-    if w44 and not (fast and modconv_wino44_eligible(cin, cout, h, w)):
-        raise RuntimeError(f"modconv2d: wino44_u= needs the F(4x4,3x3) kernel, which does not take {cin} -> {cout} at {h}x{w}")
-    if rgb is not None:
-        if not w44 and (wino24_u is None or not fast or not modconv_wino24_eligible(cin, cout, h, w)):
+    # size) and its arguments up to the stream.
+    form = None
+    if wino44_u is not None:
+        if not (fast and modconv_wino44_eligible(cin, cout, h, w)):
+            raise RuntimeError(f"modconv2d: wino44_u= needs the F(4x4,3x3) kernel, which does not take {cin} -> {cout} at {h}x{w}")
+        form = "wino44"
+    elif rgb is not None:
+        if wino24_u is None or not fast or not modconv_wino24_eligible(cin, cout, h, w):
             raise RuntimeError(f"modconv2d: rgb= needs the F(2x4,3x3) kernel, which does not take {cin} -> {cout} at {h}x{w}")
-        rgb_w, rgb_s, rgb_scale, part = rgb
-        rgb_w, rgb_s = _f32(rgb_w, "rgb weight"), _f32(rgb_s, "rgb style")
-        if rgb_w.numel() != 3 * cout or tuple(rgb_s.shape) != (batch, cout):
-            raise RuntimeError(f"modconv2d: rgb weight {tuple(rgb_w.shape)} / style {tuple(rgb_s.shape)} do not fit 3 x {cout} channels")
-        _out_or_new(part, rgb_part_shape(batch, cout, h, w), x.device, "modconv2d rgb part")
-        if w44:
-            symbol, factor, reads, u, tpw = "sis_modconv2d_wino44_rgb", 0.5625, ((wino44_u, 4.0), (part, 4.0)), wino44_u, wino44_tiles_per_wg
-        else:
-            symbol, factor, reads, u, tpw = "sis_modconv2d_wino24_rgb", 0.75, ((wino24_u, 4.0), (part, 4.0)), wino24_u, wino24_tiles_per_wg
-        args = (_ptr(out), _ptr(part), _ptr(x), _ptr(u)) + tail + (_ptr(rgb_w), _ptr(rgb_s), float(rgb_scale)) + shape + (
-            fuse, int(tpw))
-    elif w44:
-        symbol, factor, reads = "sis_modconv2d_wino44", 0.5625, ((wino44_u, 4.0),)
-        args = (_ptr(out), _ptr(x), _ptr(wino44_u)) + tail + shape + (fuse, int(wino44_tiles_per_wg))
+        form = "wino24"
     elif bf16_w is not None and fast and modconv_bf16_eligible(cin, cout, h, w):
+        form = "bf16"
+    elif wino24_u is not None and fast and modconv_wino24_eligible(cin, cout, h, w):
+        form = "wino24"
+    if form in _WINO512:
+        u, tpw = (wino44_u, wino44_tiles_per_wg) if form == "wino44" else (wino24_u, wino24_tiles_per_wg)
+        symbol, symbol_rgb, factor = _WINO512[form]
+        reads, args = ((u, 4.0),), (_ptr(out), _ptr(x), _ptr(u)) + tail + shape + (fuse, int(tpw))
+        if rgb is not None:
+            rgb_w, rgb_s, rgb_scale, part = rgb
+            rgb_w, rgb_s = _f32(rgb_w, "rgb weight"), _f32(rgb_s, "rgb style")
+            if rgb_w.numel() != 3 * cout or tuple(rgb_s.shape) != (batch, cout):
+                raise RuntimeError(f"modconv2d: rgb weight {tuple(rgb_w.shape)} / style {tuple(rgb_s.shape)} do not fit 3 x {cout} channels")
+            _out_or_new(part, rgb_part_shape(batch, cout, h, w), x.device, "modconv2d rgb part")
+            symbol, reads = symbol_rgb, reads + ((part, 4.0),)
+            args = (_ptr(out), _ptr(part), _ptr(x), _ptr(u)) + tail + (_ptr(rgb_w), _ptr(rgb_s), float(rgb_scale)) + shape + (fuse, int(tpw))
+    elif form == "bf16":
         if bf16_w.dtype != torch.bfloat16 or bf16_w.numel() != lib().sis_modconv_bf16_packed_elems(cin, cout) or not bf16_w.is_contiguous():
             raise RuntimeError(f"modconv2d: bf16_w is not the modconv_prepack_bf16 image of a {cin} -> {cout} layer")
         symbol, factor, reads = "sis_modconv2d_bf16", 1.0, ((bf16_w, 2.0),)
         args = (_ptr(out), _ptr(x), _ptr(bf16_w)) + tail + shape + (fuse,)
-    elif wino24_u is not None and fast and modconv_wino24_eligible(cin, cout, h, w):
-        symbol, factor, reads = "sis_modconv2d_wino24", 0.75, ((wino24_u, 4.0),)
-        args = (_ptr(out), _ptr(x), _ptr(wino24_u)) + tail + shape + (fuse, int(wino24_tiles_per_wg))
     else:   # the general entry: F(2x2,3x3) where ``wino_u`` is given and that kernel takes the shape, else the direct kernels
         ws = _workspace(x.device)
         symbol, factor, reads = "sis_modconv2d", 1.0, ((wpk, 4.0),)

@@ -48,3 +48,33 @@ def test_f2x4_nested():
 def test_binding_declares_the_entries():
     import sis_hip
     assert {"sis_modconv_prepack_wino24", "sis_modconv_wino24_eligible", "sis_modconv2d_wino24"} <= set(sis_hip.exported_symbols())
+
+
+def test_eligibility_rule():
+    """The explicit cases of test_wino44_cpu.test_eligibility_rule, with the answers of the library before the two plans became
+    one: H needs whole 2 x 4 tiles only, so 18 rows pass here."""
+    import sis_hip
+    ok = sis_hip.modconv_wino24_eligible
+    assert ok(8, 64, 16, 32) and ok(8, 64, 8, 64) and ok(8, 64, 12, 64) and ok(128, 128, 256, 256)
+    assert not ok(12, 64, 16, 32)    # Cin % 8
+    assert not ok(8, 32, 16, 32)     # Cout % 64
+    assert ok(8, 64, 18, 32)         # H % 4 is F(4x4)'s rule: H % 2 here
+    assert ok(8, 64, 14, 64) and not ok(8, 64, 15, 64)   # H % 2
+    assert not ok(8, 64, 16, 34)     # W % 4
+    assert not ok(8, 64, 64, 16)     # W <= 16
+    assert not ok(8, 64, 16, 16)     # fewer than 512 pixels
+
+
+def test_the_two_forms_share_one_rule():
+    """One plan serves both forms (csrc/modconv_wino_tile512.h): they differ in the H multiple, in a 2^31 bound and in an LDS
+    total, and neither of the latter two is reached at these sizes."""
+    import sis_hip
+    ok24, ok44 = sis_hip.modconv_wino24_eligible, sis_hip.modconv_wino44_eligible
+    seen = set()
+    for cin in (8, 16):
+        for cout in (64, 128):
+            for h in range(2, 70, 2):
+                for w in range(4, 140, 4):
+                    assert ok44(cin, cout, h, w) == (ok24(cin, cout, h, w) and h % 4 == 0), (cin, cout, h, w)
+                    seen.add((ok24(cin, cout, h, w), ok44(cin, cout, h, w)))
+    assert seen == {(False, False), (True, False), (True, True)}   # the grid reaches every answer

@@ -83,7 +83,7 @@ def test_route_of_every_layer(monkeypatch, position):
     g = Generator(64, 512, 8, channel_multiplier=2)
     if precision is not None:
         g.set_matrix_precision(precision)
-    assert ROUTES == ("bf16", "wino24", "wino", "direct")
+    assert ROUTES == ("bf16", "wino44", "wino24", "wino", "direct")
     res, skip, routes, images = 4, None, [], {}
     for layer, _ in g._layer_sequence():
         conv = layer.conv

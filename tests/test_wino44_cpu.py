@@ -73,14 +73,15 @@ def _routes(size, monkeypatch, env):
 @pytest.mark.parametrize("size", [256, 64])
 def test_route_names_wino44_exactly_on_the_ship_list(monkeypatch, size):
     import sis_hip
-    from networks.stylegan2.model import WINO44_LAYERS, WINO44_ROUTE
+    from networks.stylegan2.model import ROUTES, WINO44_LAYERS
+    assert "wino44" in ROUTES and ROUTES.index("wino44") < ROUTES.index("wino24")
     routes = _routes(size, monkeypatch, {})
     for cin, cout, res, route in routes:
-        assert (route == WINO44_ROUTE) == ((cin, cout, res, res) in WINO44_LAYERS), (cin, cout, res, route)
+        assert (route == "wino44") == ((cin, cout, res, res) in WINO44_LAYERS), (cin, cout, res, route)
     for cin, cout, h, w in WINO44_LAYERS:
         assert sis_hip.modconv_wino44_eligible(cin, cout, h, w)
     if size == 256:
-        assert {r[:3] for r in routes if r[3] == WINO44_ROUTE} == {l[:3] for l in WINO44_LAYERS}
+        assert {r[:3] for r in routes if r[3] == "wino44"} == {l[:3] for l in WINO44_LAYERS}
 
 
 @pytest.mark.parametrize("size", [256, 64])
@@ -93,13 +94,13 @@ def test_switch_restores_the_previous_routes(monkeypatch, size):
 
 
 def test_rgb_fusion_accepts_both_winograd_routes(monkeypatch):
-    from networks.stylegan2.model import Generator, WINO44_ROUTE
+    from networks.stylegan2.model import Generator
     for name in ("SIS_WINOGRAD", "SIS_WINO24", "SIS_WINO44", "SIS_GEN_PRECISION"):
         monkeypatch.delenv(name, raising=False)
     g = Generator(64, 32, 1, channel_multiplier=2)
     conv, rgb, skip = g.convs[-1], g.to_rgbs[-1], torch.zeros(1)
-    assert g._rgb_fused(conv, rgb, 64, 64, skip, route=WINO44_ROUTE) and g._rgb_fused(conv, rgb, 64, 64, skip, route="wino24")
-    assert not g._rgb_fused(conv, rgb, 64, 64, skip, route="wino") and not g._rgb_fused(conv, rgb, 64, 64, None, route=WINO44_ROUTE)
+    assert g._rgb_fused(conv, rgb, 64, 64, skip, route="wino44") and g._rgb_fused(conv, rgb, 64, 64, skip, route="wino24")
+    assert not g._rgb_fused(conv, rgb, 64, 64, skip, route="wino") and not g._rgb_fused(conv, rgb, 64, 64, None, route="wino44")
 
 
 def test_eligibility_rule():
