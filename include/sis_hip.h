@@ -1169,6 +1169,31 @@ int sis_scan_resample(uint8_t* out, const uint8_t* page, int in_h, int in_w, int
                       const int32_t* count_y, int ksize_y, void* workspace, int64_t workspace_bytes, void* stream);
 int sis_scan_patches(uint8_t* out, const uint8_t* page, const int32_t* origins, int n, int size, int height, int width, void* stream);
 
+/* Scanner-margin removal (csrc/scan_margin.h): the content box of an analysis image uint8 [height][width][3] on
+ * the device, 3 <= height, width <= 4096.  The reference calls OpenCV's blur, Canny, dilate, erode, findContours and
+ * boundingRect; §20 states that sequence in integers from OpenCV's documented behaviour -- nothing was compared with OpenCV.
+ * Integer arithmetic, sums, minima and maxima only: two calls give the same bytes.  Fixed launch sequence on `stream`, nothing
+ * read back.
+ * sis_scan_content_box_workspace_bytes (scripts/create_stylegan_train_dataset.py:49, get_content_box): bytes of device workspace
+ *   of one call; 0 for a side outside 3..4096.
+ * sis_scan_content_box (scripts/create_stylegan_train_dataset.py:49-111, get_content_box with edge_detect=True; :114-138 scale
+ *   the box and crop on the host): 3x3 box blur, Sobel gradients of the strongest channel, non-maximum suppression, hysteresis
+ *   between `low` and `high` (20 and 150 in the tool), closing with the 3x3 cross, one contour per 8-connected component of
+ *   the result E and per hole of E, then the reference's "largest gap of the sorted box areas" cut.
+ *   box int32 [4] = x0, y0, x1, y1 with exclusive ends (the whole image unless info[4] is 0);
+ *   info int32 [8] = contours, outer contours, largest box area, contours kept, decision (0 cut, 1 at most one contour, 2 largest
+ *     area below 0.6 of the image), T (kept: area >= T; 0 unless the decision is 0), pixels of E, 0;
+ *   edges uint8 [height][width] = E as 0 / 255, or NULL;
+ *   contours int32 [max_contours][6] = kind (0 outer, 1 hole), root (smallest y * width + x), x0, y0, w, h: outers by ascending
+ *     root, then holes by ascending root; rows from min(count, max_contours) on are not written; NULL: no table.  Neither box
+ *     nor info depends on max_contours.
+ *   box, info, contours and workspace 4-byte aligned.  Declines with an error code and launches nothing: a null pointer (box,
+ *   info, page, workspace), an unaligned one, a workspace below sis_scan_content_box_workspace_bytes, a side outside 3..4096,
+ *   low < 0, high < low, max_contours < 0. */
+int64_t sis_scan_content_box_workspace_bytes(int height, int width);
+int sis_scan_content_box(int32_t* box, int32_t* info, uint8_t* edges, int32_t* contours, int max_contours, const uint8_t* page,
+                         int height, int width, int low, int high, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Validation pass of the segmenters (csrc/seg_eval.h).  The reference leaves its evaluator hook empty for them
  * (training_builder/base_train_builder.py:64-65); the scores are those of evaluation/segmentation_metric_calculation.py:71-94

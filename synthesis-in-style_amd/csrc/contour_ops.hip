@@ -187,3 +187,4 @@ extern "C" int sis_remove_small_contours(float* out, const float* pred, void* wo
 
 #include "coco_gt.h"   // the dataset's ground truth: region tables and COCO run lengths on the same labelling kernels
 #include "page_visual.h"   // page visualisation: regions of whole pages, colouring, outlines and crops on the same kernels
+#include "scan_margin.h"   // scanner-margin removal: Canny front, hysteresis, closing and contour boxes on the same kernels

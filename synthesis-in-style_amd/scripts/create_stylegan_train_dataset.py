@@ -23,7 +23,12 @@ What differs from the reference:
 * Files are decoded IN FULL and converted to RGB before anything else, on both paths.  The reference calls ``thumbnail`` on
   the still lazy file, where Pillow's ``draft`` lets a JPEG decode at a DCT scale when it is to shrink 2x or more: JPEG
   sources give other pixels than the reference there, PNG and TIFF sources the same.
-* ``--margin-remove`` is not built and raises: it needs Canny and a contour hierarchy, and OpenCV is not a dependency.
+* ``--margin-remove`` runs on the device path only: ``sis_hip.scan_remove_margin`` finds the content box of every decoded page
+  on its 1000-pixel thumbnail (blur, Canny, closing, contour boxes and the largest-gap cut of the reference's
+  ``get_content_box``, stated in integers in DESIGN.md §20 and run by csrc/scan_margin.h) and crops the page before anything
+  else, as the reference does.  The statement follows OpenCV's documented behaviour; OpenCV is not a dependency and nothing was
+  compared with it.  With ``--pixel-path pil`` the option still raises: there is no host implementation.  The random stream
+  does not see the option: one ``--seed`` gives the same names, factors and lists with and without it.
 * No progress bars (tqdm is not a dependency).
 """
 import argparse
@@ -38,7 +43,7 @@ if __name__ == "__main__":   # run as a file: the package root is the directory 
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from data.segmentation_dataset import is_image
-from utils.scan_patches import patch_origins, random_resize_size, window_starts
+from utils.scan_patches import ANALYSIS_SIZE, patch_origins, random_resize_size, window_starts
 
 PIXEL_PATHS = ("device", "pil")
 PNG_ENCODERS = ("device", "pil")
@@ -74,14 +79,17 @@ def page_patches_pil(image, factor: int, image_size: int, max_size: int, min_siz
     return crop_patches(image, image_size)
 
 
-def page_patches_device(image, factor: int, image_size: int, max_size: int, min_size: int, device):
-    """One decoded page -> its patches as uint8 [n, size, size, 3] on the device, the same pixels as ``page_patches_pil``."""
+def page_patches_device(image, factor: int, image_size: int, max_size: int, min_size: int, device, margin_remove: bool = False):
+    """One decoded page -> its patches as uint8 [n, size, size, 3] on the device, the same pixels as ``page_patches_pil``.
+    ``margin_remove``: the scanner margin is cropped off first (``sis_hip.scan_remove_margin``, one host read of four integers)."""
     import numpy
     import torch
     import sis_hip
     host = torch.empty((image.height, image.width, 3), dtype=torch.uint8, pin_memory=True)
     numpy.copyto(host.numpy(), numpy.asarray(image, dtype=numpy.uint8))
     page = host.to(device, non_blocking=True)
+    if margin_remove:
+        page = sis_hip.scan_remove_margin(page, ANALYSIS_SIZE)[0]
     if any(side > max_size for side in (page.shape[1], page.shape[0])):
         page = sis_hip.scan_thumbnail(page, max_size)
     new_size = random_resize_size(int(page.shape[1]), int(page.shape[0]), factor, min_size)
@@ -129,6 +137,8 @@ def resolve_paths(args):
     png_encoder = getattr(args, "png_encoder", None) or ("device" if pixel_path == "device" else "pil")
     if pixel_path not in PIXEL_PATHS or png_encoder not in PNG_ENCODERS:
         raise ValueError(f"pixel path {pixel_path!r}, PNG encoder {png_encoder!r}: each must be one of {PIXEL_PATHS}")
+    if getattr(args, "margin_remove", False) and pixel_path != "device":
+        raise NotImplementedError(MARGIN_REMOVE_MESSAGE)
     return pixel_path, png_encoder
 
 
@@ -153,6 +163,7 @@ def cut_patches(args, root_dir: Path, destination: Path, rng):
     num_files_to_use = min(len(files_in_root), args.max_num_samples)
     rng.shuffle(files_in_root)
     image_size, max_size, min_size = args.image_size, args.max_size, getattr(args, "min_size", 1000)
+    margin_remove = bool(getattr(args, "margin_remove", False))
 
     patch_paths = []
     pending = None   # (names, host buffer, host sizes, event) of the page before: written while this page's kernels run
@@ -178,7 +189,7 @@ def cut_patches(args, root_dir: Path, destination: Path, rng):
                     patches = page_patches_pil(image, factor, image_size, max_size, min_size)
                     count = len(patches)
                 else:
-                    pixels = page_patches_device(image, factor, image_size, max_size, min_size, device)
+                    pixels = page_patches_device(image, factor, image_size, max_size, min_size, device, margin_remove)
                     count = int(pixels.shape[0])
                 names = [dest_dir / f"{file_path.stem}_{patch_idx}.png" for patch_idx in range(count)]
                 if png_encoder == "pil":
@@ -210,8 +221,7 @@ def cut_patches(args, root_dir: Path, destination: Path, rng):
 
 
 def main(args: argparse.Namespace):
-    if args.margin_remove:
-        raise NotImplementedError(MARGIN_REMOVE_MESSAGE)
+    resolve_paths(args)   # declines what is not built (--margin-remove off the device path) before anything is written
     seed = getattr(args, "seed", None)
     rng = random.Random(seed) if seed is not None else random
     root_dir = Path(args.root_dir)
@@ -241,7 +251,8 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--only-jsons", action='store_true', default=False, help="cut nothing: write the two lists from the patches the destination already holds")
     parser.add_argument("--max-size", type=int, default=3000, help="a scan with a longer side is shrunk to this side first")
     parser.add_argument("--margin-remove", action='store_true', default=False,
-                        help="not built (raises): margin removal needs Canny and a contour hierarchy, and OpenCV is not a dependency")
+                        help="crop the scanner margin off every page first (the reference does it with OpenCV's Canny and findContours; here "
+                        "--pixel-path device does it with the kernels of csrc/scan_margin.h, DESIGN.md §20; --pixel-path pil raises)")
     parser.add_argument("--filter", help="use only scans whose path contains this expression")
     parser.add_argument("--seed", type=int, default=None, help="seed of the host random stream: the shuffle of the files, the downsample "
                         "factor 1..4 of every page, the shuffle before the 90/10 split")

@@ -234,6 +234,8 @@ _SIGNATURES = {
     "sis_scan_resample_workspace_bytes": ([_i] * 4, _i64),
     "sis_scan_resample": ([_vp, _vp] + [_i] * 4 + [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i64, _vp], _i),
     "sis_scan_patches": ([_vp, _vp, _vp] + [_i] * 4 + [_vp], _i),
+    "sis_scan_content_box_workspace_bytes": ([_i, _i], _i64),
+    "sis_scan_content_box": ([_vp] * 4 + [_i, _vp] + [_i] * 4 + [_vp, _i64, _vp], _i),
     "sis_seg_eval_workspace_bytes": ([_i] * 4, _i64),
     "sis_seg_eval": ([_vp] * 4 + [_i, _vp] + [_i] * 6 + [_vp], _i),
 }
@@ -3949,3 +3951,55 @@ def scan_patches(page, origins, size):
         _check(_launch("scan_patches_kernel", 0.0, 2.0 * out.numel(),
                        lambda: lib().sis_scan_patches(_ptr(out), _ptr(page), _ptr(table), n, size, h, w, _stream())), "sis_scan_patches")
     return out
+
+
+# ------------------------------------------------------------------------------ scanner margin (csrc/scan_margin.h)
+SCAN_MARGIN_MIN_SIDE, SCAN_MARGIN_MAX_SIDE = 3, 4096
+ScanContentBox = collections.namedtuple("ScanContentBox", "box info edges contours")
+
+
+def scan_content_box(page, low=20, high=150, edges=False, max_contours=0):
+    """uint8 [h, w, 3] analysis image (device, 3 <= h, w <= 4096) -> a ``ScanContentBox`` of device tensors (the
+    reference's ``get_content_box`` with ``edge_detect=True``): ``box`` int32 [4] = x0, y0, x1, y1 with exclusive ends, ``info``
+    int32 [8] = contours, outer contours, largest box area, contours kept, decision (0 cut at the largest gap of the box areas,
+    1 at most one contour, 2 largest area below 0.6 of the image: the last two give the whole image), T, pixels of E, 0;
+    ``edges`` uint8 [h, w] = the closed edge image E as 0 / 255 (None unless asked for); ``contours`` int32 [max_contours, 6] =
+    kind (0 outer, 1 hole), root, x0, y0, w, h in the order outers by root, then holes by root (None for 0), rows from
+    ``info[0]`` on not written.  Fixed launch sequence on the current stream, no host sync."""
+    page = _scan_page(page, "scan_content_box")
+    h, w = int(page.shape[0]), int(page.shape[1])
+    max_contours = int(max_contours)
+    if not (SCAN_MARGIN_MIN_SIDE <= h <= SCAN_MARGIN_MAX_SIDE and SCAN_MARGIN_MIN_SIDE <= w <= SCAN_MARGIN_MAX_SIDE):
+        raise RuntimeError(f"scan_content_box: image {h} x {w} outside {SCAN_MARGIN_MIN_SIDE}..{SCAN_MARGIN_MAX_SIDE} a side")
+    if max_contours < 0:
+        raise RuntimeError("scan_content_box: negative max_contours")
+    dev = page.device
+    box = torch.empty((4,), dtype=torch.int32, device=dev)
+    info = torch.empty((8,), dtype=torch.int32, device=dev)
+    edge_image = torch.empty((h, w), dtype=torch.uint8, device=dev) if edges else None
+    table = torch.empty((max_contours, 6), dtype=torch.int32, device=dev) if max_contours > 0 else None
+    ws_bytes = int(lib().sis_scan_content_box_workspace_bytes(h, w))
+    ws = torch.empty(((max(ws_bytes, 4) + 3) // 4,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _check(_launch("margin_front_kernel", 0.0, 60.0 * h * w,
+                       lambda: lib().sis_scan_content_box(_ptr(box), _ptr(info), _ptr(edge_image), _ptr(table), max_contours, _ptr(page),
+                                                          h, w, int(low), int(high), _ptr(ws), ws.numel() * 4, _stream())),
+               "sis_scan_content_box")
+    return ScanContentBox(box, info, edge_image, table)
+
+
+def scan_remove_margin(page, analysis_size=1000):
+    """uint8 [H, W, 3] page (device) -> (cropped page, box, crop): the reference's ``remove_scanning_margin``.  ``box`` is the
+    content box of ``scan_thumbnail(page, analysis_size)`` (``scan_content_box``), ``crop`` that box scaled to the page
+    (``utils.scan_patches.scale_bounding_box``), both Python lists [x0, y0, x1, y1]; the cropped page is contiguous.
+    ONE host read, of ``box``: the sizes of the thumbnails that follow are decided on the host from the size of the cropped
+    page, so the crop has to be known there."""
+    from utils import scan_patches as tables
+    page = _scan_page(page, "scan_remove_margin")
+    analysis = scan_thumbnail(page, analysis_size)
+    box = [int(v) for v in scan_content_box(analysis).box.tolist()]   # the one host read
+    crop = tables.scale_bounding_box(box, (int(analysis.shape[1]), int(analysis.shape[0])), (int(page.shape[1]), int(page.shape[0])))
+    window = page[crop[1]:crop[3], crop[0]:crop[2]]
+    cropped = torch.empty(tuple(window.shape), dtype=torch.uint8, device=page.device)
+    cropped.copy_(window)
+    return cropped, box, crop

@@ -7,7 +7,9 @@ before a pixel is touched, restated in Python floats so that the kernels are lef
 - ``thumbnail_plan``: the three composed, as ``sis_hip.scan_thumbnail`` runs them;
 - ``patch_origins``: the windows of the reference's ``crop_patches`` (scripts/create_stylegan_train_dataset.py:18-34), each
   bound rounded as ``Image.crop`` rounds it (Python's ``round``: .5 goes to even);
-- ``random_resize_size``: the size the reference's ``random_resize`` (:37-46) hands to ``thumbnail``.
+- ``random_resize_size``: the size the reference's ``random_resize`` (:37-46) hands to ``thumbnail``;
+- ``scale_bounding_box``: the reference's function of that name (:114-129), which carries the content box found on the
+  ``ANALYSIS_SIZE`` thumbnail (``sis_hip.scan_content_box``) over to the page.
 
 Sizes are (width, height) as Pillow writes them."""
 import functools
@@ -17,6 +19,7 @@ from typing import List, NamedTuple, Optional, Tuple
 
 PRECISION_BITS = 22          # Pillow: 32 - 8 - 2
 BICUBIC_SUPPORT = 2.0
+ANALYSIS_SIZE = 1000         # the side of the thumbnail that the reference's remove_scanning_margin (:132-138) looks for the margin on
 
 
 def c_float(value: float) -> float:
@@ -173,3 +176,14 @@ def patch_origins(width: int, height: int, image_size: int) -> List[Tuple[int, i
 
     columns = rounded(window_starts(width, image_size))
     return [(x, y) for y in rounded(window_starts(height, image_size)) for x in columns]
+
+
+def scale_bounding_box(box, box_extent, new_extent) -> List[int]:
+    """``box`` = [x0, y0, x1, y1] found on an image of ``box_extent`` = (width, height), carried to ``new_extent``: every bound
+    times the axis' float factor, truncated by ``int`` -- written as the reference writes it."""
+    box_width, box_height = box_extent
+    new_width, new_height = new_extent
+    width_factor = new_width / box_width
+    height_factor = new_height / box_height
+    new_box = [box[0] * width_factor, box[1] * height_factor, box[2] * width_factor, box[3] * height_factor]
+    return list(map(int, new_box))
